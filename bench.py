@@ -2,7 +2,8 @@
 """Headline benchmark: megapixels/s of tiled 4x super-resolution of 1080p frames (model a4 = Net4x,
 256-px tiles with 5-px overlap: BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3     (plain: set up, warm up, time the steps, print the line; --dump-outputs DIR also writes the last step's result)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full     (+ every leg below: roofline objects, CPU baseline + parity gate, configs 3-5, ...)
     python bench.py --gpus N ...                       (started plainly: re-executes itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W          (the driver's form)
@@ -20,9 +21,9 @@ split operands on conv_input2 + the first ARSB, ~22-bit tail weights), the mode 
 Weights: `a4` is absent from the reference mount (.MISSING_LARGE_BLOBS); a synthetic Net4x in the zoo's exact
 schema/format is used (tests/golden_defs.py: a2's real trunk + its upsampler duplicated), written and re-read
 through the legacy-format file path.  Inputs: the headline is a seeded natural-image-like synthetic frame; the
-SURVEY 8(d) input (seed-0 uniform uint8 noise / 255) is timed and parity-checked as a second input (`inputs`).
+SURVEY 8(d) input (seed-0 uniform uint8 noise / 255) is timed and parity-checked as a second input under --full (`inputs`).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line under --full (a plain run prints the headline keys, `config`, `device`, `inputs` and `summary` only):
   roofline          the kernel group with the largest share of the frame among the ones bracketed by hipEvents on the launch stream
                     (the two 3x3 64->256 implicit-GEMM convs at 2x resolution -- R and U branch are timed SEPARATELY, they run different
                     epilogues -- and the one-launch ARSBs).  `achieved` / `frac` use ALGORITHMIC FLOPs (the frame's pixels,
@@ -45,7 +46,7 @@ Extra objects on the JSON line:
   cpu_baseline      the oracle (a port of the reference's PyTorch-CPU fp32 path, proven equal to it on the goldens) timed on
                     this host with one socket's physical cores on a full tile row (8 tiles) + the ragged corner of the same
                     frame, and on BASELINE config 1 (256x256, a2) in full; rank 0 only.
-Parity gate (same oracle tiles): the worst max-abs error of the engine's fp32 tile results vs the oracle over BOTH inputs must be
+Parity gate (--full, same oracle tiles): the worst max-abs error of the engine's fp32 tile results vs the oracle over BOTH inputs must be
 <= 1e-3, and the delivered fp16 canvas must equal those tiles to fp16 rounding (<= 1e-3 + half an fp16 ulp of the value); otherwise every
 rank exits non-zero.
 """
@@ -119,8 +120,15 @@ def main():
     ap.add_argument('--no-floor', action='store_true', help='config 2: skip the value_floor legs (the same frame with six split-operand blocks / in fp16x3)')
     ap.add_argument('--no-pmc', action='store_true', help='config 2: do not try the rocprofv3 --pmc passes over a short child of this command (`traffic` then comes from the committed, '
                     'digest-gated profiles/pmc_bench.json)')
+    ap.add_argument('--full', action='store_true', help='config 2: every leg besides the headline (roofline objects, value_floor, power_roofline, I/O edges, sustained leg, noise input, '
+                    'drop-in loop, CPU baseline + parity gate, configs 3 / 4 / 5, the first-contact step of --gpus N); the --no-* options skip single legs of it.  Without it a '
+                    'run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='config 2: after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, '
+                    'a fixed sample of each canvas: see _dump_outputs)')
     args = ap.parse_args()
     args.steps_given = any(a == '--steps' or a.startswith('--steps=') for a in sys.argv[1:])
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started plainly: become the launcher (one rank per GPU, rendezvous on the loopback address); the ranks re-enter main()
@@ -131,7 +139,12 @@ def main():
 
     if args.config != 2:
         import bench_extra
+        if args.dump_outputs:
+            ap.error('--dump-outputs applies to config 2 only')
         return bench_extra.run_config(args.config, args)
+    if not args.full:       # a plain run: the headline alone, every optional leg off
+        args.no_floor = args.no_pmc = args.no_extras = args.no_noise_input = args.no_dropin_loop = args.no_cpu_baseline = args.no_configs = True
+        args.sustain = 0.0
 
     import numpy as np
     import torch
@@ -211,20 +224,23 @@ def main():
             v = float(t.item())
         return v
 
-    def timed(fr, steps, fn=None):
+    def timed(fr, steps, fn=None, keep=None):
         fn = fn or step
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn(fr)
+            out = fn(fr)
         fence()
-        return all_max(time.perf_counter() - t0)
+        dt = all_max(time.perf_counter() - t0)
+        if keep is not None:
+            keep.append(out)
+        return dt
 
     in_mp = nframes * FRAME[1] * FRAME[2] / 1e6
     # ---- first contact of the multi-rank path with real links: before anything is timed, one step whose result is held, bit for bit, against a
     # single-rank doCrop of the same frame on every rank that holds a piece of it; how many ranks took part comes out of an all-reduce, not out of WORLD_SIZE
     first_contact = None
-    if world > 1:
+    if world > 1 and args.full:
         from moephoto_amd import dist as mdist
         got = step(frames)
         worst = 0.0
@@ -247,12 +263,19 @@ def main():
         del got
     for _ in range(args.warmup):
         step(frames)
-    model.set_profile(','.join([g[0] for g in GROUPS] + HBM_KEYS + ['tailadd']))      # hipEvent pairs on the launch stream around the launches of each group
-    dt = timed(frames, args.steps)
-    profs = model.get_profile(all_keys=True)
-    model.set_profile(None)
+    if args.full:       # the roofline legs' live kernel timing
+        model.set_profile(','.join([g[0] for g in GROUPS] + HBM_KEYS + ['tailadd']))      # hipEvent pairs on the launch stream around the launches of each group
+    last = []
+    dt = timed(frames, args.steps, keep=last)
+    profs = []
+    if args.full:
+        profs = model.get_profile(all_keys=True)
+        model.set_profile(None)
     ms_per_step = dt / args.steps * 1e3
     value = in_mp / (ms_per_step / 1e3)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last[0])
+    del last
 
     res = {
         'metric': 'megapixels/sec (input), 1080p 4x SR (Net4x a4), 256-px tiles with overlap',
@@ -306,7 +329,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_pmc:
         pmc = _pmc_live()
         pmc_source = 'this run' if pmc else None
-    if not pmc:
+    if not pmc and profs:
         pmc = _pmc_table()
         pmc_source = 'committed' if pmc else None
     kernels = []
@@ -338,7 +361,7 @@ def main():
     kernels.sort(key=lambda k: -k['ms_per_frame'])
     # what the package power cap lets the matrix pipe deliver on operands whose bits toggle: a loop of nothing but v_mfma_f32_32x32x16_f16 on uniform random
     # fp16 data (tools/micro/mfma_power.hip), measured here on this box -- the practical ceiling beside the nominal peak every `frac` is quoted against
-    power = _power_roofline() if (rank == 0 and world == 1) else None      # (single-GPU runs only: a second process on the device has no place in a scaling run)
+    power = _power_roofline() if (args.full and rank == 0 and world == 1) else None      # (single-GPU runs only: a second process on the device has no place in a scaling run)
     if power:
         res['power_roofline'] = power
         for k in kernels:
@@ -598,6 +621,45 @@ def main():
         dist.destroy_process_group()
     if not parity_ok:
         raise SystemExit('parity gate failed: the engine differs from the oracle by more than {} (tiles) or the fp16 canvas by more than that plus half an ulp'.format(PARITY_TOL))
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: all files of all ranks together, up to 16 ranks (each rank writes at least its window and sums, ~3.4 MB)
+DUMP_SAMPLE = 1 << 22       # sampled elements of one canvas (at most)
+DUMP_WINDOW = (896, 896, 512)       # top, left, side of the full-resolution window: it spans the first inner tile seams of the 4x canvas
+
+
+def _dump_outputs(path, out):
+    """--dump-outputs: what the last timed step returned, written so that two builds can be compared output for output.  A step returns an fp16
+    canvas (3 x 4320 x 7680: 398 MB as float32), so per canvas this writes a fixed sample of it:
+      <name>_sample.npy     float32, the elements at seeded positions of the flattened canvas (sorted, the same positions in every run)
+      <name>_window.npy     float32, the full-resolution window DUMP_WINDOW (3 x 512 x 512)
+      <name>_row_sums.npy   float64, per plane and row;  <name>_col_sums.npy  float64, per plane and column (every element enters both)
+    <name>: `canvas` on one GPU; `frame<f>` for the frames a rank stitched under --gpus N; `frame<f>_rows<y0>_<y1>` for a rank's row band under --strong.
+    Each rank writes what it holds, one canvas or band; the sample shrinks with the rank count to keep all files within DUMP_BYTES (up to 16 ranks)."""
+    import numpy as np
+    import torch
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    parts = [('canvas', out)]
+    if isinstance(out, dict):               # --gpus N: {frame: canvas} of the frames this rank stitched; --strong: {frame: (first row, row band)}
+        parts = []
+        for f, v in sorted(out.items()):
+            if not isinstance(v, tuple):
+                parts.append(('frame%d' % f, v))
+            elif v[1].shape[-2]:            # (a rank whose band holds no rows writes nothing)
+                parts.append(('frame%d_rows%d_%d' % (f, v[0], v[0] + v[1].shape[-2]), v[1]))
+    os.makedirs(path, exist_ok=True)
+    top, left, side = DUMP_WINDOW
+    for name, y in parts:
+        C, H, W = y.shape
+        win = y[:, min(top, H):min(top + side, H), min(left, W):min(left + side, W)]
+        fixed = win.numel() * 4 + C * (H + W) * 8 + 4096       # (+ the four .npy headers)
+        n = min(DUMP_SAMPLE, max(1 << 16, (DUMP_BYTES // max(1, world) - fixed) // 4))
+        idx = np.unique(np.random.default_rng(20240601).integers(0, y.numel(), n))
+        flat = y.reshape(-1)
+        np.save(os.path.join(path, name + '_sample.npy'), flat[torch.from_numpy(idx).to(y.device)].float().cpu().numpy())
+        np.save(os.path.join(path, name + '_window.npy'), win.float().cpu().numpy())
+        np.save(os.path.join(path, name + '_row_sums.npy'), y.sum(dim=-1, dtype=torch.float64).cpu().numpy())
+        np.save(os.path.join(path, name + '_col_sums.npy'), y.sum(dim=-2, dtype=torch.float64).cpu().numpy())
 
 
 def _reference_style_loop(opt, x, plan, ramp, torch, blend_tile=None):

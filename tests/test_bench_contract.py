@@ -86,3 +86,43 @@ def test_pmc_summary_names_its_tree():
     assert isinstance(d.get('source_sha256'), str) and len(d['source_sha256']) == 64
     for g in ('convt_R1.up1', 'u.up1', 'arsb', 'exact'):            # the groups bench.py looks its `traffic` fields up under
         assert g in d['groups'] and d['groups'][g]['hbm_bytes_per_frame'] > 0, g
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample_of_the_canvas(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's fp16 canvas (3 x 4320 x 7680) as float32 / float64 .npy files -- the same positions in every run, every
+    element inside the row / column sums, all files of all ranks of one node within 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.delenv('WORLD_SIZE', raising=False)
+    y = torch.rand((3, 4320, 7680), generator=torch.Generator().manual_seed(0)).half()
+    bench._dump_outputs(str(tmp_path / 'a'), y)
+    bench._dump_outputs(str(tmp_path / 'b'), y.clone())
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['canvas_col_sums.npy', 'canvas_row_sums.npy', 'canvas_sample.npy', 'canvas_window.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= bench.DUMP_BYTES
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    top, left, side = bench.DUMP_WINDOW
+    assert np.array_equal(np.load(tmp_path / 'a' / 'canvas_window.npy'), y[:, top:top + side, left:left + side].float().numpy())
+    y[2, 4000, 7000] += 0.5                     # one element that neither the sample nor the window needs to hold
+    bench._dump_outputs(str(tmp_path / 'c'), y)
+    for n in ('canvas_row_sums.npy', 'canvas_col_sums.npy'):
+        assert not np.array_equal(np.load(tmp_path / 'a' / n), np.load(tmp_path / 'c' / n)), n
+    # --gpus 8: each rank writes the frame it stitched, within an eighth of the budget
+    monkeypatch.setenv('WORLD_SIZE', '8')
+    bench._dump_outputs(str(tmp_path / 'r'), {5: y})
+    names = sorted(os.listdir(tmp_path / 'r'))
+    assert names == ['frame5_col_sums.npy', 'frame5_row_sums.npy', 'frame5_sample.npy', 'frame5_window.npy']
+    assert sum(os.path.getsize(tmp_path / 'r' / n) for n in names) <= bench.DUMP_BYTES // 8
+    # --gpus 16 --strong: {frame: (first row, row band)}; a rank whose band holds no rows writes nothing
+    monkeypatch.setenv('WORLD_SIZE', '16')
+    bench._dump_outputs(str(tmp_path / 's'), {0: (1080, y[:, 1080:1350])})
+    names = sorted(os.listdir(tmp_path / 's'))
+    assert names == ['frame0_rows1080_1350_col_sums.npy', 'frame0_rows1080_1350_row_sums.npy', 'frame0_rows1080_1350_sample.npy', 'frame0_rows1080_1350_window.npy']
+    assert np.array_equal(np.load(tmp_path / 's' / 'frame0_rows1080_1350_row_sums.npy'), np.load(tmp_path / 'c' / 'canvas_row_sums.npy')[:, 1080:1350])
+    bench._dump_outputs(str(tmp_path / 'e'), {0: (4320, y[:, 4320:])})
+    assert os.listdir(tmp_path / 'e') == []
+    bench._dump_outputs(str(tmp_path / 'f'), {3: y})     # a full canvas: 16 ranks' files still fit DUMP_BYTES
+    assert sum(os.path.getsize(tmp_path / 'f' / n) for n in os.listdir(tmp_path / 'f')) <= bench.DUMP_BYTES // 16

@@ -478,7 +478,7 @@ def test_dist_two_ranks_on_one_gpu_over_rccl(dev):
 def test_bench_gpus2_strong_scaling_one_frame_over_the_ranks(dev):
     """`python bench.py --gpus 2 --strong`: ONE 1080p frame per step, its 40 tiles dealt over the ranks, every rank folding its row band of the canvas
     (dist.run_frame_bands) -- the north star's "tiles of a frame across the GPUs" -- with "scaling": "strong" on the line; shared-GPU mode."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--strong', '--steps', '2', '--warmup', '1', '--sustain', '0', '--cpu-tiles', '2', '--no-noise-input']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--strong', '--steps', '2', '--warmup', '1', '--full', '--sustain', '0', '--cpu-tiles', '2', '--no-noise-input']
     p = subprocess.run(cmd, cwd=ROOT, env=_shared_gpu_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{') and '"metric"' in l]
@@ -495,7 +495,7 @@ def test_bench_gpus2_strong_scaling_one_frame_over_the_ranks(dev):
 def test_bench_gpus3_on_grouped_isend_irecv(dev):
     """The exchange's second form (dist._p2p_exchange: one isend + one irecv per peer, batched -- what an all_to_all_single failure falls back to) under `bench.py --gpus 3`
     in shared-GPU mode, MOE_DIST_EXCHANGE=p2p: the line says which form ran, and the first-contact comparison holds every rank's frames bit for bit against single-rank doCrop."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--steps', '2', '--warmup', '1', '--sustain', '0', '--no-cpu-baseline', '--no-noise-input']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--steps', '2', '--warmup', '1', '--full', '--sustain', '0', '--no-cpu-baseline', '--no-noise-input']
     p = subprocess.run(cmd, cwd=ROOT, env=dict(_shared_gpu_env(), MOE_DIST_EXCHANGE='p2p'), capture_output=True, text=True, timeout=900)
     if p.returncode != 0:
         try:
@@ -512,7 +512,7 @@ def test_bench_gpus3_on_grouped_isend_irecv(dev):
 def test_bench_gpus2_started_plainly(dev):
     """`python bench.py --gpus 2` with NO torchrun around it (the way the driver starts its N = 1 run): it must re-launch itself as two
     ranks, run the sharded step, and rank 0 must print one JSON line with n_gpus 2 whose parity gate ran."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--sustain', '0', '--cpu-tiles', '9']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--sustain', '0', '--cpu-tiles', '9']
     t0 = time.time()
     p = subprocess.run(cmd, cwd=ROOT, env=_shared_gpu_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]

@@ -8,7 +8,7 @@ OUT=gpurun_out/prof
 mkdir -p $OUT
 STEPS=${PROF_STEPS:-3}
 # 1. per-kernel time of the benchmark command
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -f csv -- python bench.py --steps $STEPS --warmup 1 --no-cpu-baseline > $OUT/stats_stdout.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -f csv -- python bench.py --steps $STEPS --warmup 1 --full --no-cpu-baseline > $OUT/stats_stdout.log 2>&1
 echo "stats rc=$?" >> $OUT/stats_stdout.log
 # 2. counters on the fixed Net4x workload, conv kernel only
 timeout 120 rocprofv3-avail list > $OUT/counters_avail.txt 2>&1 || timeout 120 rocprofv3 -L > $OUT/counters_avail.txt 2>&1
