@@ -1587,9 +1587,13 @@ int run_forward(moe_net& n, Fwd& f, const void* x, int x_dtype, long long sB, lo
         const bool fuse1 = n.opt.fuse_tail && !f.direct && !n.debug && n.stages >= 1;
         float* part[2] = {nullptr, nullptr};
         // fp16 input and the table of this checkpoint's U branch at hand (moe_net::lut): the U branch is not run, the final sum looks its value up
-        const bool use_lut = !f.dry() && !f.lut_capture && fuse1 && x_dtype == MOE_F16 && n.lut_state == 1 && n.lut && n.opt.lite_lut;
+        // -- decided after branch 0: a launch set whose R tail came out in the two-part form (conv1x1 refused its 32-bit offsets) computes the U branch as well
+        bool use_lut = !f.dry() && !f.lut_capture && fuse1 && x_dtype == MOE_F16 && n.lut_state == 1 && n.lut && n.opt.lite_lut;
         for (int br = 0; br < 2; ++br) {
-            if (br == 1 && use_lut) { H = h * n.scale; W = w * n.scale; break; }
+            if (br == 1 && use_lut) {
+                if (f.tail1_parts == 1) { H = h * n.scale; W = w * n.scale; break; }
+                use_lut = false;
+            }
             Act cur = br == 0 ? Bb : A;
             H = h; W = w;
             for (int st = 0; st < n.stages; ++st) {
@@ -1641,7 +1645,6 @@ int run_forward(moe_net& n, Fwd& f, const void* x, int x_dtype, long long sB, lo
                     HIP_TRY(hipMemcpyAsync(f.lut_capture, part[1], (size_t)H * W * 4, hipMemcpyDeviceToDevice, s));
                     return MOE_OK;
                 }
-                if (use_lut && f.tail1_parts != 1) return fail(MOE_EINVAL, "lite: the U-branch table needs the one-part form of the fused tail");
                 Tail1SumArgs t{};
                 t.p0 = part[0]; t.p1 = use_lut ? nullptr : part[1]; t.nparts = f.tail1_parts; t.y = y; t.y_dtype = y_dtype; t.y_off = y_off_dev; t.B = B; t.H = H; t.W = W;
                 if (use_lut) { t.lut = n.lut; t.r = n.scale; t.x = x; t.x_off = x_off_dev; t.sB = sB; t.sH = sH; t.sW = sW; t.vec_ok = f.y_vec; }
@@ -1669,12 +1672,8 @@ int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int h, int 
 // The table of lite's U branch (moe_net::lut), filled on the first fp16 forward of a checkpoint: one ordinary forward of the net on a 256 x 256 one-plane image whose pixel
 // (i, j) holds the fp16 bit pattern 256 i + j; run_forward copies the U branch's plane (part[1]) instead of summing.  Not during stream capture (it allocates), not for
 // precisions / options whose fused tail is not the one-part form (then the table stays unavailable and the branch is computed as before).
-static void build_lite_lut(moe_net& n, hipStream_t s)
+static void build_lite_lut_on_device(moe_net& n, hipStream_t s)
 {
-    n.lut_state = -1;
-    if (n.arch != MOE_ARCH_LITE || !n.opt.lite_lut || n.debug || !n.opt.fuse_tail || n.precision == MOE_PREC_DEBUG_DIRECT) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); n.lut_state = 0; return; }      // (another forward may try)
     const int r = n.scale;
     std::vector<unsigned short> pat(65536);
     for (int i = 0; i < 65536; ++i) pat[(size_t)i] = (unsigned short)i;
@@ -1690,11 +1689,23 @@ static void build_lite_lut(moe_net& n, hipStream_t s)
     n.lut_state = 1;
 }
 
+static void build_lite_lut(moe_net& n, hipStream_t s)
+{
+    n.lut_state = -1;
+    if (n.arch != MOE_ARCH_LITE || !n.opt.lite_lut || n.debug || !n.opt.fuse_tail || n.precision == MOE_PREC_DEBUG_DIRECT) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); n.lut_state = 0; return; }      // (another forward may try)
+    // the table, its input and the scratch live on the net's device, whichever device the caller has current; the caller's current device is left as it was
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || (cur != n.device && hipSetDevice(n.device) != hipSuccess)) { (void)hipGetLastError(); n.lut_state = 0; return; }
+    build_lite_lut_on_device(n, s);
+    if (cur != n.device) (void)hipSetDevice(cur);
+}
+
 int forward_dev(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
                 const long long* x_off_dev, void* y, int y_dtype, const long long* y_off_dev, hipStream_t s, bool y_off_mult8 = true)
 {
     if (!n.finalized) return fail(MOE_ESTATE, "moe_net_forward: net is not finalized (load_state_dict + to(device) first)");
-    if (n.arch == MOE_ARCH_LITE && x_dtype == MOE_F16 && n.lut_state == 0 && n.opt.lite_lut) build_lite_lut(n, s);
     if (B < 1 || h < 1 || w < 1) return fail(MOE_EINVAL, "moe_net_forward: bad shape B=%d h=%d w=%d", B, h, w);
     if ((x_dtype != MOE_F32 && x_dtype != MOE_F16) || (y_dtype != MOE_F32 && y_dtype != MOE_F16))
         return fail(MOE_EINVAL, "moe_net_forward: x/y dtype must be MOE_F32 or MOE_F16");
@@ -1704,6 +1715,7 @@ int forward_dev(moe_net& n, const void* x, int x_dtype, int B, int h, int w, lon
     if (bmax < 1)
         return fail(MOE_ENOMEM, "a %dx%d tile exceeds the convolution kernels' addressing range (%lld pixels per plane at most for this net): use a smaller cropsize",
                     h, w, kSpRange / sp_bytes_per_pixel(n));
+    if (n.arch == MOE_ARCH_LITE && x_dtype == MOE_F16 && n.lut_state == 0 && n.opt.lite_lut) build_lite_lut(n, s);      // (after the checks: a refused call builds nothing)
     if (B <= bmax) return forward_dev_chunk(n, x, x_dtype, B, h, w, sB, sH, sW, x_off_dev, y, y_dtype, y_off_dev, s, y_off_mult8);
     const size_t xe = x_dtype == MOE_F32 ? 4 : 2, ye = y_dtype == MOE_F32 ? 4 : 2;
     const long long yplane = (long long)h * n.scale * w * n.scale;

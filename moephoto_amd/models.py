@@ -247,7 +247,12 @@ class EngineModule(object):
         (python/imageProcess.py:164-170: every tile is a slice of one padded image that exists before the loop); consecutive forwards then overlap inside the engine
         (include/moephoto_amd.h).  Anything else -- a new image, an input produced between the calls, another stream -- gets plain stream order."""
         base = x._base if x._base is not None else x
-        key = (base._version, stream)
+        try:
+            key = (base._version, stream)
+        except RuntimeError:      # an inference tensor (torch.inference_mode) has no version counter: nothing shows that x is unchanged -- plain stream order
+            self._last_input = None
+            self._last_flag = 0
+            return 0
         last = self._last_input
         flag = _lib.FWD_INPUT_SINCE_PREV if (last is not None and last[0]() is base and last[1] == key) else 0
         self._last_input = (weakref.ref(base), key)

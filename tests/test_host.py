@@ -170,6 +170,25 @@ def test_module_protocol_without_gpu():
         Net(upscale=3)
 
 
+def test_input_since_prev_on_inference_tensors():
+    """EngineModule._input_since_prev (MOE_FWD_INPUT_SINCE_PREV) reads the input storage's version counter.  An inference tensor has none: the flag falls back to 0
+    (plain stream order) instead of raising, and the next ordinary call does not pair with it; two calls on one ordinary storage at one version still get the flag."""
+    from moephoto_amd.models import Net2x
+    m = Net2x()
+    img = torch.zeros((3, 1, 40, 48))
+    assert m._input_since_prev(img[:, :, :8, :16], 7) == 0
+    assert m._input_since_prev(img[:, :, 8:16, :16], 7) == _lib.FWD_INPUT_SINCE_PREV
+    with torch.inference_mode():
+        xi = torch.zeros((3, 1, 40, 48))
+        assert xi.is_inference()
+        for view in (xi, xi[:, :, :8, :16], xi[:, :, 8:16, :16]):
+            assert m._input_since_prev(view, 7) == 0 and m._last_flag == 0
+    assert m._input_since_prev(img[:, :, :8, :16], 7) == 0          # (the inference calls broke the pair)
+    assert m._input_since_prev(img[:, :, 8:16, :16], 7) == _lib.FWD_INPUT_SINCE_PREV
+    img.add_(1)
+    assert m._input_since_prev(img[:, :, :8, :16], 7) == 0          # (a write between the calls)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='checks the no-GPU failure mode')
 def test_fails_loudly_without_device():
     from moephoto_amd.models import Net2x
