@@ -153,12 +153,20 @@ int moe_net_get_profile(moe_net* net, double* total_ms, int64_t* launches, doubl
 /* MOE_PREC_MIXED only: how many leading ARSBs run with split operands (0..6; -1 = the calibrated count of these weights if there is one, else the
  * architecture's default: Net2x 4, Net3x 2, Net4x 1, NetDN 1).  Takes effect at the next forward. */
 int moe_net_set_exact_blocks(moe_net* net, int blocks);
-/* Kernel-form switches of one net, for A/B measurements and the parity tests that compare forms of one layer in-process
- * ("sp_impl" = "auto" | "rw" | "sp", "arsb_fuse" / "x3_fuse" / "conv1x1" / "fuse_tail" / "sedn_fuse" / "pool_fuse" = "0" | "1",
- * "tail_split" = "0" | "r" | "ru", "tail_form" = "sums" | "planes", "conv_impl" = "sp" | "v1", "tiles_per_batch", "max_groups",
- * "k48" = "0" | "1", "repeat" = "<layer key>:<n>" (measurement: the matching bracketed launches are issued n times -- tools/kernel_power.py), "x3_impl" = "auto" | "x3" | "q8" (the split-operand layers' kernel: three fp16 products, or the two
- * corrections on fp8 operands; auto = q8 for the SR nets), "lo8" = "on" | "off" (fp8 low parts between conv64_q8 layers)).
- * Defaults come from the MOE_* environment variables of the same names ONCE, at moe_net_create; the forward path itself reads no
+/* Kernel-form switches of one net, for A/B measurements and the parity tests that compare forms of one layer in-process.  Every key (the rows of
+ * the option table in csrc/options.cpp; defaults and the measurements behind them: NetOptions in csrc/net.h) with its values, the default first:
+ *   flags, "1" | "on" | "0" | "off":  "arsb_fuse", "x3_fuse", "exact_fuse", "conv1x1", "up_fuse2", "fuse_tail", "sedn_fuse", "s64", "pool_fuse",
+ *       "frm_pre", "stem2", "lite_lut", "k48", "lo8" (fp8 low parts between conv64_q8 layers), "branch_streams", "overlap_calls",
+ *       "auto_calibrate"; off by default: "overlap_fork", "calib_log"
+ *   "conv_impl" = "sp" | "v1";  "sp_impl" = "auto" | "rw" | "sp";  "up_impl" = "ps4" | "rw";  "tail_split" = "r" | "ru" | "0";
+ *   "tail_form" = "sums" | "planes";  "q8_impl" = "s" | "p";  "x3_impl" = "auto" | "x3" | "q8" (the split-operand layers' kernel: three fp16
+ *       products, or the two corrections on fp8 operands; auto = q8 for the SR nets and NetDN)
+ *   counts, a non-negative integer with 0 = the built-in choice:  "branch_groups", "overlap_groups", "tiles_per_batch", "max_groups"
+ *   "dbg" = an integer (timing-ablation bits of the conv kernels: results are wrong when set), "trace_key" = a layer key
+ *   "repeat" = "<layer key>:<n>", n >= 1 (measurement: the matching bracketed launches are issued n times -- tools/kernel_power.py); "" | "0" clears
+ * A value the key does not have is refused with MOE_EINVAL and leaves the option as it was.
+ * Defaults come from the environment variables MOE_<KEY> ONCE, at moe_net_create ("calib_log" and "repeat" have none; a value the option does not
+ * have is reported on stderr and ignored); the forward path itself reads no
  * environment.  The reference has no such switches: its forward is torch.nn (python/imageProcess.py:391-395). */
 int moe_net_set_option(moe_net* net, const char* key, const char* value);
 /* keep fp32 copies of named intermediates during forwards (slow; debugging / layer-by-layer parity only) */

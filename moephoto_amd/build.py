@@ -10,8 +10,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'blend.hip', 'engine.cpp', 'planner.cpp']
-HEADERS = ['common.h', 'engine.h', os.path.join('..', '..', 'include', 'moephoto_amd.h')]
+SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'blend.hip',
+           'errors.cpp', 'options.cpp', 'weights.cpp', 'forward.cpp', 'forward_arsb.cpp', 'forward_sedn.cpp', 'forward_lite.cpp', 'calibrate.cpp', 'plan_run.cpp', 'planner.cpp']
+HEADERS = ['common.h', 'engine.h', 'net.h', 'rowtile.h', os.path.join('..', '..', 'include', 'moephoto_amd.h')]      # (paths from csrc/; the ABI header last)
 LIB = os.path.join(HERE, 'libmoephoto_amd.so')
 ARCH = 'gfx950'
 # packed fp32 VALU (v_pk_add_f32 / v_pk_fma_f32, formed by the SLP vectoriser) costs ~+11 cycles per instruction beside MFMAs
@@ -35,8 +36,7 @@ def source_digest():
     bench.py must not pair the PMC bytes of one tree with the timings of another (profiles/pmc_bench.json carries this digest)."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(SOURCES + ['common.h', 'engine.h', 'rowtile.h'])
-    for f in files + [os.path.join('..', '..', 'include', 'moephoto_amd.h')]:
+    for f in sorted(SOURCES + HEADERS[:-1]) + HEADERS[-1:]:
         h.update(f.encode())
         h.update(open(os.path.join(CSRC, f), 'rb').read())
     return h.hexdigest()
@@ -77,7 +77,7 @@ def build_lib(force=False, verbose=False):
         if old not in keep:
             os.remove(os.path.join(HERE, '_obj', old))
     extra = os.environ.get('MOE_HIPCC_FLAGS', '').split()        # experiments only, e.g. -DMOE_NO_SGB
-    hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS + ['rowtile.h'])
+    hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     jobs = []
     for src in SOURCES:
         obj = os.path.join(HERE, '_obj', os.path.splitext(src)[0] + '.o')

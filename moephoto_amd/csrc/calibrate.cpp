@@ -1,0 +1,132 @@
+// calibrate.cpp -- how many leading ARSBs of THIS checkpoint run with split operands under MOE_PREC_MIXED (moe_net_calibrate).
+#include "net.h"
+
+using namespace moe;
+
+// ---- calibration of one checkpoint (moe_net_calibrate) ---------------------------------------------------------------------------------
+// The per-architecture counts of split-operand ARSBs were chosen on the zoo's weights with ~2e-4 of the 1e-3 budget to spare on uint8 noise; a checkpoint
+// whose trunk swings wider spends more (profiles/r04/n_margin_sweep_and_fuzz_final_tree.txt: the trunk's weights x 1.15 -> 1.3e-3 / 1.8e-3 with the defaults).
+// The reference's contract is "load any state dict, get the fp32 answer" (python/imageProcess.py:319-334), so the count is a property of the CHECKPOINT and is
+// measured when it is loaded: uniform uint8-noise tiles (the input class that spends the most: SURVEY.md appendix) go through the exact mode (FP16X3: pinned to the
+// fp32 oracle at 2e-5 by the tests) and through MIXED with n = default .. 6 blocks; the smallest n whose PREDICTED worst tile of a full frame is within `target`
+// is kept, and when not even six blocks reach it the net runs in FP16X3.  ~0.2-0.5 s once per checkpoint and device.
+//
+// Round 6: the measurement is conservative by construction.  Rounds 4-5 measured two tiles of 3 x 192 x 192 from one seed and compared the value
+// itself with 7.5e-4; the worst tile of an all-tile sweep over full frames lay 1.05-1.29x above such a sample (a maximum over 5-20x more values, and tiles differ: a4 as
+// shipped 6.7e-4 there, 7.4e-4 over 48 plane-tiles; a perturbed checkpoint 6.5e-4 on nine planes, 8.3e-4 over 48 -- profiles/r05/margin_sweep.txt,
+// profiles/r06/calibration_vs_frames.txt).  Now: TWELVE seeds, tiles of 3 x 256 x 256 (the tile size that ships; 36 plane-tiles, run as four forwards of nine planes and
+// compared on the device), and the comparison is  measured x kCalibInflate <= target  for what is left between this sample and the 120 plane-tiles of a 1080p frame.
+// `err` reports the predicted (inflated) figure.  Hysteresis: the ARCHITECTURE'S DEFAULT count is kept while its prediction is within 5 % above the target -- a zoo key
+// that sits next to the target must not flip between n and n + 1 (and change its bits and speed) with the driver, the device or the launch geometry; every
+// larger count must be strictly within the target.
+namespace moe {
+
+constexpr double kCalibTarget = 8.5e-4;       // predicted worst tile of a full frame; 1.5e-4 of the 1e-3 contract stay in hand (the exact mode itself is pinned to the oracle at 2e-5,
+                                              // an fp16 result adds half an ulp of the value)
+constexpr double kCalibInflate = 1.10;        // full-frame worst tile / this sample's worst value
+constexpr double kCalibInflateDN = 1.30;      // ... NetDN: its all-tile sweeps lie 1.06-1.275x above the sample (dn_lite5 as shipped: 6.40e-4 on the sample, 8.16e-4 over 48 plane-tiles; profiles/r06/margin_sweep.txt)
+constexpr double kCalibHysteresis = 1.05;     // the default count only
+constexpr int kCalibTiles = 12;               // noise seeds = tiles of 3 planes, run in chunks of three tiles
+
+bool calibratable(const moe_net& n) { return n.arch == MOE_ARCH_NET2X || n.arch == MOE_ARCH_NET3X || n.arch == MOE_ARCH_NET4X || n.arch == MOE_ARCH_NETDN; }
+
+int calibrate_blocks(moe_net& n, double target, hipStream_t s)
+{
+    if (!(target > 0)) target = kCalibTarget;
+    const int B = 9, h = 256, w = 256, sc = n.scale;              // a chunk: three tiles of three planes (what one forward takes: the workspace stays that of a small launch set)
+    const int nchunks = kCalibTiles / 3;
+    const size_t nin = (size_t)B * h * w, nout = nin * sc * sc, per_seed = (size_t)3 * h * w;
+    std::vector<float> x(nin * nchunks);
+    for (int t = 0; t < kCalibTiles; ++t) {
+        unsigned long long st = 0x9E3779B97F4A7C15ull * (unsigned long long)(2 * t + 1);      // splitmix64 -> bytes -> / 255: the uint8 noise of SURVEY 8(d), one fixed seed per tile
+        for (size_t i = 0; i < per_seed; i += 8) {
+            unsigned long long z = (st += 0x9E3779B97F4A7C15ull);
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+            for (size_t k = 0; k < 8 && i + k < per_seed; ++k) x[t * per_seed + i + k] = (float)((z >> (8 * k)) & 255) / 255.f;
+        }
+    }
+    HIP_TRY(hipSetDevice(n.device));
+    // device scratch: the inputs, the exact mode's results of every chunk, one chunk of candidate results, the folded maximum -- nothing but 4 bytes per count comes back
+    struct Scratch { float *xd = nullptr, *ref = nullptr, *got = nullptr; unsigned* mx = nullptr; ~Scratch() { (void)hipFree(xd); (void)hipFree(ref); (void)hipFree(got); (void)hipFree(mx); } } sc_;
+    if (hipMalloc((void**)&sc_.xd, x.size() * 4) != hipSuccess || hipMalloc((void**)&sc_.ref, nout * nchunks * 4) != hipSuccess || hipMalloc((void**)&sc_.got, nout * 4) != hipSuccess ||
+        hipMalloc((void**)&sc_.mx, 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MOE_ENOMEM, "moe_net_calibrate: %zu bytes of scratch do not fit", (x.size() + nout * (nchunks + 1)) * 4);
+    }
+    HIP_TRY(hipMemcpyAsync(sc_.xd, x.data(), x.size() * 4, hipMemcpyHostToDevice, s));
+    const int prec0 = n.precision, blocks0 = n.exact_blocks;
+    const bool debug0 = n.debug;
+    n.debug = false;
+    auto run = [&](int c, float* out) -> int { return forward_dev(n, sc_.xd + (size_t)c * nin, MOE_F32, B, h, w, (long long)h * w, w, 1, nullptr, out, MOE_F32, nullptr, s); };
+    auto restore = [&](int rc) {
+        n.exact_blocks = blocks0; n.debug = debug0;
+        // the measurement's launch sets are larger than a per-tile caller's (nine planes): give the workspace back, the next forward sizes it for what the caller runs
+        (void)hipStreamSynchronize(s);
+        if (n.ws) { (void)hipFree(n.ws); n.ws = nullptr; n.ws_bytes = 0; }
+        return rc;
+    };
+    int rc = build_device_weights(n, MOE_PREC_FP16X3);
+    if (rc) return restore(rc);
+    n.precision = MOE_PREC_FP16X3;
+    for (int c = 0; c < nchunks && !rc; ++c) rc = run(c, sc_.ref + (size_t)c * nout);
+    if (rc) { n.precision = prec0; (void)build_device_weights(n, prec0); return restore(rc); }
+    if ((rc = build_device_weights(n, MOE_PREC_MIXED))) return restore(rc);
+    n.precision = MOE_PREC_MIXED;
+    n.calib_valid = false; n.calib_blocks = -1; n.calib_err = 0.0;
+    int best = -1;
+    double err = 0.0;
+    const int nb0 = default_exact_blocks(n.arch);
+    for (int nb = nb0; nb <= 6; ++nb) {
+        n.exact_blocks = nb;
+        HIP_TRY(hipMemsetAsync(sc_.mx, 0, 4, s));
+        for (int c = 0; c < nchunks && !rc; ++c) {
+            rc = run(c, sc_.got);
+            if (!rc) launch_maxabsdiff(sc_.got, sc_.ref + (size_t)c * nout, (long long)nout, sc_.mx, s);
+        }
+        if (rc) break;
+        unsigned bits = 0;
+        HIP_TRY(hipMemcpyAsync(&bits, sc_.mx, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float e;
+        memcpy(&e, &bits, 4);
+        err = (double)e * (n.arch == MOE_ARCH_NETDN ? kCalibInflateDN : kCalibInflate);                          // the predicted worst tile of a full frame (a NaN / Inf result: +inf, no count passes)
+        if (n.opt.calib_log) fprintf(stderr, "moe_net_calibrate: %d split blocks: measured %.3e on %d noise tiles of 3 x %d x %d, predicted %.3e (target %.3e)\n", nb, (double)e, kCalibTiles, h, w, err, target);
+        if (err <= (nb == nb0 ? target * kCalibHysteresis : target)) { best = nb; break; }
+    }
+    if (!rc) { n.calib_valid = true; n.calib_blocks = best; n.calib_err = err; }
+    if (prec0 != MOE_PREC_MIXED) { n.precision = prec0; const int rc2 = build_device_weights(n, prec0); if (!rc) rc = rc2; }
+    return restore(rc);
+}
+
+}  // namespace moe
+
+extern "C" {
+
+int moe_net_calibrate(moe_net* n, double target, int* blocks, double* err, void* stream)
+{
+    if (!n) return fail(MOE_EINVAL, "moe_net_calibrate: NULL net");
+    if (!n->finalized) return fail(MOE_ESTATE, "moe_net_calibrate: net is not finalized");
+    if (!calibratable(*n)) { if (blocks) *blocks = 0; if (err) *err = 0.0; return MOE_OK; }      // SEDN / lite: no such knob (their AUTO arithmetic has no split-block count)
+    if (n->precision != MOE_PREC_MIXED && n->precision != MOE_PREC_FP16X3) return fail(MOE_ESTATE, "moe_net_calibrate: finalize with MOE_PREC_AUTO or MOE_PREC_MIXED first");
+    const int rc = calibrate_blocks(*n, target, (hipStream_t)stream);
+    if (rc) { n->finalized = false; return rc; }      // (a failure half-way may have left the other arithmetic's weights on the device: finalize again)
+    if (blocks) *blocks = n->calib_blocks;
+    if (err) *err = n->calib_err;
+    return MOE_OK;
+}
+
+int moe_net_exact_blocks(const moe_net* n)
+{
+    if (!n) return fail(MOE_EINVAL, "moe_net_exact_blocks: NULL net");
+    return (n->precision == MOE_PREC_MIXED && calibratable(*n)) ? exact_blocks_of(*n) : 0;
+}
+
+int moe_net_set_exact_blocks(moe_net* n, int blocks)
+{
+    if (!n) return fail(MOE_EINVAL, "moe_net_set_exact_blocks: NULL net");
+    if (blocks < -1 || blocks > 6) return fail(MOE_EINVAL, "moe_net_set_exact_blocks: %d not in -1..6", blocks);
+    n->exact_blocks = blocks;
+    return MOE_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,87 @@
+// forward_sedn.cpp -- the forward of SEDN (models.py:190-223: sixteen _Conv_Blocks with their squeeze-excite gates).
+#include "net.h"
+
+using namespace moe;
+
+int moe::forward_sedn(moe_net& n, Fwd& f)
+{
+    const int B = f.B, h = f.h, w = f.w;
+    const long long P = (long long)B * h * w;
+    hipStream_t s = f.s;
+    Act A = f.act(P), Cc = f.act(P), Dd = f.act(P), T = f.act(P, 256);
+    const int nslab = (int)std::min<long long>(64, std::max<long long>(1, ((long long)h * w) / 256));
+    float* partial = (float*)f.ar.take((size_t)B * nslab * 256 * 4);
+    const ConvLayer& Lt = n.convs[n.conv_index.at("b0.trans")];
+    const size_t wel = (size_t)Lt.nchunks * Lt.nfrag() * 512;
+    half_t* wplane = (half_t*)f.ar.take(f.direct ? (size_t)B * 64 * 256 * 4 : (size_t)B * wel * 2);
+    half_t* wplane_lo = f.x3 ? (half_t*)f.ar.take((size_t)B * wel * 2) : nullptr;
+    f.stem(A);
+    f.tap("stem", A, h, w, 64, 64);
+    // fused block tail (see sedn_fuse in misc_kernels.hip): single-pass precision, fast kernel, planes fit the per-XCD split
+    const bool sfuse = n.opt.sedn_fuse && !f.x3 && !f.direct && !n.debug && n.opt.conv_impl == 2 && B <= n.max_groups &&
+                       2ll * B * h * w * 64 < (1ll << 32) - 8192;
+    float* xpart = (float*)f.ar.take((size_t)B * nslab * 5 * 64 * 4);
+    // the channel totals of rblock.2's output come out of that conv's epilogue (conv3x3_rw EPI 4), sedn_xsum then only visits the border
+    const int pslabs = 2 * n.max_groups;
+    float* xpool = (float*)f.ar.take((size_t)B * pslabs * 64 * 4);
+    const bool spool = n.opt.pool_fuse;
+    float* fgate = (float*)f.ar.take((size_t)B * 256 * 4);
+    half_t* weff = (half_t*)f.ar.take((size_t)B * 72 * 512 * 2);
+    for (int b = 0; b < 16; ++b) {
+        const std::string k = "b" + std::to_string(b);
+        f.conv(k + ".rb0", A, Cc, nullptr, h, w);
+        ConvExtra rb2;
+        if (sfuse && spool) { rb2.pool_out = xpool; rb2.pool_slabs = pslabs; }      // (the conv writes the first 2 min(G, py) slabs of every plane, all of them: no memset)
+        const bool pooled = f.conv(k + ".rb2", Cc, Dd, nullptr, h, w, rb2).pooled;
+        if (sfuse) {
+            if (!f.dry()) {
+                SednFuseArgs fa{};
+                fa.x = Dd.hi; fa.partial = xpart; fa.nslab = nslab; fa.B = B; fa.H = h; fa.W = w;
+                if (pooled) {
+                    const int py = (h + kTileH - 1) / kTileH;
+                    fa.pooled = xpool; fa.pooled_slabs = pslabs;
+                    fa.pooled_count = 2 * std::min(pooled_groups((long long)py, (long long)B * py, n.max_groups), py);      // conv3x3_rw EPI 4: slab 2 (g % py) + wave half
+                }
+                fa.w256t = f.small<float>(k + ".w256t"); fa.w256 = f.small<float>(k + ".w256"); fa.wt = f.small<float>(k + ".wt");
+                fa.w_down = f.small<float>(k + ".down"); fa.w_up = f.small<float>(k + ".up");
+                fa.gate = fgate; fa.weff = weff;
+                launch_sedn_fuse(fa, s);
+                ConvArgs a{};
+                a.in = Dd.hi; a.out = A.hi; a.res = A.hi; a.wpk = weff; a.plane_w = 1;
+                a.bias = f.small<float>("zero_bias"); a.bias_img = f.small<float>("zero_bias_img");
+                a.zero = f.small<half_t>("zero"); a.trash = f.small<half_t>("trash");
+                a.B = B; a.H = h; a.W = w; a.in_cs = 64; a.out_cs = 64; a.r = 1; a.nchunks = B;
+                a.px = (w + kTileW - 1) / kTileW; a.py = (h + kTileH - 1) / kTileH;
+                a.G = (int)std::max<long long>(B, std::min<long long>(n.max_groups, (long long)B * a.px * a.py));   // total workgroups (plane b gets every B-th)
+                a.slope = 0.2f; a.scale = 1.f;
+                if (!(n.opt.s64 && launch_conv64_s(a, n.max_groups, s)) && !launch_conv3x3_sp(a, s)) return fail(MOE_EINVAL, "SEDN fused block tail: kernel rejected the layer");
+            }
+            continue;
+        }
+        f.conv(k + ".rb4", Dd, T, nullptr, h, w);
+        if (!f.dry()) {
+            launch_pool_partial(T.hi, T.lo, partial, B, (long long)h * w, 256, nslab, s);
+            const ConvLayer& L = n.convs[n.conv_index.at(k + ".trans")];
+            SednSeArgs a{};
+            a.partial = partial; a.nslab = nslab; a.HW = (long long)h * w;
+            a.w_down = f.small<float>(k + ".down"); a.w_up = f.small<float>(k + ".up");
+            a.B = B;
+            if (f.direct) {
+                // plain fp32 OIHW weights [64][256]: element i -> cin = i % 256; reuse the SE kernel with a
+                // "fragment" view of 1 element per cin is not possible, so the debug path scales on the host-side layout:
+                a.trans_pk32 = f.blob<float>(L.w_plain); a.nfrag = -(64 * 256);   // negative: plain layout marker
+                a.trans_out = wplane;
+            } else {
+                a.trans_pk32 = f.blob<float>(L.w_pk32); a.nfrag = L.nfrag() * L.nchunks;
+                a.trans_out = wplane; a.trans_out_lo = wplane_lo;
+            }
+            launch_sedn_se(a, s);
+        }
+        ConvExtra trans;
+        trans.plane_w = wplane; trans.plane_w_lo = wplane_lo;
+        f.conv(k + ".trans", T, A, &A, h, w, trans);
+        f.tap("block" + std::to_string(b), A, h, w, 64, 64);
+    }
+    f.tail(&A, nullptr, h, w, true);
+    return MOE_OK;
+}

@@ -9,7 +9,7 @@ kernels do, so `F.conv2d` on rounded operands models them up to summation order.
   python tests/emu_precision.py budget         max-abs error of fp16 / mixed(n) on noise and natural tiles, all ARSB nets
   python tests/emu_precision.py wino a4        the upsampler convs as Winograd F(2x2, 3x3) with fp16 transformed operands, per branch (round 4 study)
 
-Used by tests/test_precision_budget.py (CPU suite) to pin the defaults of `exact_blocks_of` in engine.cpp.
+Used by tests/test_precision_budget.py (CPU suite) to pin the defaults of `exact_blocks_of` in forward.cpp.
 """
 import os
 import sys
@@ -265,7 +265,7 @@ def lite_budget(keys=('lite2', 'lite4', 'lite8')):
             print(line, flush=True)
 
 
-DEFAULT_EXACT = {'net2x': 4, 'net3x': 2, 'net4x': 1, 'netdn': 1}      # == exact_blocks_of() in engine.cpp
+DEFAULT_EXACT = {'net2x': 4, 'net3x': 2, 'net4x': 1, 'netdn': 1}      # == exact_blocks_of() in forward.cpp
 
 
 def _load(key):

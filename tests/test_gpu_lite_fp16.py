@@ -1,4 +1,4 @@
-"""lite's fp16 path against the oracle: the U branch as a table over the 65,536 fp16 bit patterns (option lite_lut; build_lite_lut, run_forward in engine.cpp;
+"""lite's fp16 path against the oracle: the U branch as a table over the 65,536 fp16 bit patterns (option lite_lut; build_lite_lut in forward.cpp, forward_lite.cpp;
 tail1sum_kernel / tail1sum_lut4_kernel in misc_kernels.hip).  Needs a HIP device: `pytest -m gpu`.
 
 The reference is oracle.nets.forward in fp32 on the fp16-rounded input.  Bounds are those of lite's default arithmetic (fp16x3, split operands everywhere):

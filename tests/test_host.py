@@ -410,3 +410,71 @@ def test_blend_tile_wrapper_refuses_tensors_of_another_rank():
                       (torch.zeros(2, 3, 16, 16), torch.zeros(3, 16, 16)), (torch.zeros(16, 16), torch.zeros(3, 16, 16))):
         with pytest.raises(ValueError, match='expected'):
             ip.blendTile(r, canvas, tile, 2, 4, ramp)
+
+
+# ---- the option parser (moephoto_amd/csrc/options.cpp: one table, walked by moe_net_set_option and by the MOE_* seeding at moe_net_create) ---------------------
+_FLAGS = ('up_fuse2', 'lo8', 'k48', 's64', 'auto_calibrate', 'overlap_calls', 'overlap_fork', 'calib_log', 'branch_streams', 'exact_fuse', 'conv1x1', 'x3_fuse', 'arsb_fuse',
+          'fuse_tail', 'sedn_fuse', 'pool_fuse', 'frm_pre', 'stem2', 'lite_lut')
+_ENUMS = {'conv_impl': ('sp', 'v1'), 'sp_impl': ('sp', 'auto', 'rw'), 'tail_split': ('0', 'r', 'ru'), 'tail_form': ('planes', 'sums'), 'up_impl': ('rw', 'ps4'),
+          'x3_impl': ('auto', 'x3', 'q8'), 'q8_impl': ('s', 'p')}
+_COUNTS = ('overlap_groups', 'branch_groups', 'tiles_per_batch', 'max_groups')
+OPTION_CASES = (
+    [(k, v, True) for k in _FLAGS for v in ('0', '1', 'on', 'off')] + [(k, v, False) for k in _FLAGS for v in ('yes', '-1', '', '2', 'ON')] +
+    [(k, v, True) for k, vs in _ENUMS.items() for v in vs] + [(k, v, False) for k in _ENUMS for v in ('nonsense', '-1', '', '1', 'off')] +
+    # the counts go through atoi: a negative number is refused (and, since the table, leaves the option as it was -- branch_groups, tiles_per_batch and max_groups used to
+    # store it first); a word or the empty string reads as 0, the option's "default" value, and is accepted
+    [(k, v, True) for k in _COUNTS for v in ('0', '64', '', 'nonsense')] + [(k, v, False) for k in _COUNTS for v in ('-1', '-64')] +
+    [('dbg', v, True) for v in ('0', '64', '-1', '', 'x')] +                   # timing-ablation bits: whatever atoi makes of it
+    [('trace_key', v, True) for v in ('convt_R1.up1', 'c2_3', '')] +
+    [('repeat', v, True) for v in ('arsb3:20', '0', '', 'a:b:2')] + [('repeat', v, False) for v in ('arsb3:0', 'k:-3', 'nonsense', ':4', '1')] +
+    [(k, '1', False) for k in ('arsb_impl', '', 'CONV_IMPL', 'exact_blocks', 'arsb_trace', 'repeat_key', 'MOE_K48', 'k48 ')])
+
+
+def test_option_parser_accepts_and_refuses_what_it_always_did():
+    """Every key of the option table with each of its values and with values it refuses, and keys it does not have.  The expectations were recorded against the parser as it
+    was before the table (the hand-written chain of comparisons); the one intended difference is not visible in a return code: a refused count used to be stored first."""
+    L = _lib.lib()
+    h = ctypes.c_void_p()
+    _lib.check(L.moe_net_create(_lib.ARCH_NET4X, 4, ctypes.byref(h)))
+    try:
+        wrong = [(k, v, ok) for k, v, ok in OPTION_CASES if L.moe_net_set_option(h, k.encode(), v.encode()) != (0 if ok else _lib.EINVAL)]
+        assert not wrong, wrong
+        assert L.moe_net_set_option(h, b'k48', None) == _lib.EINVAL and L.moe_net_set_option(h, None, b'1') == _lib.EINVAL
+        assert L.moe_net_set_option(h, b'up_impl', b'nonsense') == _lib.EINVAL and b'"up_impl" = "nonsense"' in L.moe_last_error()
+    finally:
+        L.moe_net_destroy(h)
+    assert {k for k, _, ok in OPTION_CASES if ok} == set(_option_table_keys())      # (no key of the table goes untested)
+
+
+def test_environment_seeds_the_options_at_create_and_reports_typos():
+    """The MOE_* variables are read once, when a net is created: a valid value is silent, a value the option does not have is reported on stderr and ignored."""
+    code = ('import ctypes; from moephoto_amd import _lib; L = _lib.lib(); h = ctypes.c_void_p(); '
+            'rc = L.moe_net_create(_lib.ARCH_NET2X, 2, ctypes.byref(h)); print("rc", rc); L.moe_net_destroy(h)')
+    for value, complains in (('rw', False), ('nonsense', True)):
+        env = dict(os.environ, MOE_UP_IMPL=value)
+        out = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and 'rc 0' in out.stdout, out.stderr[-2000:]
+        line = 'MOE_UP_IMPL="{}" is not a value of option up_impl'.format(value)
+        assert ('is not a value of option' in out.stderr) == complains and (line in out.stderr) == complains, out.stderr[-2000:]
+
+
+def _option_table_keys():
+    src = open(os.path.join(ROOT, 'moephoto_amd', 'csrc', 'options.cpp')).read()
+    body = src[src.index('kOptionTable[]'):]
+    body = body[:body.index('\n};')]
+    return re.findall(r'^\s*\{"([a-z0-9_]+)",\s*(?:"MOE_[A-Z0-9_]+"|nullptr),', body, re.M)
+
+
+def test_option_documentation_follows_the_table():
+    """Every key of the table is named in the header's comment of moe_net_set_option and in README's option paragraph (the header listed fewer than half)."""
+    keys = _option_table_keys()
+    assert len(keys) >= 33 and len(set(keys)) == len(keys)
+    hdr = open(os.path.join(ROOT, 'include', 'moephoto_amd.h')).read()
+    end = hdr.index('int moe_net_set_option(')
+    comment = hdr[hdr.rindex('/*', 0, end):end]
+    readme = open(os.path.join(ROOT, 'README.md')).read()
+    start = readme.index('Per-net options (`moe_net_set_option`')
+    para = readme[start:readme.index('Tooling:', start)]
+    for k in keys:
+        assert re.search(r'(?<![A-Za-z0-9_]){}(?![A-Za-z0-9_])'.format(re.escape(k)), comment), 'include/moephoto_amd.h does not document option ' + k
+        assert re.search(r'(?<![A-Za-z0-9_]){}(?![A-Za-z0-9_])'.format(re.escape(k)), para), 'README.md does not name option ' + k

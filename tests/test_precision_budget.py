@@ -1,5 +1,5 @@
 """The error budget behind MOE_PREC_MIXED, on the CPU (tests/emu_precision.py emulates the engine's roundings on top of an
-fp32 forward).  Pins the defaults of exact_blocks_of() in moephoto_amd/csrc/engine.cpp: with them every ARSB net stays
+fp32 forward).  Pins the defaults of exact_blocks_of() in moephoto_amd/csrc/forward.cpp: with them every ARSB net stays
 within 1e-3 of the fp32 forward on white noise (the adversarial input), and plain fp16 operands do not."""
 import re
 import os
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_defaults_match_engine_source():
-    src = open(os.path.join(ROOT, 'moephoto_amd', 'csrc', 'engine.cpp')).read()
+    src = open(os.path.join(ROOT, 'moephoto_amd', 'csrc', 'forward.cpp')).read()
     body = src[src.index('int exact_blocks_of('):]
     got = {a.lower(): int(v) for a, v in re.findall(r'case MOE_ARCH_(NET2X|NET3X|NET4X|NETDN): return (\d+);', body)}
     assert got == emu.DEFAULT_EXACT
@@ -75,7 +75,7 @@ def test_fp8_corrections_and_fp8_low_part_budget(key):
 
 
 def test_e4m3_rounding_of_the_emulation():
-    """emu.q8 = OCP e4m3 with round-to-nearest-even and saturation at 448 (what to_e4m3 in engine.cpp and v_cvt_scalef32_pk_fp8_f16 under MODE.FP16_OVFL do)."""
+    """emu.q8 = OCP e4m3 with round-to-nearest-even and saturation at 448 (what to_e4m3 in weights.cpp and v_cvt_scalef32_pk_fp8_f16 under MODE.FP16_OVFL do)."""
     v = torch.tensor([0.0, 1.0, 1.0625, 1.1875, 17.0, 18.0, 19.0, 447.0, 448.0, 464.0, 1000.0, 2.0 ** -9, 2.0 ** -10, 3.0 * 2.0 ** -11, -0.3])
     got = emu.q8(v, 0)
     want = torch.tensor([0.0, 1.0, 1.0, 1.25, 16.0, 18.0, 20.0, 448.0, 448.0, 448.0, 448.0, 2.0 ** -9, 0.0, 2.0 ** -9, -0.3125])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """GPU exploration: worst tile error (default arithmetic vs the engine's own exact mode 'fp16x3') and frame time of Net2x / Net4x / NetDN
-for every setting of `exact_blocks` (leading ARSBs with split operands) -- the data behind exact_blocks_of() in engine.cpp."""
+for every setting of `exact_blocks` (leading ARSBs with split operands) -- the data behind exact_blocks_of() in forward.cpp."""
 import os
 import sys
 import time
