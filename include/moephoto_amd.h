@@ -99,7 +99,9 @@ int moe_net_param_info(const moe_net* net, int index, const char** name, int64_t
 int moe_net_set_param(moe_net* net, const char* name, const float* data, const int64_t* shape, int ndim);
 /* pack + upload weights to HIP device `device`; strict like load_state_dict (every parameter set).
  * May be called again to move / change precision.  precision: MOE_PREC_AUTO for the family's default (what a drop-in caller
- * passes), or a specific arithmetic (MIXED is refused for SEDN / lite, which have no such recipe). */
+ * passes), or a specific arithmetic (MIXED is refused for SEDN / lite, which have no such recipe).  MOE_PREC_AUTO also measures the
+ * loaded checkpoint once (moe_net_calibrate below): Net2x/3x/4x and NetDN get their count of split-operand blocks or FP16X3, SEDN
+ * keeps FP16 when that holds the contract on these weights and runs in FP16X3 when it does not; lite always runs in FP16X3. */
 int moe_net_finalize(moe_net* net, int device, int precision);
 /* what `precision` resolves to for this net's family (MOE_PREC_AUTO -> FP16 / FP16X3 / MIXED; anything else -> itself).  After a finalize with MOE_PREC_AUTO:
  * what that finalize settled on for the loaded weights (see moe_net_calibrate). */
@@ -112,8 +114,13 @@ int moe_net_resolved_precision(const moe_net* net, int precision);
  * full frame; *blocks = the smallest count whose prediction is <= target (target <= 0: 8.5e-4; the architecture's default count is kept up to 5 % above it, so that a
  * zoo key next to the target does not flip with the device or driver), *err = that prediction; *blocks = -1 when six blocks do not reach it (*err = what they reach).
  * The count is kept (moe_net_exact_blocks) until a parameter changes or moe_net_set_exact_blocks overrides it.  moe_net_finalize(MOE_PREC_AUTO) runs this by itself,
- * once per checkpoint, and finalizes in MOE_PREC_FP16X3 when no count reaches the target: a drop-in caller needs no extra line.  SEDN / lite: *blocks = 0, nothing
- * is measured (their AUTO arithmetic has no such knob).  Synchronises `stream`; ~0.2-0.4 s.  (moe_net_finalize runs its measurement on a private non-blocking stream.) */
+ * once per checkpoint, and finalizes in MOE_PREC_FP16X3 when no count reaches the target: a drop-in caller needs no extra line.
+ * SEDN (finalized in FP16 or FP16X3) has no count, and a two-way answer: the same sample runs in FP16 -- with the net's current options, as it ships -- and in FP16X3;
+ * *err = the worst difference times SEDN's inflation factor (the predicted worst tile of a full frame in FP16), *blocks = 0.  The net keeps the arithmetic it was
+ * finalized with; moe_net_finalize(MOE_PREC_AUTO) keeps FP16 while *err <= target x 1.05 (FP16 is the family's default: the same 5 %) and runs the checkpoint in FP16X3
+ * otherwise (moe_net_resolved_precision(net, MOE_PREC_AUTO) then says so); option auto_calibrate = 0 keeps FP16 unmeasured.
+ * lite: *blocks = 0, *err = 0, nothing is measured (its AUTO arithmetic is the exact mode).
+ * Synchronises `stream`; ~0.2-0.4 s.  (moe_net_finalize runs its measurement on a private non-blocking stream.) */
 int moe_net_calibrate(moe_net* net, double target, int* blocks, double* err, void* stream);
 /* the count of split-operand ARSBs the next forward runs with (0 when the net is not in MOE_PREC_MIXED) */
 int moe_net_exact_blocks(const moe_net* net);

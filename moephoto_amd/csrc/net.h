@@ -116,8 +116,8 @@ struct NetOptions {
                               //             fork 1 / 128 groups 35.8; GPU_MAX_HW_QUEUES = 8 or 16 instead of HIP's 4: 36-39 ms.  The chip is saturated either way: what separates the
                               //             loop from the device-resident path is the fixed cost of forty 3-plane launch sets (weight preloads, ramp-up and tail of every kernel), which
                               //             two forwards in flight hide only in part
-    int calib_log = 0;        // calib_log   1: moe_net_calibrate prints every count's measured and predicted error to stderr (tools/calib_report.py)
-    int auto_calibrate = 1;   // auto_calibrate  1 (default): moe_net_finalize(MOE_PREC_AUTO) measures the count of split-operand ARSBs on the loaded weights | 0: per-architecture defaults
+    int calib_log = 0;        // calib_log   1: moe_net_calibrate prints every count's (SEDN: fp16's) measured and predicted error to stderr (tools/calib_report.py)
+    int auto_calibrate = 1;   // auto_calibrate  1 (default): moe_net_finalize(MOE_PREC_AUTO) measures the count of split-operand ARSBs (SEDN: whether fp16 holds) on the loaded weights | 0: per-architecture defaults
     int exact_blocks_env = -1;   // MOE_EXACT_BLOCKS (moe_net_set_exact_blocks overrides)
     int tiles_per_batch = 0;  // tiles_per_batch   tiles of 256^2 pixels per launch set when the caller passes 0 (0: 32)
     int max_groups = 0;       // max_groups  persistent workgroups per launch (0: one per CU), applied at finalize
@@ -145,14 +145,15 @@ struct moe_net {
     bool finalized = false;
     int device = -1, precision = MOE_PREC_FP16;
     int exact_blocks = -1;       // MOE_PREC_MIXED: leading ARSBs computed with split operands (-1: the calibrated count if there is one, else the per-architecture default)
-    // calibration of THESE weights (moe_net_calibrate; run by moe_net_finalize(MOE_PREC_AUTO) on the ARSB nets): valid until a parameter changes
+    // calibration of THESE weights (moe_net_calibrate; run by moe_net_finalize(MOE_PREC_AUTO) on the ARSB nets and on SEDN): valid until a parameter changes
     bool calib_valid = false;
     // lite, fp16 inputs (round 6): the U branch (MoeNet_lite2.py:47,50: conv_input, uim, convt_I1) is POINTWISE -- 1x1 convs, pixel shuffles, PReLUs on a one-channel input -- so its
     // output at an HR pixel is a function of ONE input value and the pixel's phase: a table over the 65,536 fp16 bit patterns, filled once per checkpoint by the U branch's own
     // kernels run on an image of all patterns (bit-identical to computing it), [256 r][256 r] fp32.  lut_state: 0 not tried, 1 ready, -1 not available, 2 being built
     float* lut = nullptr; half_t* lut_in = nullptr; int lut_state = 0;
-    int calib_blocks = -1;       // smallest count of split-operand ARSBs whose worst noise-tile error against the exact mode is within the target (-1: none is -> FP16X3)
-    double calib_err = 0.0;      // that error
+    int calib_blocks = -1;       // smallest count of split-operand ARSBs whose worst noise-tile error against the exact mode is within the target (-1: none is -> FP16X3);
+                                 // SEDN: 0 = plain fp16 is within it, -1 = it is not -> FP16X3
+    double calib_err = 0.0;      // that error, as predicted for the worst tile of a full frame (measured x the family's inflation factor)
     int auto_resolved = -1;      // what MOE_PREC_AUTO resolved to at the last finalize with it (-1: not finalized that way since the parameters changed)
     // device weights
     char* blob = nullptr;
@@ -343,5 +344,6 @@ void drop_lut(moe_net& n);
 // calibrate.cpp
 bool calibratable(const moe_net& n);
 int calibrate_blocks(moe_net& n, double target, hipStream_t s);
+int calibrate_sedn(moe_net& n, double target, hipStream_t s, bool adopt);
 
 }  // namespace moe

@@ -570,7 +570,7 @@ static int resolve_precision(int arch, int precision)
 {
     if (precision != MOE_PREC_AUTO) return precision;
     switch (arch) {
-        case MOE_ARCH_SEDN: return MOE_PREC_FP16;       // l15 / l25 / l50: 4-6e-4 in plain fp16
+        case MOE_ARCH_SEDN: return MOE_PREC_FP16;       // l15 / l25 / l50: 4-6e-4 in plain fp16 on the synthetic l25; moe_net_finalize measures the checkpoint
         case MOE_ARCH_LITE: return MOE_PREC_FP16X3;     // lite2 / 4 / 8: every conv but one would have to be split anyway
         default: return MOE_PREC_MIXED;                 // Net2x / 3x / 4x, NetDN
     }
@@ -646,6 +646,23 @@ int moe_net_finalize(moe_net* n, int device, int precision)
                 if (rc) { n->finalized = false; return rc; }
             }
             if (n->calib_blocks < 0) {
+                rc = build_device_weights(*n, MOE_PREC_FP16X3);
+                if (rc) { n->finalized = false; return rc; }
+                n->precision = precision = MOE_PREC_FP16X3;
+            }
+        }
+        // SEDN: the family's default is plain fp16; whether THIS checkpoint holds the contract in it is measured the same way (calibrate_sedn: fp16 as it ships against
+        // the exact mode), and a checkpoint that does not runs in FP16X3 -- whose weights the measurement then leaves on the device.  auto_calibrate = 0: fp16, unmeasured.
+        if (n->arch == MOE_ARCH_SEDN && precision == MOE_PREC_FP16 && n->opt.auto_calibrate) {
+            if (!n->calib_valid) {
+                hipStream_t cs = nullptr;
+                HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+                rc = calibrate_sedn(*n, 0.0, cs, true);
+                (void)hipStreamSynchronize(cs);
+                (void)hipStreamDestroy(cs);
+                if (rc) { n->finalized = false; return rc; }
+                precision = n->precision;
+            } else if (n->calib_blocks < 0) {
                 rc = build_device_weights(*n, MOE_PREC_FP16X3);
                 if (rc) { n->finalized = false; return rc; }
                 n->precision = precision = MOE_PREC_FP16X3;

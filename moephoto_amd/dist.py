@@ -421,9 +421,10 @@ def broadcast_state_dict(sd, src=0, device=None, group=None):
 
 def agree_arithmetic(model, group=None):
     """Every rank runs the arithmetic rank 0 settled on.  moe_net_finalize(MOE_PREC_AUTO) calibrates per process (moe_net_calibrate: the count of split-operand ARSBs, or the
-    exact mode); the measurement is deterministic for equal weights and kernels, but ranks that disagreed -- another driver, another device generation in one job -- would
+    exact mode; SEDN: 'fp16' or, for a checkpoint that misses the target in it, 'fp16x3'); the measurement is deterministic for equal weights and kernels, but ranks that disagreed -- another driver, another device generation in one job -- would
     compute the tiles of ONE frame with different bits (ADVICE r05).  Rank 0's resolved precision and block count are broadcast and imposed (set_precision / set_exact_blocks);
-    returns (precision, blocks).  Called once per finalized model by run_frames / run_frames_overlapped (a collective: every rank calls it at the same place)."""
+    returns (precision, blocks).  A SEDN net that fell back on rank 0 alone is finalized with the explicit 'fp16x3' on the others (and one that fell back on another
+    rank alone with the explicit 'fp16'): a band or frame split never mixes arithmetics inside one image.  Called once per finalized model by run_frames / run_frames_overlapped (a collective: every rank calls it at the same place)."""
     key = (id(group), getattr(model, '_finalized_key', None))
     if getattr(model, '_dist_agreed', None) == key:
         return model._dist_agreed_value

@@ -52,7 +52,7 @@ class EngineModule(object):
         self.training = False
         # 'auto' = the cheapest arithmetic that stays within 1e-3 of the fp32 reference on every input class:
         #   'mixed'  Net2x/3x/4x, NetDN: fp16 MFMA operands, hi+lo trunk stream, split operands on the few layers that set the error
-        #   'fp16'   SEDN (4-6e-4 as it is)
+        #   'fp16'   SEDN (4-6e-4 as it is on the synthetic l25; a checkpoint that misses the target in it, measured when it is loaded, runs in 'fp16x3')
         #   'fp16x3' lite* (every layer of these shallow 48-channel nets is error-critical)
         # MOE_PRECISION=fp16 forces the single-pass mode everywhere (the arithmetic of the reference's own GPU fp16 mode).
         self.precision = os.environ.get('MOE_PRECISION', 'auto')
@@ -183,10 +183,16 @@ class EngineModule(object):
         n = default .. 6 blocks, on the device) and keep it.  Returns (n, predicted worst-tile error of a full frame at n); n = -1 when six blocks do not reach `target`
         (<= 0: the library's default).  With precision 'auto' the module is finalized again on the result (n blocks, or 'fp16x3' when n = -1); with an explicit 'mixed' the
         count applies (exact_blocks()) and n = -1 leaves the architecture's count in force.  `.to(device)` with precision 'auto' already does this once per checkpoint (moe_net_finalize(MOE_PREC_AUTO)); this is the explicit call, e.g. with
-        another target.  None for families without the knob (SEDN, lite) or when the module runs in another arithmetic."""
+        another target.  SEDN has no count but the same question -- does its default, plain fp16, hold on THESE weights? -- and returns (0, predicted worst-tile
+        error of a full frame in fp16): with precision 'auto' the module then runs in 'fp16' while that is within the target and in 'fp16x3' when it is not
+        (resolved_precision()); with an explicit 'fp16' / 'fp16x3' the figure is reported and nothing changes.  None for lite (no knob: always 'fp16x3') or when the
+        module runs in another arithmetic."""
         if self._device is None:
             raise _lib.EngineError('calibrate: move the module to its device first')
-        if self.ARCH in (_lib.ARCH_LITE, _lib.ARCH_SEDN) or self.resolved_precision() not in ('mixed', 'fp16x3') or self.precision not in ('auto', 'mixed'):
+        if self.ARCH == _lib.ARCH_SEDN:
+            if self.resolved_precision() not in ('fp16', 'fp16x3'):
+                return None
+        elif self.ARCH == _lib.ARCH_LITE or self.resolved_precision() not in ('mixed', 'fp16x3') or self.precision not in ('auto', 'mixed'):
             return None
         n, err = ctypes.c_int(), ctypes.c_double()
         stream = torch.cuda.current_stream(self._device).cuda_stream
