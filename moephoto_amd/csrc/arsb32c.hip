@@ -664,17 +664,22 @@ hipError_t arsb32c_init()
 }
 
 // w1 / w2: packed A fragments in the conv3x3_sp / pack_conv order (ConvLayer::w_hi).  false: the layer does not fit this kernel
+bool arsb32c_applicable(int B, int H, int W, float slope, bool x_lo, bool y_lo, int cin)
+{
+    if (!(slope <= 1.f)) return false;                                  // PReLU as max(x, slope * x)
+    if ((long long)B * H * W * 128 + (2ll * W + 2) * 128 >= (1ll << 32) - 65536) return false;   // 32-bit byte offsets
+    if (x_lo != y_lo) return false;
+    if ((long long)B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH) >= (1ll << 31) / 256) return false;
+    return cin == 0 || cin == 48 || cin == 64;
+}
+
 bool launch_arsb32c(ArsbArgs a, int max_groups, hipStream_t s)
 {
-    if (!(a.slope <= 1.f)) return false;                                  // PReLU as max(x, slope * x)
-    if ((long long)a.B * a.H * a.W * 128 + (2ll * a.W + 2) * 128 >= (1ll << 32) - 65536) return false;   // 32-bit byte offsets
-    if ((a.x_lo == nullptr) != (a.y_lo == nullptr)) return false;
+    if (!arsb32c_applicable(a.B, a.H, a.W, a.slope, a.x_lo != nullptr, a.y_lo != nullptr, a.cin)) return false;
     a.px = (a.W + TW - 1) / TW;
     a.py = (a.H + TH - 1) / TH;
     const long long items = (long long)a.B * a.px * a.py;
-    if (items >= (1ll << 31) / 256) return false;
     const int G = (int)std::min<long long>(items, max_groups);
-    if (a.cin != 0 && a.cin != 48 && a.cin != 64) return false;
     const bool k3 = a.cin == 48;               // the fourth 16-channel k-slice carries zeros only
     if (a.x_lo) { if (k3) arsb32c_kernel<true, 3><<<dim3(G), dim3(256), LDS_BYTES + TRACE_LDS, s>>>(a); else arsb32c_kernel<true, 4><<<dim3(G), dim3(256), LDS_BYTES + TRACE_LDS, s>>>(a); }
     else { if (k3) arsb32c_kernel<false, 3><<<dim3(G), dim3(256), LDS_BYTES + TRACE_LDS, s>>>(a); else arsb32c_kernel<false, 4><<<dim3(G), dim3(256), LDS_BYTES + TRACE_LDS, s>>>(a); }

@@ -548,15 +548,19 @@ hipError_t arsb_sq_init()
 
 // One exact ARSB of a conv64_q8 / conv64_sq chain (fp8 low words in; out: fp8, or fp16 behind the last exact block); y must not alias x.
 // false: not this kernel's (the caller runs the two convs)
+bool arsb_sq_applicable(int B, int H, int W, float slope)
+{
+    if (!(slope <= 1.f) || H % RB != 0 || H < RB) return false;
+    if ((long long)B * H * W * 128 + (long long)(RB * W + 2) * 128 >= (1ll << 32) - 65536) return false;
+    return (long long)B * ((W + TW - 1) / TW) * (H / RB) < (1ll << 31) / 4;
+}
+
 bool launch_arsb_sq(const ArsbSqArgs& q, int max_groups, hipStream_t s)
 {
-    if (!(q.slope <= 1.f) || q.H % RB != 0 || q.H < RB) return false;
-    if ((long long)q.B * q.H * q.W * 128 + (long long)(RB * q.W + 2) * 128 >= (1ll << 32) - 65536) return false;
+    if (!arsb_sq_applicable(q.B, q.H, q.W, q.slope)) return false;
     if (!q.x_hi || !q.x_lo8 || !q.y_hi || !q.y_lo || q.y_hi == q.x_hi) return false;
     for (int i = 0; i < 2; ++i) if (!q.w16[i] || !q.wh8[i] || !q.wl8[i]) return false;
-    const int px = (q.W + TW - 1) / TW;
-    const long long items = (long long)q.B * px * (q.H / RB);
-    if (items >= (1ll << 31) / 4) return false;
+    const long long items = (long long)q.B * ((q.W + TW - 1) / TW) * (q.H / RB);
     ArsbSqArgsK a{};
     a.x_hi = q.x_hi; a.x_lo8 = q.x_lo8; a.y_hi = q.y_hi; a.y_lo = q.y_lo;
     for (int i = 0; i < 2; ++i) { a.w16[i] = q.w16[i]; a.wh8[i] = q.wh8[i]; a.wl8[i] = q.wl8[i]; }

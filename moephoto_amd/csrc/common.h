@@ -64,6 +64,25 @@ struct ConvArgs {
     float* pool; int pool_slabs;
 };
 
+// What a launcher of a ConvArgs kernel decides on: the shape and WHICH optional operands are present -- flags, never the pointers themselves (the planning pass of a
+// forward has none).  Every launcher that can refuse a layer refuses by its *_applicable predicate below, and the planners (Fwd::route, the families' sequences)
+// ask the same predicate: a condition written on one side only would turn a performance choice into a failed forward.
+struct ConvForm {
+    int B = 0, H = 0, W = 0, in_cs = 64, out_cs = 64, r = 1, nchunks = 1, G = 1, py = 1;
+    float slope = 1.f, scale = 1.f;
+    int acc_mode = 0, dbg = 0, tail_form = 0, tail_split = 0, pool_slabs = 0;
+    bool res = false, res_lo = false, in_lo = false, out_lo = false, side16 = false, tail = false, tail1 = false, pool = false, plane_w = false;
+};
+inline ConvForm conv_form(const ConvArgs& a)
+{
+    ConvForm c;
+    c.B = a.B; c.H = a.H; c.W = a.W; c.in_cs = a.in_cs; c.out_cs = a.out_cs; c.r = a.r; c.nchunks = a.nchunks; c.G = a.G; c.py = a.py;
+    c.slope = a.slope; c.scale = a.scale; c.acc_mode = a.acc_mode; c.dbg = a.dbg; c.tail_form = a.tail_form; c.tail_split = a.tail_split; c.pool_slabs = a.pool_slabs;
+    c.res = a.res != nullptr; c.res_lo = a.res_lo != nullptr; c.in_lo = a.in_lo != nullptr; c.out_lo = a.out_lo != nullptr; c.side16 = a.side16 != nullptr;
+    c.tail = a.tplanes != nullptr; c.tail1 = a.tail1_w != nullptr; c.pool = a.pool != nullptr; c.plane_w = a.plane_w != 0;
+    return c;
+}
+
 // Fused tail, "phase-class sums" form (tests/tailsum_model.py states the arithmetic).  One branch's buffer, fp32 ELEMENT offsets:
 //   S  [4 phases][4 classes][B][H][W]      sums of the per-tap products that land on output pixels of one parity class, formed inside a patch
 //   RA [4][2][B][py][W]                    row aprons: what patch row pyi exports to the vertically adjacent patch's edge row (classes (1, cj))
@@ -100,7 +119,9 @@ struct Conv1x1Args {
     int B, H, W, r, nchunks, out_cs;
     int nks;                                      // k-slices of 16 input channels that are not all zeros: 3 for the 48-channel nets (option k48), else 4
 };
-bool launch_conv1x1(const Conv1x1Args& a, int max_groups, hipStream_t s);   // false: shape not compiled (caller uses conv_mfma_kernel)
+struct Conv1x1Form { int B, H, W, r, nchunks, out_cs; float slope; bool x3, tail, out_lo; };      // (x3: split operands; tail: the folded 48->1 conv; out_lo: the output has a low part)
+bool conv1x1_applicable(const Conv1x1Form& a, int max_groups);
+bool launch_conv1x1(const Conv1x1Args& a, int max_groups, hipStream_t s);   // false: !conv1x1_applicable (shape not compiled: conv_mfma_kernel takes the layer)
 hipError_t conv1x1_init();
 
 // Two upsampler stages of MoeNet_lite2 (1x1 48 -> 192, PixelShuffle(2), PReLU, twice) + the folded 48 -> 1 tail in one launch, split operands (conv1x1_f2.hip):
@@ -114,17 +135,20 @@ struct Conv1x1F2Args {
     float slope_a, slope_b;                       // PReLU slopes (<= 1)
     int B, H, W;
 };
-bool launch_conv1x1_f2(const Conv1x1F2Args& a, int max_groups, hipStream_t s);   // false: not applicable
+bool conv1x1_f2_applicable(int B, int H, int W, float slope_a, float slope_b, int max_groups);
+bool launch_conv1x1_f2(const Conv1x1F2Args& a, int max_groups, hipStream_t s);   // false: !conv1x1_f2_applicable (the stages run one by one on conv1x1.hip)
 hipError_t conv1x1_f2_init();
 
 void launch_conv_mfma(const ConvArgs& a, int taps, int nseg, hipStream_t s);
 int conv_mfma_max_groups();  // persistent workgroups the device holds (1 per CU)
 hipError_t conv_mfma_init(); // raise dynamic-LDS limits once per process
 // 3x3 / 64-channel specialisation: one wave per SIMD with the epilogue software-pipelined into the MFMA stream (conv3x3_sp.hip)
-bool launch_conv3x3_sp(const ConvArgs& a, hipStream_t s);   // false: epilogue variant not compiled, use another kernel
+bool conv3x3_sp_applicable(const ConvForm& c);
+bool launch_conv3x3_sp(const ConvArgs& a, hipStream_t s);   // false: !conv3x3_sp_applicable (epilogue variant not compiled, range: another kernel takes the layer)
 hipError_t conv3x3_sp_init();
 // the upsampler convs with register-resident weights (conv3x3_rw.hip): PReLU (+ fused tail) epilogues only
-bool launch_conv3x3_rw(const ConvArgs& a, hipStream_t s);   // false: not applicable, use conv3x3_sp
+bool conv3x3_rw_applicable(const ConvForm& c);
+bool launch_conv3x3_rw(const ConvArgs& a, hipStream_t s);   // false: !conv3x3_rw_applicable (conv3x3_sp takes the layer)
 hipError_t conv3x3_rw_init();
 
 // The last upsampler stage (3x3, 64 -> 256, + bias, PixelShuffle(2), PReLU) with the 64 -> 1 tail conv, all four phases in one workgroup (conv3x3_ps4.hip)
@@ -132,7 +156,7 @@ struct Ps4Args {
     const half_t* in;        // [B][H][W][64]
     const half_t* wpk;       // pack_conv fragments [phase 4][72][lane 64][8]
     const float* bias;       // [256] fp32 in packed output-channel order (ConvLayer::bias)
-    const half_t* tail_w;    // eight A fragments of the tail conv (engine.cpp tail(): "<key>.frag")
+    const half_t* tail_w;    // eight A fragments of the tail conv (weights.cpp tail(): "<key>.frag")
     half_t* out;             // store form (not the last stage): [B][2H][2W][64] fp16, PReLU'd and pixel-shuffled; plane / apron / tail_w unused
     float* plane;            // out: [B][2H][2W] fp32, this branch's tail-conv sums without the terms that cross a 32-pixel column
     float* apron;            // out: [side 2][B][px][2H] fp32, those terms (side 0: for the column to the right, 1: to the left)
@@ -145,6 +169,7 @@ bool ps4_applicable(int B, int H, int W);                                    // 
 // the ONE predicate of the fused-tail form: the engine plans its buffers with it and launch_conv3x3_ps4 refuses with it -- a condition added to one side only would
 // turn a performance choice into a failed forward
 inline bool ps4_tail_applicable(int B, int H, int W, float slope) { return slope < 1.f && ps4_applicable(B, H, W); }
+bool ps4_store_applicable(int B, int H, int W, float slope);                 // ... and of the store form (Ps4Args::out): the HR tensor within 32-bit byte offsets as well
 size_t ps4_plane_bytes(int B, int H, int W);
 size_t ps4_apron_bytes(int B, int H, int W);
 hipError_t conv3x3_ps4_init();
@@ -164,7 +189,7 @@ struct Ps9Args {
     const half_t* in;        // [B][H][W][64]
     const half_t* wpk;       // pack_conv fragments [phase 9][72][lane 64][8]
     const float* bias;       // [576] fp32 in packed output-channel order (ConvLayer::bias)
-    const half_t* tail_w;    // eight A fragments of the tail conv (engine.cpp tail(): "<key>.frag")
+    const half_t* tail_w;    // eight A fragments of the tail conv (weights.cpp tail(): "<key>.frag")
     float* plane;            // out: [dy 3][B][3H][3W] fp32, S[dy][HR row][HR column] = the tail conv's sums over dx for tap row dy, terms crossing a 32-pixel column left out
     float* apron;            // out: [side 2][dy 3][B][px][3H] fp32, those terms (side 0: for the column to the right, 1: to the left)
     float slope;             // PReLU slope (< 1)
@@ -203,6 +228,7 @@ struct ArsbArgs {
 };
 // arsb32c.hip: v_mfma_f32_32x32x16_f16, four waves in lock-step, both convs' weights resident (w1 / w2 in the pack_conv fragment order, ConvLayer::w_hi), ten output rows
 // per patch, the two last m rows of a patch stay in LDS for the patch below.  false: not applicable (the caller runs the two convs)
+bool arsb32c_applicable(int B, int H, int W, float slope, bool x_lo, bool y_lo, int cin);
 bool launch_arsb32c(ArsbArgs a, int max_groups, hipStream_t s);
 hipError_t arsb32c_init();
 
@@ -227,15 +253,32 @@ struct ConvX3Args {
     // conv64_q8.hip only: in_lo (and res_lo) / out_lo hold fp8 e4m3 words -- (v - fp16(v)) 2^11 / 4, one byte a channel, [B][H][W][64] -- instead of fp16
     int in8, out8;
 };
-bool launch_conv64_x3(ConvX3Args a, int max_groups, hipStream_t s);   // false: not applicable (caller uses the three-launch form)
+// the form of such a layer, as flags (see ConvForm): what the three launchers of ConvX3Args decide on
+struct ConvX3Form {
+    int B = 0, H = 0, W = 0, pool_slabs = 0;
+    float slope = 1.f;
+    bool res = false, res_lo = false, pool = false, gate = false, in8 = false, out8 = false;
+};
+inline ConvX3Form conv_x3_form(const ConvX3Args& a)
+{
+    ConvX3Form c;
+    c.B = a.B; c.H = a.H; c.W = a.W; c.pool_slabs = a.pool_slabs; c.slope = a.slope;
+    c.res = a.res_hi != nullptr; c.res_lo = a.res_lo != nullptr; c.pool = a.pool != nullptr; c.gate = a.gate != nullptr; c.in8 = a.in8 != 0; c.out8 = a.out8 != 0;
+    return c;
+}
+bool conv64_x3_applicable(const ConvX3Form& c, int max_groups);
+bool launch_conv64_x3(ConvX3Args a, int max_groups, hipStream_t s);   // false: !conv64_x3_applicable (the three-launch form takes the layer)
 hipError_t conv64_x3_init();
 // the same conv with its two correction products on fp8 operands (conv64_q8.hip); false: not applicable (caller uses conv64_x3)
+bool conv64_q8_applicable(const ConvX3Form& c);
 bool launch_conv64_q8(ConvX3Args a, int max_groups, hipStream_t s);
 hipError_t conv64_q8_init();
 // the chain form of that layer (fp8 low parts in) streamed down a column by one fp16 wave + one fp8 wave per workgroup (conv64_sq.hip); false: not applicable (caller uses conv64_q8)
+bool conv64_sq_applicable(const ConvX3Form& c, int max_groups);      // (with its performance heuristics: MOE_SQ_EPIS, MOE_SQ_MIN_ITEMS)
 bool launch_conv64_sq(ConvX3Args a, int max_groups, hipStream_t s);
 hipError_t conv64_sq_init();
 // conv64_s.hip: SEDN's fused block tail (per-plane weights, LeakyReLU, residual) streamed down 32-pixel columns with the plane's weights in registers; false: not applicable
+bool conv64_s_applicable(const ConvForm& c);
 bool launch_conv64_s(const ConvArgs& a, int max_groups, hipStream_t s);
 hipError_t conv64_s_init();
 // arsb_sq.hip: ONE exact ARSB of such a chain in one launch -- conv_1's rows stay in LDS (producer / consumer wave pairs); false: not applicable (caller runs the two convs)
@@ -246,6 +289,7 @@ struct ArsbSqArgs {
     float slope;                                         // PReLU slope of conv_1 (<= 1)
     int B, H, W, out8;
 };
+bool arsb_sq_applicable(int B, int H, int W, float slope);
 bool launch_arsb_sq(const ArsbSqArgs& a, int max_groups, hipStream_t s);
 hipError_t arsb_sq_init();
 
@@ -291,7 +335,7 @@ struct StemArgs {
     half_t* out_lo;                  // FP16X3 low part or nullptr
     int B, H, W, taps;
     int out_lo8;                     // the low part as fp8 e4m3 words of lo / 4, one byte a channel (what conv64_q8 with in8 reads: ConvX3Args)
-    // lite (taps == 1; MoeNet_lite2.py:40-41): conv_input2(PReLU(conv_input(x))) is x times a fixed vector -- P for x >= 0, Q for x < 0 (engine.cpp: "stem.p2") -- so the stem
+    // lite (taps == 1; MoeNet_lite2.py:40-41): conv_input2(PReLU(conv_input(x))) is x times a fixed vector -- P for x >= 0, Q for x < 0 (weights.cpp: "stem.p2") -- so the stem
     // writes that tensor as well and the 48 -> 48 1x1 conv is never launched.  w2 = [2][64] fp32 (P, Q) or nullptr; out2 / out2_lo as out / out_lo (out2_lo may be nullptr)
     const float* w2; half_t* out2; half_t* out2_lo;
 };
@@ -328,7 +372,7 @@ struct Tail1SumArgs {
     int nparts;                            // 2: two 32-channel halves per branch (conv_mfma_kernel), 1: complete dot products (conv1x1.hip)
     void* y; int y_dtype; const long long* y_off;
     int B, H, W;
-    // lite, fp16 input: the U branch's value from the table of the net (engine.cpp, moe_net::lut: [256 r][256 r] fp32, the entry of input pattern v and phase (py, px) at
+    // lite, fp16 input: the U branch's value from the table of the net (net.h, moe_net::lut: [256 r][256 r] fp32, the entry of input pattern v and phase (py, px) at
     // ((v >> 8) r + py) 256 r + (v & 255) r + px) instead of p1 (nullptr then); x = the forward's fp16 input (strides in elements, x_off = device [B] offsets or nullptr: b sB)
     const float* lut; int r; const void* x; const long long* x_off; long long sB, sH, sW;
     int vec_ok;                            // every output plane starts 16-byte aligned (the four-outputs-per-thread table kernel)

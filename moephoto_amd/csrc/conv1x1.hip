@@ -306,20 +306,26 @@ hipError_t conv1x1_init()
     return hipSuccess;
 }
 
-// false: the layer is not one of the compiled shapes (caller uses conv_mfma_kernel)
+static int conv1x1_groups(int B, int H, int W, int max_groups) { return (int)std::min<long long>(max_groups, ((long long)B * H * ((W + 31) / 32) + 3) / 4); }
+
+// false: the layer is not one of the compiled shapes (conv_mfma_kernel takes it)
+bool conv1x1_applicable(const Conv1x1Form& a, int max_groups)
+{
+    if (!((a.r == 1 && a.nchunks == 1) || (a.r == 2 && a.nchunks == 4))) return false;
+    if (a.tail && a.r != 2) return false;
+    if (!(a.slope <= 1.f)) return false;
+    if (a.x3 && !a.tail && !a.out_lo) return false;
+    const long long in_b = 128ll * a.B * a.H * a.W, out_b = (a.tail ? 4ll : 2ll * a.out_cs) * a.B * a.H * a.r * a.W * a.r;
+    if (in_b >= (1ll << 32) - 65536 || out_b >= (1ll << 32) - 65536) return false;       // 32-bit buffer offsets
+    return conv1x1_groups(a.B, a.H, a.W, max_groups) >= 1;
+}
+
 bool launch_conv1x1(const Conv1x1Args& a, int max_groups, hipStream_t s)
 {
     const bool x3 = a.in_lo != nullptr, tail = a.tail_out != nullptr;
-    if (!((a.r == 1 && a.nchunks == 1) || (a.r == 2 && a.nchunks == 4))) return false;
-    if (tail && a.r != 2) return false;
-    if (!(a.slope <= 1.f) || !a.bias || !a.w_hi) return false;
-    if (x3 && (!a.w_lo || (!tail && !a.out_lo))) return false;
-    if (!tail && !a.out_hi) return false;
-    const long long in_b = 128ll * a.B * a.H * a.W, out_b = (tail ? 4ll : 2ll * a.out_cs) * a.B * a.H * a.r * a.W * a.r;
-    if (in_b >= (1ll << 32) - 65536 || out_b >= (1ll << 32) - 65536) return false;       // 32-bit buffer offsets
-    const long long ntiles = (long long)a.B * a.H * ((a.W + 31) / 32);
-    const int groups = (int)std::min<long long>(max_groups, (ntiles + 3) / 4);
-    if (groups < 1) return false;
+    if (!conv1x1_applicable(Conv1x1Form{a.B, a.H, a.W, a.r, a.nchunks, a.out_cs, a.slope, x3, tail, a.out_lo != nullptr}, max_groups)) return false;
+    if (!a.bias || !a.w_hi || (x3 && !a.w_lo) || (!tail && !a.out_hi)) return false;
+    const int groups = conv1x1_groups(a.B, a.H, a.W, max_groups);
     if (a.nchunks == 1) { if (x3) launch_t<true, 1, false>(a, groups, s); else launch_t<false, 1, false>(a, groups, s); }
     else if (!tail) { if (x3 && a.nks == 3) launch_t<true, 4, false, 3>(a, groups, s); else if (x3) launch_t<true, 4, false>(a, groups, s); else launch_t<false, 4, false>(a, groups, s); }
     else { if (x3 && a.nks == 3) launch_t<true, 4, true, 3>(a, groups, s); else if (x3) launch_t<true, 4, true>(a, groups, s); else launch_t<false, 4, true>(a, groups, s); }

@@ -262,16 +262,22 @@ hipError_t conv1x1_f2_init()
     return hipFuncSetAttribute((const void*)conv1x1_f2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
 }
 
-// false: not this kernel's case (the caller runs the stages one by one on conv1x1.hip)
+static int conv1x1_f2_groups(int B, int H, int W, int max_groups) { return (int)std::min<long long>(max_groups, ((long long)B * H * ((W + 31) / 32) + 3) / 4); }
+
+// false: not this kernel's case (the stages run one by one on conv1x1.hip)
+bool conv1x1_f2_applicable(int B, int H, int W, float slope_a, float slope_b, int max_groups)
+{
+    if (!(slope_a <= 1.f) || !(slope_b <= 1.f)) return false;
+    const long long in_b = 128ll * B * H * W, out_b = 64ll * B * H * W;
+    if (in_b >= (1ll << 32) - 65536 || out_b >= (1ll << 32) - 65536) return false;       // 32-bit buffer offsets
+    return conv1x1_f2_groups(B, H, W, max_groups) >= 1;
+}
+
 bool launch_conv1x1_f2(const Conv1x1F2Args& a, int max_groups, hipStream_t s)
 {
     if (!a.in_hi || !a.in_lo || !a.wa_hi || !a.wa_lo || !a.wb_hi || !a.wb_lo || !a.bias_a || !a.bias_b || !a.tail_w || !a.tail_out) return false;
-    if (!(a.slope_a <= 1.f) || !(a.slope_b <= 1.f)) return false;
-    const long long in_b = 128ll * a.B * a.H * a.W, out_b = 64ll * a.B * a.H * a.W;
-    if (in_b >= (1ll << 32) - 65536 || out_b >= (1ll << 32) - 65536) return false;       // 32-bit buffer offsets
-    const long long ntiles = (long long)a.B * a.H * ((a.W + 31) / 32);
-    const int groups = (int)std::min<long long>(max_groups, (ntiles + 3) / 4);
-    if (groups < 1) return false;
+    if (!conv1x1_f2_applicable(a.B, a.H, a.W, a.slope_a, a.slope_b, max_groups)) return false;
+    const int groups = conv1x1_f2_groups(a.B, a.H, a.W, max_groups);
     conv1x1_f2_kernel<<<dim3(groups), dim3(256), LDS, s>>>(a);
     return true;
 }

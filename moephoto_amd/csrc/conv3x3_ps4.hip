@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
         for (int f = 28; f < 36; ++f) asm volatile("" : "+v"(wf[1][f]));
     }
     // ---- LDS tables: bias as the accumulators' initial value ([wave][cg][hh][16]: register 4q + e of a lane is MFMA row 8q + 4hh + e), the tail
-    // conv's A fragments (engine.cpp tail(): rows 0..8 fp16 weights, rows 16..24 their remainders; fragments 4..7 for the activations' low parts),
+    // conv's A fragments (weights.cpp tail(): rows 0..8 fp16 weights, rows 16..24 their remainders; fragments 4..7 for the activations' low parts),
     // the tap-image ring as zeros (the slots no lane ever writes -- the consumer column beyond the 32 pixels -- stay zero)
     {
         const int bw = tid >> 6, bcg = (tid >> 5) & 1, bhh = (tid >> 4) & 1, bq = (tid >> 2) & 3, be = tid & 3;
@@ -651,16 +651,21 @@ bool ps4_applicable(int B, int H, int W)
     return (long long)B * ((W + kTileW - 1) / kTileW) * (H / RB) < (1ll << 31) / 4;
 }
 
+bool ps4_store_applicable(int B, int H, int W, float slope)      // (the store form has the fused tail's shape conditions, and stores the HR tensor)
+{
+    return ps4_tail_applicable(B, H, W, slope) && (long long)B * H * W * 512 < (1ll << 32) - 65536;
+}
+
 // false: not applicable (the caller keeps conv3x3_rw + tapsum4)
 bool launch_conv3x3_ps4(const Ps4Args& a, int max_groups, hipStream_t s)
 {
-    if (!ps4_tail_applicable(a.B, a.H, a.W, a.slope)) return false;      // (the store form below has the same shape conditions)
+    if (!(a.out ? ps4_store_applicable(a.B, a.H, a.W, a.slope) : ps4_tail_applicable(a.B, a.H, a.W, a.slope))) return false;
     const int px = (a.W + kTileW - 1) / kTileW;
     const long long items = (long long)a.B * px * (a.H / RB);
     const int G = (int)std::min<long long>(items, max_groups);
     const bool ragged = a.W % kTileW != 0;
     if (a.out) {        // store form
-        if (a.plane || (long long)a.B * a.H * a.W * 512 >= (1ll << 32) - 65536) return false;
+        if (a.plane) return false;
         conv3x3_ps4_kernel<0, true><<<dim3(G), dim3(256), LDS_BYTES, s>>>(a);
         return true;
     }

@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
         slope2 = __builtin_bit_cast(unsigned, s2);
     }
     // fused tail: A fragments of the 64 -> 1 conv for this wave's two 16-channel k-slices (rows = taps, rows 16..24 their rounding remainders);
-    // tailw2 (EPI 7): the fp16 tail weights again, in rows 16..24, for the activations' low parts (engine.cpp, tail())
+    // tailw2 (EPI 7): the fp16 tail weights again, in rows 16..24, for the activations' low parts (weights.cpp, tail())
     half8_t tailw[2], tailw2[2];
 #pragma unroll
     for (int gp = 0; gp < 2; ++gp) {
@@ -796,18 +796,23 @@ hipError_t conv3x3_rw_init()
     return set_limit<3>();
 }
 
-// false: not one of the compiled epilogues / shapes (caller uses conv3x3_sp)
-bool launch_conv3x3_rw(const ConvArgs& a, hipStream_t s)
+// false: not one of the compiled epilogues / shapes (conv3x3_sp takes the layer)
+bool conv3x3_rw_applicable(const ConvForm& a)
 {
     if (a.acc_mode != 0 || a.dbg || a.plane_w || a.res || a.out_lo || a.side16) return false;
-    if (!(a.slope < 1.f) || a.scale != 1.f || !a.bias_img || a.in_cs != 64) return false;
-    const bool tail = a.tplanes != nullptr;
-    if (tail && (a.tail_form != 1 || a.r != 2 || a.nchunks != 4 || a.W % 4 != 0 || !tailsum_fits(a.B, a.H, a.W))) return false;     // (the nine-plane form lives in conv3x3_sp.hip)
-    if (!tail && !a.out) return false;
+    if (!(a.slope < 1.f) || a.scale != 1.f || a.in_cs != 64) return false;
+    if (a.tail && (a.tail_form != 1 || a.r != 2 || a.nchunks != 4 || a.W % 4 != 0 || !tailsum_fits(a.B, a.H, a.W))) return false;     // (the nine-plane form lives in conv3x3_sp.hip)
     if (2ll * a.B * a.H * a.W * a.in_cs + 2ll * (a.W + 1) * a.in_cs >= (1ll << 32) - 65536) return false;
-    if (!tail && 2ll * a.B * a.H * a.r * a.W * a.r * a.out_cs >= (1ll << 32) - 65536) return false;
+    if (!a.tail && 2ll * a.B * a.H * a.r * a.W * a.r * a.out_cs >= (1ll << 32) - 65536) return false;
+    if (a.pool && (a.tail || a.nchunks != 1 || a.r != 1 || a.pool_slabs < 2 * std::min(a.G, a.py) || (a.G % a.py != 0 && a.py % a.G != 0))) return false;
+    return true;
+}
+
+bool launch_conv3x3_rw(const ConvArgs& a, hipStream_t s)
+{
+    const bool tail = a.tplanes != nullptr;
+    if (!conv3x3_rw_applicable(conv_form(a)) || !a.bias_img || (!tail && !a.out)) return false;
     const int blocks = a.nchunks * ((a.G + 7) / 8) * 8;
-    if (a.pool && (tail || a.nchunks != 1 || a.r != 1 || a.pool_slabs < 2 * std::min(a.G, a.py) || (a.G % a.py != 0 && a.py % a.G != 0))) return false;
     const bool ragged = a.H % kTileH != 0 || a.W % kTileW != 0;
     if (tail && a.tail_split) {
         if (ragged) conv3x3_rw_kernel<7, true><<<dim3(blocks), dim3(256), LDS_BYTES, s>>>(a);

@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void conv3x3_sp_kernel(ConvArgs a)
         tailw[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
         tailw2[i] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
         if (TAIL) tailw[i] = *(const half8_t*)(a.tail_w + i * 512 + lane * 8);
-        if (TAIL2) tailw2[i] = *(const half8_t*)(a.tail_w + (4 + i) * 512 + lane * 8);     // rows 16..24 = fp16 tail weights (engine.cpp)
+        if (TAIL2) tailw2[i] = *(const half8_t*)(a.tail_w + (4 + i) * 512 + lane * 8);     // rows 16..24 = fp16 tail weights (weights.cpp, tail())
     }
     float16_t Gacc[2];
 #pragma unroll
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void conv3x3_sp_kernel(ConvArgs a)
                 Gacc[o] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tailw2[nb * 2 + gp], bl, Gacc[o], 0, 0, 0);
             }
             if ((s8 & 3) == 3) {     // row o complete: lane (j, hh) holds taps 4*hh .. 4*hh+3 in regs 0..3 and tap 8 + 4*hh in reg 4
-                // rows 16..24 of the A fragments hold the rounding remainders of the tail weights (units of 2^-11, engine.cpp): the
+                // rows 16..24 of the A fragments hold the rounding remainders of the tail weights (units of 2^-11, weights.cpp): the
                 // same MFMAs formed the low-order sums in regs 8..12 -- fold them in (5 FMAs per row for ~22-bit tail weights)
 #pragma unroll
                 for (int k = 0; k < 5; ++k) Gacc[o][k] = __builtin_fmaf(Gacc[o][8 + k], 0.00048828125f, Gacc[o][k]);
@@ -706,21 +706,27 @@ hipError_t conv3x3_sp_init()
     return hipSuccess;
 }
 
-// Returns false when the layer's epilogue is not one of the four compiled variants (caller uses another kernel).
-bool launch_conv3x3_sp(const ConvArgs& a, hipStream_t s)
+// false: the layer's epilogue is not one of the compiled variants, or the shape leaves the kernel's 32-bit offsets (another kernel takes the layer)
+bool conv3x3_sp_applicable(const ConvForm& a)
 {
     const bool x3 = a.acc_mode == 3 && a.side16 && a.out_lo;          // split-precision final pass (the low-order products are in side16)
     if ((a.acc_mode != 0 && !x3 && !(a.dbg & 64)) || a.slope > 1.f) return false;
     // 32-bit BYTE offsets for stores / residual loads (the fused-tail epilogue stores no tensor: its tap planes are checked below)
-    if (!a.tplanes && 2ll * a.B * a.H * a.r * a.W * a.r * a.out_cs >= (1ll << 32) - 8192) return false;
+    if (!a.tail && 2ll * a.B * a.H * a.r * a.W * a.r * a.out_cs >= (1ll << 32) - 8192) return false;
     if (2ll * a.B * a.H * a.W * a.in_cs + 2ll * (a.W + 1) * a.in_cs >= (1ll << 32) - 65536) return false;   // 32-bit buffer offsets of the patch DMA
-    if (a.scale != 1.f || !a.bias_img) return false;           // the engine folds ScaleLayer into the weights and always passes a bias vector
-    const bool act = a.slope != 1.f, res = a.res != nullptr, tail = a.tplanes != nullptr;
-    if ((act || tail) && res && !a.plane_w) return false;
-    if (x3 && (tail || a.res_lo)) return false;                        // (the engine folds res_lo into side16)
-    if (tail && 36ll * a.B * a.H * a.r * a.W * a.r >= (1ll << 32) - 8192) return false;
-    const bool planew = a.plane_w != 0;                                 // per-plane weights: act + residual only (SEDN fused block tail)
-    if (planew && (!res || tail || x3 || a.r != 1)) return false;
+    if (a.scale != 1.f) return false;                          // the engine folds ScaleLayer into the weights
+    const bool act = a.slope != 1.f;
+    if ((act || a.tail) && a.res && !a.plane_w) return false;
+    if (x3 && (a.tail || a.res_lo)) return false;                      // (the engine folds res_lo into side16)
+    if (a.tail && (36ll * a.B * a.H * a.r * a.W * a.r >= (1ll << 32) - 8192 || a.W % 4 != 0)) return false;      // (the fused tail stores its tap planes four input columns at a time)
+    if (a.plane_w && (!a.res || a.tail || x3 || a.r != 1)) return false;        // per-plane weights: act + residual only (SEDN fused block tail)
+    return true;
+}
+
+bool launch_conv3x3_sp(const ConvArgs& a, hipStream_t s)
+{
+    if (!conv3x3_sp_applicable(conv_form(a)) || !a.bias_img) return false;     // (the engine always passes a bias vector)
+    const bool x3 = a.acc_mode == 3 && a.side16 && a.out_lo, res = a.res != nullptr, act = a.slope != 1.f, tail = a.tplanes != nullptr, planew = a.plane_w != 0;
     const int epi = planew ? 6 : x3 ? (res ? 5 : 4) : tail ? (a.tail_split ? 7 : 3) : (res ? 2 : (act ? 1 : 0));
     const int blocks = planew ? a.G : a.nchunks * ((a.G + 7) / 8) * 8;          // per-plane weights: a.G is the TOTAL number of workgroups
     const dim3 grid(blocks), blk(256);

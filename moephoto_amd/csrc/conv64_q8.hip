@@ -12,7 +12,7 @@
 // its scale operand and gives NaN beyond 464 unless MODE.FP16_OVFL is set -- the kernel runs with it: saturation at +-448).
 //
 // Drop-in for conv64_x3.hip (same tensors in and out) -- and, between two layers of this kernel, a cheaper interface: the low part of an activation tensor as
-// the fp8 word the correction product reads anyway (ConvX3Args::in8 / out8, template parameters IN8 / OUT8; engine.cpp plans the chain: Act::lo8).  These
+// the fp8 word the correction product reads anyway (ConvX3Args::in8 / out8, template parameters IN8 / OUT8; forward_arsb.cpp plans the chain: Act::lo8).  These
 // layers are held by their bytes (profiles/r03/o_stream_bytes.txt): 384 / 576 instead of 512 / 768 bytes a pixel, and the a_lo image arrives by DMA.
 //
 //   wave (c, h)   output channels 32c .. 32c+31, output rows 4h .. 4h+3 of the 8 x 32 patch (arsb32.hip's conv_2 half)
@@ -686,11 +686,23 @@ hipError_t conv64_q8_init()
     return set_limit<2, true, false>();
 }
 
-// false: the layer does not fit this kernel (caller uses conv64_x3)
-bool launch_conv64_q8(ConvX3Args a, int max_groups, hipStream_t s)
+// formats of the low parts (in8: input and residual, out8: output) -- the combinations a chain of these layers needs (forward_arsb.cpp, chain8):
+//   conv_input2 fp8 (the stem writes it) or fp16 -> fp8 | conv_1 fp8 -> fp8 | conv_2 fp8 -> fp8, and fp8 -> fp16 for the last one (the fused ARSB kernels read fp16 low parts)
+static int conv64_q8_fmt(const ConvX3Form& a) { return (a.res ? 2 : a.slope != 1.f ? 1 : 0) * 4 + (a.in8 ? 2 : 0) + (a.out8 ? 1 : 0); }
+
+// false: the layer does not fit this kernel (conv64_x3 takes it)
+bool conv64_q8_applicable(const ConvX3Form& a)
 {
     if (!(a.slope <= 1.f)) return false;
     if ((long long)a.B * a.H * a.W * 128 + (a.W + 1ll) * 128 >= (1ll << 32) - 65536) return false;
+    if (a.pool || a.res != a.res_lo || (a.res && a.slope != 1.f)) return false;
+    const int fmt = conv64_q8_fmt(a);
+    return fmt == 0 || fmt == 1 || fmt == 3 || fmt == 4 || fmt == 7 || fmt == 8 || fmt == 10 || fmt == 11;      // (the compiled ones)
+}
+
+bool launch_conv64_q8(ConvX3Args a, int max_groups, hipStream_t s)
+{
+    if (!conv64_q8_applicable(conv_x3_form(a))) return false;
 #ifdef Q8_TRACE
     static unsigned long long* tbuf = nullptr;
     static int tcount = 0;
@@ -710,16 +722,12 @@ bool launch_conv64_q8(ConvX3Args a, int max_groups, hipStream_t s)
         return false;
 #endif
     }
-    if ((a.res_hi == nullptr) != (a.res_lo == nullptr)) return false;
-    if (a.res_hi && a.slope != 1.f) return false;
     a.px = (a.W + TW - 1) / TW;
     a.py = (a.H + TH - 1) / TH;
     const long long items = (long long)a.B * a.px * a.py;
     const int G = (int)std::min<long long>(items, max_groups);
     const dim3 grid(G), blk(256);
-    // formats of the low parts (in8: input and residual, out8: output) -- the combinations a chain of these layers needs (engine.cpp, forward):
-    //   conv_input2 fp8 (the stem writes it) or fp16 -> fp8 | conv_1 fp8 -> fp8 | conv_2 fp8 -> fp8, and fp8 -> fp16 for the last one (the fused ARSB kernels read fp16 low parts)
-    const int epi = a.res_hi ? 2 : a.slope != 1.f ? 1 : 0, fmt = epi * 4 + (a.in8 ? 2 : 0) + (a.out8 ? 1 : 0);
+    const int fmt = conv64_q8_fmt(conv_x3_form(a));
     const size_t lds = LDS_BYTES + TRACE_LDS;
     switch (fmt) {
     case 0: conv64_q8_kernel<0, false, false><<<grid, blk, lds, s>>>(a); break;

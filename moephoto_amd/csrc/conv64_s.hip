@@ -1,5 +1,5 @@
 // conv64_s.hip -- SEDN's fused block tail (python/models.py:186-224 of the reference: rblock.4 and the 1x1 `trans` folded, per plane, into one effective 3x3 64->64 conv,
-// y = x + LeakyReLU(conv(W_eff[b], t)); engine.cpp, misc_kernels.hip: sedn_weff) STREAMED down a 32-pixel column: conv64_sq.hip without its fp8 half, with the
+// y = x + LeakyReLU(conv(W_eff[b], t)); forward_sedn.cpp, misc_kernels.hip: sedn_weff) STREAMED down a 32-pixel column: conv64_sq.hip without its fp8 half, with the
 // plane's weights in REGISTERS.  conv3x3_sp<6> kept the per-plane weights in LDS and read 72 of its 120 fragments per patch for them: 166 us a launch; this form 145.
 //
 //   workgroup     TWO waves (c = 0, 1: output channels 32c .. 32c+31; 36 fp16 A fragments = 144 registers in AGPRs), two workgroups per CU
@@ -345,16 +345,20 @@ hipError_t set_limit() { return hipFuncSetAttribute((const void*)conv64_s_kernel
 hipError_t conv64_s_init() { return set_limit<6>(); }
 
 // false: not this kernel's layer (the caller uses conv3x3_sp<6>)
-bool launch_conv64_s(const ConvArgs& a, int max_groups, hipStream_t s)
+bool conv64_s_applicable(const ConvForm& a)
 {
-    if (a.r != 1 || a.in_cs != 64 || a.out_cs != 64 || a.out_lo || a.in_lo || a.res_lo || a.acc_mode != 0 || a.tplanes || a.tail1_w || a.pool || a.scale != 1.f || a.dbg) return false;
+    if (a.r != 1 || a.in_cs != 64 || a.out_cs != 64 || a.out_lo || a.in_lo || a.res_lo || a.acc_mode != 0 || a.tail || a.tail1 || a.pool || a.scale != 1.f || a.dbg) return false;
     if (!(a.slope <= 1.f) || a.H % RB != 0 || a.H < RB) return false;
     if ((long long)a.B * a.H * a.W * 128 + (long long)((RB + 1) * a.W + 2) * 128 >= (1ll << 32) - 65536) return false;
     if (!a.plane_w || !a.res || a.nchunks != a.B) return false;      // (EPI 1 -- shared weights, no residual -- is not instantiated: see the head of the file)
+    return (long long)a.B * ((a.W + TW - 1) / TW) * (a.H / RB) < (1ll << 31) / 4;
+}
+
+bool launch_conv64_s(const ConvArgs& a, int max_groups, hipStream_t s)
+{
+    if (!conv64_s_applicable(conv_form(a))) return false;
     if (!a.in || !a.out || !a.wpk || a.in == a.out) return false;
-    const int px = (a.W + TW - 1) / TW;
-    const long long items = (long long)a.B * px * (a.H / RB);
-    if (items >= (1ll << 31) / 4) return false;
+    const long long items = (long long)a.B * ((a.W + TW - 1) / TW) * (a.H / RB);
     const int G = (int)std::min<long long>(items, 2ll * max_groups);
     conv64_s_kernel<6><<<dim3(G), dim3(128), LDS_RES, s>>>(a);
     return true;

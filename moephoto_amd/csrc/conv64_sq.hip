@@ -566,15 +566,14 @@ hipError_t conv64_sq_init()
 }
 
 // The chain form of conv64_q8.hip's layer (fp8 low parts in; out: fp8, or fp16 behind the last layer).  false: not this kernel's (the caller uses conv64_q8)
-bool launch_conv64_sq(ConvX3Args a, int max_groups, hipStream_t s)
+bool conv64_sq_applicable(const ConvX3Form& a, int max_groups)
 {
     if (!(a.slope <= 1.f) || !a.in8 || a.pool) return false;
     if (a.H % RB != 0 || a.H < RB) return false;
     if ((long long)a.B * a.H * a.W * 128 + (long long)((RB + 1) * a.W + 2) * 128 >= (1ll << 32) - 65536) return false;
-    if (!a.in_hi || !a.in_lo || !a.out_hi || !a.out_lo || !a.wq_hi16 || !a.wq_hi8 || !a.wq_lo8) return false;
-    if ((a.res_hi == nullptr) != (a.res_lo == nullptr)) return false;
-    if (a.res_hi && a.slope != 1.f) return false;
-    const int epi = a.res_hi ? 2 : a.slope != 1.f ? 1 : 0;
+    if (a.res != a.res_lo) return false;
+    if (a.res && a.slope != 1.f) return false;
+    const int epi = a.res ? 2 : a.slope != 1.f ? 1 : 0;
     if (!a.out8 && epi != 2) return false;
     static const int epis = [] { const char* e = getenv("MOE_SQ_EPIS"); int m = 0; if (!e) return 7; for (; *e; ++e) if (*e >= '0' && *e <= '2') m |= 1 << (*e - '0'); return m; }();      // (diagnosis: the layer kinds this kernel takes)
     if (!(epis >> epi & 1)) return false;
@@ -585,7 +584,15 @@ bool launch_conv64_sq(ConvX3Args a, int max_groups, hipStream_t s)
     // profiles/r04/k_conv64_sq_frame_launches.txt) -- and still take this kernel: which form a layer runs on must not depend on how many tiles share its
     // launch, or a tile's bits would (the two forms differ in the order of their sums).  MOE_SQ_MIN_ITEMS = blocks per workgroup below which the patch form runs (experiments).
     static const long long min_items = [] { const char* e = getenv("MOE_SQ_MIN_ITEMS"); return e ? atoll(e) : 0ll; }();
-    if (items < min_items * 2 * max_groups) return false;
+    return items >= min_items * 2 * max_groups;
+}
+
+bool launch_conv64_sq(ConvX3Args a, int max_groups, hipStream_t s)
+{
+    if (!conv64_sq_applicable(conv_x3_form(a), max_groups)) return false;
+    if (!a.in_hi || !a.in_lo || !a.out_hi || !a.out_lo || !a.wq_hi16 || !a.wq_hi8 || !a.wq_lo8) return false;
+    const int epi = a.res_hi ? 2 : a.slope != 1.f ? 1 : 0;
+    const long long items = (long long)a.B * ((a.W + TW - 1) / TW) * (a.H / RB);
     const int G = (int)std::min<long long>(items, 2ll * max_groups);
     const dim3 grid(G), blk(128);
     if (epi == 0) conv64_sq_kernel<0, true><<<grid, blk, LDS_PLAIN, s>>>(a);

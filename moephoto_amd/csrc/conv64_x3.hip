@@ -13,7 +13,7 @@
 //   pass 2  streams the ten rows of the a_lo patch:  acc_lo += w_hi a_lo                             (36 MFMAs per row)
 //           and finishes each output row as soon as its third a_lo row is in: v = acc_hi + acc_lo 2^-11 in fp32, then
 //           EPI 0 plain | 1 PReLU (fp32, slope <= 1) | 2 + residual (hi + lo 2^-11) | 3 plain + pooled channel sums | 4 PReLU + pooled | 5 gate[plane][channel] * conv +
-//           residual (lite's LB with the FRM gate known BEFORE conv_2 runs: engine.cpp, frm_pre_kernel); hi and lo parts stored, 16 bytes per lane.
+//           residual (lite's LB with the FRM gate known BEFORE conv_2 runs: forward_lite.cpp, frm_pre_kernel); hi and lo parts stored, 16 bytes per lane.
 //
 // LDS: a_hi double buffered (its DMA for patch p+1 rides in pass 2 of patch p), a_lo single buffered: it is only live during pass 2,
 // so its DMA for patch p is issued behind the barrier that opens patch p and lands while pass 1 runs.  2 x 45,056 + 45,056 B.
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void conv64_x3_kernel(ConvX3Args a)
         return it;
     };
 
-    // ---- weights (arsb order, engine.cpp pack_arsb): hi and lo parts, 2 x 18 A fragments, parked in the accumulator registers --------
+    // ---- weights (arsb order, weights.cpp pack_arsb): hi and lo parts, 2 x 18 A fragments, parked in the accumulator registers --------
     half8_t wh[18], wl[18];
 #pragma unroll
     for (int f = 0; f < 18; ++f) {
@@ -350,21 +350,32 @@ hipError_t conv64_x3_init()
     return set_limit<2>();
 }
 
-// false: the layer does not fit this kernel (caller uses the three-launch form)
-bool launch_conv64_x3(ConvX3Args a, int max_groups, hipStream_t s)
+static int conv64_x3_groups(int B, int H, int W, bool pool, int max_groups)
+{
+    const int px = (W + TW - 1) / TW, py = (H + TH - 1) / TH;
+    const long long items = (long long)B * px * py;
+    return pool ? pooled_groups((long long)px * py, items, max_groups) : (int)std::min<long long>(items, max_groups);
+}
+
+// false: the layer does not fit this kernel (the three-launch form takes it)
+bool conv64_x3_applicable(const ConvX3Form& a, int max_groups)
 {
     if (!(a.slope <= 1.f)) return false;
     if ((long long)a.B * a.H * a.W * 128 >= (1ll << 32) - 65536) return false;
+    if (a.res != a.res_lo) return false;
+    if (a.res && a.slope != 1.f) return false;
+    if (a.pool && (a.res || a.pool_slabs < conv64_x3_groups(a.B, a.H, a.W, true, max_groups))) return false;
+    if (a.gate && !a.res) return false;
+    return true;
+}
+
+bool launch_conv64_x3(ConvX3Args a, int max_groups, hipStream_t s)
+{
+    if (!conv64_x3_applicable(conv_x3_form(a), max_groups)) return false;
     if (!a.in_hi || !a.in_lo || !a.out_hi || !a.out_lo || !a.w_hi || !a.w_lo) return false;
-    if ((a.res_hi == nullptr) != (a.res_lo == nullptr)) return false;
-    if (a.res_hi && a.slope != 1.f) return false;
     a.px = (a.W + TW - 1) / TW;
     a.py = (a.H + TH - 1) / TH;
-    const long long items = (long long)a.B * a.px * a.py;
-    const int G = a.pool ? pooled_groups((long long)a.px * a.py, items, max_groups) : (int)std::min<long long>(items, max_groups);
-    const dim3 grid(G), blk(256);
-    if (a.pool && (a.res_hi || a.pool_slabs < G)) return false;
-    if (a.gate && !a.res_hi) return false;
+    const dim3 grid(conv64_x3_groups(a.B, a.H, a.W, a.pool != nullptr, max_groups)), blk(256);
     if (a.pool && a.slope != 1.f) conv64_x3_kernel<4><<<grid, blk, LDS_BYTES, s>>>(a);
     else if (a.pool) conv64_x3_kernel<3><<<grid, blk, LDS_BYTES, s>>>(a);
     else if (a.gate) conv64_x3_kernel<5><<<grid, blk, LDS_BYTES, s>>>(a);

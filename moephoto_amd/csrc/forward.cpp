@@ -1,51 +1,41 @@
-// forward.cpp -- one forward of a net: Fwd::conv (which kernel a layer resolves to), the workspace plan, the launch sets, the calls that run
-// ahead of the caller's stream, and the entry points around them.
+// forward.cpp -- one forward of a net: Fwd::route (which kernel a layer resolves to) and Fwd::launch (that kernel's arguments), the workspace plan and its check, the
+// launch sets, the calls that run ahead of the caller's stream, and the entry points around them.
 //
 // PLANNING PASS AND LAUNCHING PASS ARE ONE CODE PATH.  The sequence of a family (forward_arsb / forward_sedn / forward_lite) is run twice per launch set: first by
-// workspace_need with an Arena that has no base (Fwd::dry(): Arena::take only counts, conv / stem / tail and every `if (!f.dry())` block launch nothing), then by
+// workspace_need with an Arena that has no base (Fwd::dry(): Arena::take only counts, launch / stem / tail and every `if (!f.dry())` block launch nothing), then by
 // forward_dev_chunk over the workspace of that size.  So every f.ar.take -- f.act included -- must come in the same order, with the same sizes, on both passes:
 // what decides whether a buffer is taken may depend on the net, its options and the shape, never on a pointer or on what a kernel launcher answered.
+//
+// HOW A LAYER FINDS ITS KERNEL.  Fwd::conv = route, then (launching pass only) launch.  route is a pure function of the layer, the options, the shape and the operands'
+// forms -- flags: Act::has_lo / lo8, ConvExtra's requests -- and asks each candidate kernel's *_applicable predicate (common.h), the very function its launcher refuses
+// by; its answer (kernel, pooled, gated, tail parts, ok) is the same on both passes, so the sequences branch on it freely.  launch fills the arguments of exactly that
+// kernel: a launcher that refuses what its predicate promised is an internal error naming layer and kernel, never a fall-through to another kernel.
+//
+// THE CHECK.  The arena of the launching pass carries the planned size as its limit: a take beyond it turns the rest of the sequence dry (nothing is launched over
+// memory the plan did not size) and fails the forward; behind the sequence forward_dev_chunk compares the two passes' final offsets (plan_matches).
 #include "net.h"
 
 using namespace moe;
 
 namespace moe {
 
-// one convolution layer: in [B][H][W][64*nseg] -> out [B][H*r][W*r][r>1 ? 64 : 64*nchunks]
-// returns false only when asked for the fused tail (tplanes != nullptr) and the fused kernel cannot take the layer
-ConvDone Fwd::conv(const std::string& key, const Act& in, const Act& out, const Act* res, int H, int W, const ConvExtra& e)
+const char* kernel_name(ConvKernel k)      // (in ConvKernel's order)
 {
-    ConvDone done;
-    if (dry()) return done;
-    const bool x3 = this->x3 || e.exact;      // split operands for this layer (every layer under FP16X3, selected ones under MIXED)
-    const ConvLayer& L = n.convs[n.conv_index.at(key)];
-    const bool any8 = in.lo8 || out.lo8 || (res && res->lo8);      // fp8 low parts: conv64_q8 or nothing (the caller planned the chain with q8_chain_ok)
-    if (any8 && !(x3 && use_q8() && q8_capable(L) && !direct)) return ConvDone{false};
-    const int out_cs = L.r > 1 ? 64 : 64 * L.nchunks;
-    if (direct) {
-        DirectConvArgs d{};
-        d.in = in.hi; d.out = out.hi; d.res = res ? res->hi : nullptr;
-        d.w = blob<float>(L.w_plain);
-        d.bias = L.has_bias ? blob<float>(L.bias_plain) : nullptr;
-        d.w_batch_stride = 0;
-        d.B = B; d.H = H; d.W = W; d.in_cs = 64 * L.nseg; d.out_cs = out_cs; d.cin = L.cin; d.cout = L.cout; d.k = L.k; d.r = L.r;
-        d.slope = L.slope; d.scale = L.scale;
-        if (L.per_plane) { d.w = (const float*)e.plane_w; d.w_batch_stride = (long long)L.cout * L.cin; }
-        launch_conv_direct(d, s);
-        return done;
-    }
-    ConvArgs a{};
-    a.in = in.hi; a.out = out.hi; a.res = res ? res->hi : nullptr;
-    a.wpk = L.per_plane ? e.plane_w : blob<half_t>(L.w_hi);
-    a.bias = L.has_bias ? blob<float>(L.bias) : nullptr;
-    a.zero = small<half_t>("zero");
-    a.bias_img = blob<float>(L.bias_img);
-    a.trash = small<half_t>("trash");
-    if (!a.bias) a.bias = small<float>("zero_bias");   // kernels initialise their accumulators from the bias vector
-    a.w_batch_stride = L.per_plane ? (long long)L.nchunks * L.nfrag() * 512 : 0;
-    a.B = B; a.H = H; a.W = W; a.in_cs = 64 * L.nseg; a.out_cs = out_cs; a.r = L.r; a.nchunks = L.nchunks;
-    a.px = (W + kTileW - 1) / kTileW; a.py = (H + kTileH - 1) / kTileH;
-    const long long items = (long long)B * a.px * a.py;
+    static const char* const names[] = {"no kernel", "conv_direct", "conv1x1", "conv_mfma", "conv3x3_sp", "conv3x3_rw", "conv3x3_ps4 (store form)", "conv3x3_sp (hi + lo residual)",
+                                        "conv_mfma (three products)", "conv64_x3", "conv64_q8", "conv64_sq", "conv3x3_sp (three launches)", "conv_mfma (fp32 side buffer)"};
+    return names[(int)k];
+}
+
+// 3x3 / 64-input-channel layers with shared weights run on the fast kernels (conv3x3_sp.hip and its relatives); everything else (1x1 convs, SEDN's per-plane
+// `trans`, MOE_CONV_IMPL=v1) on the generic one
+static bool fast_layer(const moe_net& n, const ConvLayer& L) { return L.taps == 9 && L.nseg == 1 && !L.per_plane && n.opt.conv_impl == 2; }
+
+ConvForm Fwd::form(const ConvLayer& L, int H, int W) const
+{
+    ConvForm c;
+    c.B = B; c.H = H; c.W = W; c.in_cs = 64 * L.nseg; c.out_cs = L.r > 1 ? 64 : 64 * L.nchunks; c.r = L.r; c.nchunks = L.nchunks;
+    c.py = (H + kTileH - 1) / kTileH;
+    const long long items = (long long)B * ((W + kTileW - 1) / kTileW) * c.py;
     // Workgroup (chunk, g) is block ((g / 8) * nchunks + chunk) * 8 + g % 8 and blocks go round-robin to the 8 XCDs, so an XCD gets
     // nchunks * ceil(G / 8) persistent workgroups: keep that within its CUs (one 160-KiB workgroup per CU), or some XCDs need a
     // second round (Net3x: 9 chunks x G = 28 put 36 workgroups on four XCDs of 32 CUs -- 0.67 instead of 0.48 ms per launch)
@@ -53,126 +43,86 @@ ConvDone Fwd::conv(const std::string& key, const Act& in, const Act& out, const 
     int G = per_xcd >= L.nchunks ? 8 * (per_xcd / L.nchunks) : n.max_groups / L.nchunks;
     if (G < 1) G = 1;
     if (G > items) G = (int)items;
-    a.G = G;
-    a.slope = L.slope; a.scale = L.scale;
-    const int dbg = n.opt.dbg;
-    a.dbg = dbg;
-    a.tail_w = e.tail_w; a.tplanes = e.tplanes; a.tail_form = e.tplanes ? tail_form : 0;
-    a.tail_split = (e.tplanes && mixed && tail_split_for(key)) ? 1 : 0;
-    a.tail1_w = e.tail1_w; a.tail1_out = e.tail1_out;
-    if (e.pool_out && !x3 && L.r == 1 && L.nchunks == 1 && !res && pooled_groups_ok((long long)a.py, (long long)B * a.py, n.max_groups)) {      // conv3x3_rw's pooled epilogue (SEDN rblock.2)
-        a.pool = e.pool_out; a.pool_slabs = e.pool_slabs;
-        a.G = pooled_groups((long long)a.py, (long long)B * a.py, n.max_groups);      // its work items are patch ROWS (conv3x3_rw.hip, EPI 4): slab contents independent of the launch's plane count (common.h)
+    c.G = G;
+    c.slope = L.slope; c.scale = L.scale; c.dbg = n.opt.dbg;
+    return c;
+}
+
+ConvRoute Fwd::route(const std::string& key, const Act& in, const Act& out, const Act* res, int H, int W, const ConvExtra& e) const
+{
+    ConvRoute r;
+    auto take = [&r](ConvKernel k) { r.kernel = k; return r; };
+    auto refuse = [&r]() { r.kernel = ConvKernel::none; r.done.ok = false; return r; };
+    const ConvLayer& L = n.convs[n.conv_index.at(key)];
+    const bool x3 = this->x3 || e.exact;      // split operands for this layer (every layer under FP16X3, selected ones under MIXED)
+    const bool res_lo = res && res->has_lo;
+    const bool any8 = in.lo8 || out.lo8 || (res && res->lo8);      // fp8 low parts: conv64_q8 / conv64_sq or nothing (the caller planned the chain with q8_capable)
+    if (any8 && !(x3 && use_q8() && q8_capable(L) && !direct)) return refuse();
+    if (e.fuse_tail1) r.done.tail1_parts = 2;      // (conv_mfma_kernel's two channel halves, unless conv1x1.hip takes the layer)
+    ConvForm& c = r.form;
+    c = form(L, H, W);
+    if (direct) return take(ConvKernel::direct);
+    const int px = (W + kTileW - 1) / kTileW;
+    c.res = res != nullptr; c.tail1 = e.fuse_tail1;
+    c.tail = e.fuse_tail; c.tail_form = e.fuse_tail ? tail_form : 0; c.tail_split = (e.fuse_tail && mixed && tail_split_for(key)) ? 1 : 0;
+    if (e.pool && !x3 && L.r == 1 && L.nchunks == 1 && !res && pooled_groups_ok((long long)c.py, (long long)B * c.py, n.max_groups)) {      // conv3x3_rw's pooled epilogue (SEDN rblock.2)
+        c.pool = true; c.pool_slabs = e.pool_slabs;
+        c.G = pooled_groups((long long)c.py, (long long)B * c.py, n.max_groups);      // its work items are patch ROWS (conv3x3_rw.hip, EPI 4): slab contents independent of the launch's plane count (common.h)
     }
-    // 3x3 / 64-input-channel layers with shared weights run on the software-pipelined kernel (conv3x3_sp.hip); everything else
-    // (1x1 convs, SEDN's per-plane `trans`, epilogues that kernel does not compile, MOE_CONV_IMPL=v1) on the generic one
-    const bool fast = L.taps == 9 && L.nseg == 1 && !L.per_plane && n.opt.conv_impl == 2;
-    if (e.tplanes && !(fast && !x3)) return ConvDone{false};
-    bool fused_ok = true;
-    // PReLU-only epilogues (first upsampler stage of Net4x, SEDN's rblock convs) run on the register-resident-weights kernel
-    // (conv3x3_rw.hip: 6 % faster there), and so does the fused tail in its phase-class-sums form (tail_form = sums); option
-    // sp_impl = sp keeps the PReLU epilogues on conv3x3_sp (A/B)
-    const int rw_mode = n.opt.sp_impl;
-    auto launch = [&](const ConvArgs& ca) {
-        if (ca.tplanes && ca.tail_form == 1) {       // phase-class sums: conv3x3_rw is the only producer of that buffer layout
-            if (!(fast && launch_conv3x3_rw(ca, s))) fused_ok = false;
-            return;
-        }
-        if (fast && n.opt.up_impl == 1 && !ca.tplanes && !ca.pool && ca.r == 2 && ca.nchunks == 4 && ca.in_cs == 64 && ca.acc_mode == 0 && !ca.res && !ca.out_lo && ca.scale == 1.f &&
-            !ca.dbg && L.has_bias && (long long)ca.B * ((ca.W + kTileW - 1) / kTileW) * (ca.H / 4) >= 32ll * n.max_groups) {
-            // The x2 upsampler stages that store their tensor: all four phases in one workgroup (conv3x3_ps4.hip, store form) -- when a workgroup gets at least
-            // 32 four-row blocks: a range recomputes two blocks at its ends, and a launch of three planes of 256 x 256 (the reference's own per-tile loop) would
-            // give each of the 256 workgroups six.  conv3x3_rw<1> below produces the same bits (same MFMAs in the same order), so the choice is invisible.
-            Ps4Args q{};
-            q.in = ca.in; q.wpk = ca.wpk; q.bias = ca.bias; q.out = ca.out; q.slope = ca.slope; q.B = ca.B; q.H = ca.H; q.W = ca.W;
-            if (launch_conv3x3_ps4(q, n.max_groups, s)) return;
-        }
-        if (fast && rw_mode && !ca.tplanes && launch_conv3x3_rw(ca, s)) { done.pooled = ca.pool != nullptr; return; }
-        if (fast && launch_conv3x3_sp(ca, s)) return;
-        if (ca.tplanes) { fused_ok = false; return; }
-        launch_conv_mfma(ca, L.taps, L.nseg, s);
-    };
+    const bool fast = fast_layer(n, L);
+    if (e.fuse_tail && !(fast && !x3)) return refuse();
     // lite's 1x1 convs (conv_input2, the upsampler stages with or without the folded 48->1 tail): the HBM-bound kernel of conv1x1.hip,
     // in fp16 or with split operands; MOE_CONV1X1=0 keeps them on the generic kernel (A/B)
-    const bool c1 = n.opt.conv1x1;
-    if (c1 && L.taps == 1 && L.nseg == 1 && !L.per_plane && !res && L.scale == 1.f && !e.tplanes && n.opt.conv_impl == 2 && (!x3 || (in.lo && L.has_x3))) {
-        Conv1x1Args q{};
-        q.in_hi = in.hi; q.in_lo = x3 ? in.lo : nullptr; q.out_hi = out.hi; q.out_lo = x3 ? out.lo : nullptr;
-        q.w_hi = blob<half_t>(L.w_hi); q.w_lo = x3 ? blob<half_t>(L.w_lo) : nullptr; q.bias = a.bias;
-        q.tail_w = e.tail1_w; q.tail_out = e.tail1_out; q.slope = L.slope;
-        q.B = B; q.H = H; q.W = W; q.r = L.r; q.nchunks = L.nchunks; q.out_cs = out_cs;
-        q.nks = (L.cin <= 48 && n.opt.k48) ? 3 : 4;
-        const int rec = prof_begin(key, (x3 ? 3 : 1) * 2.0 * (double)B * H * W * L.cout * L.cin);
-        const bool ok = launch_conv1x1(q, n.max_groups, s);
-        prof_end(rec);
-        if (ok) { if (e.tail1_out) tail1_parts = 1; return done; }
+    if (n.opt.conv1x1 && L.taps == 1 && L.nseg == 1 && !L.per_plane && !res && L.scale == 1.f && !e.fuse_tail && n.opt.conv_impl == 2 && (!x3 || (in.has_lo && L.has_x3)) &&
+        conv1x1_applicable(Conv1x1Form{B, H, W, L.r, L.nchunks, c.out_cs, L.slope, x3, e.fuse_tail1, x3 && out.has_lo}, n.max_groups)) {
+        if (e.fuse_tail1) r.done.tail1_parts = 1;
+        return take(ConvKernel::conv1x1);
     }
-    if (!x3 && (dbg & 64) && fast && key == n.opt.trace_key) {   // timing trace of one launch -> /tmp/moe_trace.bin
-        unsigned long long* tr = nullptr;
-        const size_t nb = 8 * 32 * 4 * 16 * 8;
-        if (hipMalloc((void**)&tr, nb) == hipSuccess) {
-            (void)hipMemsetAsync(tr, 0, nb, s);
-            ConvArgs t = a; t.acc32 = (float*)tr;
-            launch(t);
-            std::vector<unsigned long long> host(nb / 8);
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(host.data(), tr, nb, hipMemcpyDeviceToHost);
-            if (FILE* f = fopen("/tmp/moe_trace.bin", "wb")) { fwrite(host.data(), 1, nb, f); fclose(f); }
-            (void)hipFree(tr);
-            return done;
-        }
-    }
-    if (!x3 && res && res->lo && out.lo) {
+    const bool traced = !x3 && (c.dbg & 64) && fast && key == n.opt.trace_key;      // the timing trace of one launch (launch): of the layer's plain single-pass form
+    if (!x3 && !traced && res_lo && out.has_lo) {
         // MIXED, single-pass layer on the trunk stream: fp16 operands, but the residual is read as hi + lo * 2^-11, added in fp32
         // and the sum stored as hi and lo again (the split-precision final epilogue with the residual's low part as its addend):
         // the stream x + s*conv2(...) is carried to ~22 bits through the six ARSBs, only the MFMA operand is its fp16 part
-        ConvArgs q = a; q.acc_mode = 3; q.side16 = res->lo; q.out_lo = out.lo; q.res_lo = nullptr;
-        const int rec = prof_begin(key, 2.0 * (double)B * H * W * L.cout * L.cin * L.taps);
-        const bool ok = fast && launch_conv3x3_sp(q, s);
-        prof_end(rec);
-        { done.ok = ok; return done; }
+        c.acc_mode = 3; c.side16 = true; c.out_lo = true;
+        r.done.ok = fast && conv3x3_sp_applicable(c);
+        return take(ConvKernel::sp_res_lo);
     }
     if (!x3) {
-        const int rec = prof_begin(key, 2.0 * (double)B * H * W * L.cout * L.cin * L.taps);   // algorithmic (real channel counts)
-        launch(a);
-        prof_end(rec);
-        done.ok = fused_ok;
-        return done;
+        // the fused tail in its phase-class-sums form: conv3x3_rw is the only producer of that buffer layout
+        if (c.tail && c.tail_form == 1) { r.done.ok = conv3x3_rw_applicable(c); return take(ConvKernel::rw); }
+        // The x2 upsampler stages that store their tensor: all four phases in one workgroup (conv3x3_ps4.hip, store form) -- when a workgroup gets at least
+        // 32 four-row blocks: a range recomputes two blocks at its ends, and a launch of three planes of 256 x 256 (the reference's own per-tile loop) would
+        // give each of the 256 workgroups six.  conv3x3_rw<1> below produces the same bits (same MFMAs in the same order), so the choice is invisible.
+        if (fast && n.opt.up_impl == 1 && !c.tail && !c.pool && c.r == 2 && c.nchunks == 4 && c.in_cs == 64 && !c.res && c.scale == 1.f && !c.dbg && L.has_bias &&
+            (long long)B * px * (H / 4) >= 32ll * n.max_groups && ps4_store_applicable(B, H, W, L.slope))
+            return take(ConvKernel::ps4_store);
+        // PReLU-only epilogues (first upsampler stage of Net4x, SEDN's rblock convs) run on the register-resident-weights kernel
+        // (conv3x3_rw.hip: 6 % faster there); option sp_impl = sp keeps them on conv3x3_sp (A/B)
+        if (fast && n.opt.sp_impl && !c.tail && conv3x3_rw_applicable(c)) { r.done.pooled = c.pool; return take(ConvKernel::rw); }
+        if (fast && conv3x3_sp_applicable(c)) return take(ConvKernel::sp);
+        if (c.tail) return refuse();
+        return take(ConvKernel::mfma);
     }
-    if (L.has_x3 && !fast) {
-        // 1x1 conv: all three products in one launch (K segments (w_lo, a_hi), (w_hi, a_lo), (w_hi, a_hi)); the activations are
-        // read once per product from L2/HBM and nothing goes through the fp32 side buffer (2.6x less traffic than three passes)
-        ConvArgs f4 = a; f4.wpk = blob<half_t>(L.w_x3); f4.acc_mode = 4; f4.in_lo = in.lo; f4.out_lo = out.lo; f4.res_lo = res ? res->lo : nullptr;
-        launch_conv_mfma(f4, 1, 3, s);
-        return done;
-    }
-    {   // 3x3 64->64 with both weight parts packed for it: all three products in ONE launch (conv64_x3.hip)
-        if (n.opt.x3_fuse && fast && L.w_arsb_lo && in.lo && out.lo && (!res || res->lo) && !e.tplanes && !L.has_bias) {
-            ConvX3Args q{};
-            q.in_hi = in.hi; q.in_lo = in.lo; q.out_hi = out.hi; q.out_lo = out.lo;
-            q.res_hi = res ? res->hi : nullptr; q.res_lo = res ? res->lo : nullptr;
-            q.w_hi = blob<half_t>(L.w_arsb); q.w_lo = blob<half_t>(L.w_arsb_lo); q.zero = small<half_t>("zero");
-            q.slope = L.slope; q.B = B; q.H = H; q.W = W;
-            if (e.pool_out && !res && (L.slope == 1.f || e.pool_act) && pooled_groups_ok((long long)((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH),
-                                                                        (long long)B * ((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH), n.max_groups)) {
-                q.pool = e.pool_out; q.pool_slabs = e.pool_slabs;      // (conv64_x3's patches are 8 x 32 outputs, as the launcher counts them)
-            }
-            if (e.gate_in && res && !use_q8()) q.gate = e.gate_in;
-            const int rec = prof_begin(key, 3 * 2.0 * (double)B * H * W * L.cout * L.cin * L.taps);
-            bool ok = false;
-            // (use_q8: the two correction products on fp8 operands, conv64_q8.hip)
-            if (use_q8() && L.wq_hi8 && !q.pool && (!res || res->lo8 == in.lo8)) {
-                ConvX3Args q8 = q;
-                q8.wq_hi16 = blob<half_t>(L.w_hi); q8.wq_hi8 = blob<unsigned char>(L.wq_hi8); q8.wq_lo8 = blob<unsigned char>(L.wq_lo8);
-                q8.in8 = in.lo8; q8.out8 = out.lo8;
-                if (n.opt.q8_impl == 1) ok = launch_conv64_sq(q8, n.max_groups, s);
-                if (!ok) ok = launch_conv64_q8(q8, n.max_groups, s);
-            }
-            if (!ok && any8) { prof_end(rec); return ConvDone{false}; }
-            if (!ok) ok = launch_conv64_x3(q, n.max_groups, s);
-            prof_end(rec);
-            if (ok) { done.pooled = q.pool != nullptr; done.gated = q.gate != nullptr; return done; }
+    // 1x1 conv: all three products in one launch (K segments (w_lo, a_hi), (w_hi, a_lo), (w_hi, a_hi)); the activations are
+    // read once per product from L2/HBM and nothing goes through the fp32 side buffer (2.6x less traffic than three passes)
+    if (L.has_x3 && !fast) return take(ConvKernel::mfma_x3);
+    // 3x3 64->64 with both weight parts packed for it: all three products in ONE launch (conv64_x3.hip)
+    if (n.opt.x3_fuse && fast && L.w_arsb_lo && in.has_lo && out.has_lo && (!res || res_lo) && !e.fuse_tail && !L.has_bias) {
+        ConvX3Form q;
+        q.B = B; q.H = H; q.W = W; q.slope = L.slope; q.res = res != nullptr; q.res_lo = res_lo;
+        const long long P = (long long)px * c.py;      // (conv64_x3's patches are 8 x 32 outputs, as the launcher counts them)
+        if (e.pool && !res && (L.slope == 1.f || e.pool_act) && pooled_groups_ok(P, (long long)B * P, n.max_groups)) { q.pool = true; q.pool_slabs = e.pool_slabs; }
+        if (e.gate && res && !use_q8()) q.gate = true;
+        r.x3 = q;
+        // (use_q8: the two correction products on fp8 operands, conv64_q8.hip; its chain form streamed down a column, conv64_sq.hip)
+        if (use_q8() && L.wq_hi8 && !q.pool && (!res || res->lo8 == in.lo8)) {
+            r.x3.in8 = in.lo8; r.x3.out8 = out.lo8;
+            if (n.opt.q8_impl == 1 && conv64_sq_applicable(r.x3, n.max_groups)) return take(ConvKernel::sq);
+            if (conv64_q8_applicable(r.x3)) return take(ConvKernel::q8);
+            r.x3 = q;
         }
+        if (any8) return refuse();
+        if (conv64_x3_applicable(q, n.max_groups)) { r.done.pooled = q.pool; r.done.gated = q.gate; return take(ConvKernel::x3); }
     }
     if (fast && L.nchunks <= 16) {
         // 3x3 conv: the two low-order products run on the fast kernel as ordinary fp16-output convolutions --
@@ -181,25 +131,153 @@ ConvDone Fwd::conv(const std::string& key, const Act& in, const Act& out, const 
         // both in units of 2^-11; the main pass adds side * 2^-11 before its epilogue.  fp16 is plenty for a term that small,
         // and nothing goes through the fp32 side buffer (its read-modify-write traffic bounded the three-pass form).
         // (a residual's low part is in the same units: it rides along as the `residual` of the first low-order launch)
-        ConvArgs q1 = a; q1.wpk = blob<half_t>(L.w_lo); q1.out = side16; q1.res = (res && res->lo) ? res->lo : nullptr; q1.bias = small<float>("zero_bias");
-        q1.bias_img = small<float>("zero_bias_img"); q1.slope = 1.f; q1.scale = 1.f; q1.acc_mode = 0; q1.tail_w = nullptr; q1.tplanes = nullptr;
-        ConvArgs q2 = q1; q2.in = in.lo; q2.wpk = blob<half_t>(L.w_hi); q2.res = side16;
-        if (launch_conv3x3_sp(q1, s) && launch_conv3x3_sp(q2, s)) {
-            ConvArgs q3 = a; q3.acc_mode = 3; q3.side16 = side16; q3.out_lo = out.lo; q3.res_lo = nullptr;   // res_lo is inside side16
-            if (launch_conv3x3_sp(q3, s)) return done;
-            // (a final epilogue the fast kernel does not compile, e.g. a PReLU slope above 1: redo the layer through the fp32 side buffer)
-        }
+        ConvForm q1 = c; q1.res = res_lo; q1.slope = 1.f; q1.scale = 1.f; q1.tail = false;
+        ConvForm q2 = q1; q2.res = true;
+        ConvForm q3 = c; q3.acc_mode = 3; q3.side16 = true; q3.out_lo = out.has_lo;      // (res_lo is inside side16)
+        if (conv3x3_sp_applicable(q1) && conv3x3_sp_applicable(q2) && conv3x3_sp_applicable(q3)) return take(ConvKernel::sp_three);
+        // (a final epilogue the fast kernel does not compile, e.g. a PReLU slope above 1: the layer goes through the fp32 side buffer)
     }
     // hi/lo split: (w_lo * a_hi) -> acc32,  += (w_hi * a_lo),  then (w_hi * a_hi) + acc32/2048 and the epilogue
-    if (!acc32) return ConvDone{false};                               // (MIXED carries no fp32 side buffer)
-    a.acc32 = acc32;
-    ConvArgs p1 = a; p1.wpk = L.per_plane ? e.plane_w_lo : blob<half_t>(L.w_lo); p1.acc_mode = 1; p1.res = nullptr; p1.bias = nullptr;
-    launch(p1);
-    ConvArgs p2 = a; p2.in = in.lo; p2.acc_mode = 2; p2.res = nullptr; p2.bias = nullptr;
-    launch(p2);
-    ConvArgs p3 = a; p3.acc_mode = 3; p3.out_lo = out.lo; p3.res_lo = res ? res->lo : nullptr;
-    launch(p3);
-    return done;
+    if (!acc32_elems) return refuse();                               // (MIXED carries no fp32 side buffer unless a steep PReLU needs one: run_forward)
+    return take(ConvKernel::acc32);
+}
+
+// the arguments of exactly the kernel the route names; MOE_OK, or the internal error of a launcher that refused what its predicate promised
+int Fwd::launch(const ConvRoute& r, const std::string& key, const Act& in, const Act& out, const Act* res, const ConvExtra& e)
+{
+    const ConvLayer& L = n.convs[n.conv_index.at(key)];
+    const ConvForm& c = r.form;
+    const int H = c.H, W = c.W;
+    if (r.kernel == ConvKernel::direct) {
+        DirectConvArgs d{};
+        d.in = in.hi; d.out = out.hi; d.res = res ? res->hi : nullptr;
+        d.w = blob<float>(L.w_plain);
+        d.bias = L.has_bias ? blob<float>(L.bias_plain) : nullptr;
+        d.w_batch_stride = 0;
+        d.B = B; d.H = H; d.W = W; d.in_cs = c.in_cs; d.out_cs = c.out_cs; d.cin = L.cin; d.cout = L.cout; d.k = L.k; d.r = L.r;
+        d.slope = L.slope; d.scale = L.scale;
+        if (L.per_plane) { d.w = (const float*)e.plane_w; d.w_batch_stride = (long long)L.cout * L.cin; }
+        launch_conv_direct(d, s);
+        return MOE_OK;
+    }
+    ConvArgs a{};
+    a.in = in.hi; a.out = out.hi; a.res = res ? res->hi : nullptr;
+    a.wpk = L.per_plane ? e.plane_w : blob<half_t>(L.w_hi);
+    a.bias = L.has_bias ? blob<float>(L.bias) : small<float>("zero_bias");   // kernels initialise their accumulators from the bias vector
+    a.zero = small<half_t>("zero");
+    a.bias_img = blob<float>(L.bias_img);
+    a.trash = small<half_t>("trash");
+    a.w_batch_stride = L.per_plane ? (long long)L.nchunks * L.nfrag() * 512 : 0;
+    a.B = B; a.H = H; a.W = W; a.in_cs = c.in_cs; a.out_cs = c.out_cs; a.r = c.r; a.nchunks = c.nchunks;
+    a.px = (W + kTileW - 1) / kTileW; a.py = c.py; a.G = c.G;
+    a.slope = c.slope; a.scale = c.scale; a.dbg = c.dbg;
+    a.tail_w = e.tail_w; a.tplanes = e.tplanes; a.tail_form = c.tail_form; a.tail_split = c.tail_split;
+    a.tail1_w = e.tail1_w; a.tail1_out = e.tail1_out;
+    if (c.pool) { a.pool = e.pool_out; a.pool_slabs = c.pool_slabs; }
+    const bool x3 = this->x3 || e.exact;
+    // live timing of the one-launch forms; algorithmic flops (real channel counts), three products with split operands
+    const bool timed = r.kernel != ConvKernel::mfma_x3 && r.kernel != ConvKernel::sp_three && r.kernel != ConvKernel::acc32;
+    const int rec = timed ? prof_begin(key, (x3 ? 3 : 1) * 2.0 * (double)B * H * W * L.cout * L.cin * L.taps) : -1;
+    bool ok = true;
+    auto single = [&](const ConvArgs& ca) {      // the single-pass kernels
+        if (r.kernel == ConvKernel::rw) return launch_conv3x3_rw(ca, s);
+        if (r.kernel == ConvKernel::sp) return launch_conv3x3_sp(ca, s);
+        if (r.kernel == ConvKernel::ps4_store) {
+            Ps4Args q{};
+            q.in = ca.in; q.wpk = ca.wpk; q.bias = ca.bias; q.out = ca.out; q.slope = ca.slope; q.B = ca.B; q.H = ca.H; q.W = ca.W;
+            return launch_conv3x3_ps4(q, n.max_groups, s);
+        }
+        launch_conv_mfma(ca, L.taps, L.nseg, s);
+        return true;
+    };
+    switch (r.kernel) {
+    case ConvKernel::conv1x1: {
+        Conv1x1Args q{};
+        q.in_hi = in.hi; q.in_lo = x3 ? in.lo : nullptr; q.out_hi = out.hi; q.out_lo = x3 ? out.lo : nullptr;
+        q.w_hi = blob<half_t>(L.w_hi); q.w_lo = x3 ? blob<half_t>(L.w_lo) : nullptr; q.bias = a.bias;
+        q.tail_w = e.tail1_w; q.tail_out = e.tail1_out; q.slope = L.slope;
+        q.B = B; q.H = H; q.W = W; q.r = L.r; q.nchunks = L.nchunks; q.out_cs = c.out_cs;
+        q.nks = (L.cin <= 48 && n.opt.k48) ? 3 : 4;
+        ok = launch_conv1x1(q, n.max_groups, s);
+        break;
+    }
+    case ConvKernel::mfma: case ConvKernel::sp: case ConvKernel::rw: case ConvKernel::ps4_store: {
+        unsigned long long* tr = nullptr;
+        const size_t nb = 8 * 32 * 4 * 16 * 8;
+        if (!x3 && (c.dbg & 64) && fast_layer(n, L) && key == n.opt.trace_key && hipMalloc((void**)&tr, nb) == hipSuccess) {   // timing trace of one launch -> /tmp/moe_trace.bin
+            (void)hipMemsetAsync(tr, 0, nb, s);
+            ConvArgs t = a; t.acc32 = (float*)tr;
+            ok = single(t);
+            std::vector<unsigned long long> host(nb / 8);
+            (void)hipStreamSynchronize(s);
+            (void)hipMemcpy(host.data(), tr, nb, hipMemcpyDeviceToHost);
+            if (FILE* f = fopen("/tmp/moe_trace.bin", "wb")) { fwrite(host.data(), 1, nb, f); fclose(f); }
+            (void)hipFree(tr);
+        } else
+            ok = single(a);
+        break;
+    }
+    case ConvKernel::sp_res_lo: {
+        ConvArgs q = a; q.acc_mode = 3; q.side16 = res->lo; q.out_lo = out.lo; q.res_lo = nullptr;
+        ok = launch_conv3x3_sp(q, s);
+        break;
+    }
+    case ConvKernel::mfma_x3: {
+        ConvArgs f4 = a; f4.wpk = blob<half_t>(L.w_x3); f4.acc_mode = 4; f4.in_lo = in.lo; f4.out_lo = out.lo; f4.res_lo = res ? res->lo : nullptr;
+        launch_conv_mfma(f4, 1, 3, s);
+        break;
+    }
+    case ConvKernel::x3: case ConvKernel::q8: case ConvKernel::sq: {
+        ConvX3Args q{};
+        q.in_hi = in.hi; q.in_lo = in.lo; q.out_hi = out.hi; q.out_lo = out.lo;
+        q.res_hi = res ? res->hi : nullptr; q.res_lo = res ? res->lo : nullptr;
+        q.w_hi = blob<half_t>(L.w_arsb); q.w_lo = blob<half_t>(L.w_arsb_lo); q.zero = small<half_t>("zero");
+        q.slope = L.slope; q.B = B; q.H = H; q.W = W;
+        if (r.x3.pool) { q.pool = e.pool_out; q.pool_slabs = e.pool_slabs; }
+        if (r.x3.gate) q.gate = e.gate_in;
+        if (r.kernel == ConvKernel::x3) { ok = launch_conv64_x3(q, n.max_groups, s); break; }
+        q.wq_hi16 = blob<half_t>(L.w_hi); q.wq_hi8 = blob<unsigned char>(L.wq_hi8); q.wq_lo8 = blob<unsigned char>(L.wq_lo8);
+        q.in8 = r.x3.in8; q.out8 = r.x3.out8;
+        ok = r.kernel == ConvKernel::sq ? launch_conv64_sq(q, n.max_groups, s) : launch_conv64_q8(q, n.max_groups, s);
+        break;
+    }
+    case ConvKernel::sp_three: {      // (see route)
+        ConvArgs q1 = a; q1.wpk = blob<half_t>(L.w_lo); q1.out = side16; q1.res = (res && res->has_lo) ? res->lo : nullptr; q1.bias = small<float>("zero_bias");
+        q1.bias_img = small<float>("zero_bias_img"); q1.slope = 1.f; q1.scale = 1.f; q1.acc_mode = 0; q1.tail_w = nullptr; q1.tplanes = nullptr;
+        ConvArgs q2 = q1; q2.in = in.lo; q2.wpk = blob<half_t>(L.w_hi); q2.res = side16;
+        ConvArgs q3 = a; q3.acc_mode = 3; q3.side16 = side16; q3.out_lo = out.lo; q3.res_lo = nullptr;   // res_lo is inside side16
+        ok = launch_conv3x3_sp(q1, s) && launch_conv3x3_sp(q2, s) && launch_conv3x3_sp(q3, s);
+        break;
+    }
+    case ConvKernel::acc32: {
+        a.acc32 = acc32;
+        ConvArgs p1 = a; p1.wpk = L.per_plane ? e.plane_w_lo : blob<half_t>(L.w_lo); p1.acc_mode = 1; p1.res = nullptr; p1.bias = nullptr;
+        launch_conv_mfma(p1, L.taps, L.nseg, s);
+        ConvArgs p2 = a; p2.in = in.lo; p2.acc_mode = 2; p2.res = nullptr; p2.bias = nullptr;
+        launch_conv_mfma(p2, L.taps, L.nseg, s);
+        ConvArgs p3 = a; p3.acc_mode = 3; p3.out_lo = out.lo; p3.res_lo = res ? res->lo : nullptr;
+        launch_conv_mfma(p3, L.taps, L.nseg, s);
+        break;
+    }
+    default: ok = false;
+    }
+    prof_end(rec);
+    if (!ok) return fail(MOE_EINVAL, "internal error: layer %s (%d planes of %dx%d) was routed to %s, and that launcher refused it", key.c_str(), B, H, W, kernel_name(r.kernel));
+    return MOE_OK;
+}
+
+// one convolution layer: in [B][H][W][64*nseg] -> out [B][H*r][W*r][r>1 ? 64 : 64*nchunks]
+// !ok only when asked for the fused tail / an fp8 chain / a side buffer the forward does not carry and no kernel can take the layer that way: nothing is launched then
+ConvDone Fwd::conv(const std::string& key, const Act& in, const Act& out, const Act* res, int H, int W, const ConvExtra& e)
+{
+    const ConvRoute r = route(key, in, out, res, H, W, e);
+    if (r.done.ok && !dry()) {
+        rc = launch(r, key, in, out, res, e);
+        // a refused launch ends the launching: the arena loses its base, so the rest of the sequence only counts (dry()) -- no kernel is enqueued over the tensor that
+        // was not written -- and run_forward returns rc.  (Inside forward_arsb's fork the side stream is joined by ForkGuard's destructor, as on every early exit.)
+        if (rc) ar.base = nullptr;
+    }
+    return r.done;
 }
 
 void Fwd::stem(const Act& out, const Act* out2)
@@ -224,7 +302,7 @@ void Fwd::tail(const Act* r, const Act* u, int H, int W, bool skip)
     TailArgs a{};
     a.in0 = r->hi; a.w0 = small<half_t>("tail_r");
     if (u) { a.in1 = u->hi; a.w1 = small<half_t>("tail_u"); }
-    if (r->lo && (!u || u->lo)) {     // split operands (FP16X3; MIXED on NetDN, whose tail convs read the hi + lo stream directly)
+    if (r->has_lo && (!u || u->has_lo)) {     // split operands (FP16X3; MIXED on NetDN, whose tail convs read the hi + lo stream directly)
         a.in0_lo = r->lo; a.w0_lo = small<half_t>("tail_r.lo");
         if (u) { a.in1_lo = u->lo; a.w1_lo = small<half_t>("tail_u.lo"); a.in1_lo8 = u->lo8; }
     }
@@ -312,11 +390,13 @@ static int run_forward(moe_net& n, Fwd& f, const FwdIO& io)
         for (int i = 1; i <= exact_blocks_of(n); ++i) steep = steep || n.convs[n.conv_index.at("c1_" + std::to_string(i))].slope > 1.f;
         if (steep) { f.acc32_elems = (size_t)P * 64; f.acc32 = (float*)f.ar.take(f.acc32_elems * 4); }
     }
+    int rc = MOE_OK;
     switch (n.arch) {
-        case MOE_ARCH_SEDN: return forward_sedn(n, f);
-        case MOE_ARCH_LITE: return forward_lite(n, f);
-        default: return forward_arsb(n, f);      // Net2x / Net3x / Net4x, NetDN
+        case MOE_ARCH_SEDN: rc = forward_sedn(n, f); break;
+        case MOE_ARCH_LITE: rc = forward_lite(n, f); break;
+        default: rc = forward_arsb(n, f);      // Net2x / Net3x / Net4x, NetDN
     }
+    return rc ? rc : f.rc;      // (f.rc: a launcher refused the layer its route promised -- Fwd::launch)
 }
 
 static size_t workspace_need(moe_net& n, int B, int h, int w)
@@ -325,6 +405,13 @@ static size_t workspace_need(moe_net& n, int B, int h, int w)
     f.mixed = n.precision == MOE_PREC_MIXED;
     run_forward(n, f, FwdIO{});
     return f.ar.off + 4096;
+}
+
+// THE CHECK behind the launching pass: it took exactly what the planning pass counted -- or less, where it legitimately left out work the plan had to assume
+static bool plan_matches(const Fwd& f, size_t planned)
+{
+    if (f.ar.overflow) return false;
+    return f.skips_planned_work ? f.ar.off <= planned : f.ar.off == planned;
 }
 
 static int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
@@ -405,12 +492,16 @@ static int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int 
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(MOE_ENOMEM, "workspace of %zu bytes for %d planes of %dx%d does not fit", need, B, h, w); }
         n.ws_bytes = need;
     }
-    Fwd f{n, s, B, h, w, Arena{n.ws, 0}, n.precision == MOE_PREC_FP16X3, n.precision == MOE_PREC_DEBUG_DIRECT};
+    const size_t planned = need - 4096;
+    Fwd f{n, s, B, h, w, Arena{n.ws, 0, planned}, n.precision == MOE_PREC_FP16X3, n.precision == MOE_PREC_DEBUG_DIRECT};
     f.mixed = n.precision == MOE_PREC_MIXED;
     f.y_vec = y_off_mult8 && ((uintptr_t)y % 16 == 0);   // every output plane starts 16-byte aligned: wide stores allowed
     if (n.lut_state == 2 && x == (const void*)n.lut_in) f.lut_capture = n.lut;      // (build_lite_lut's own forward)
     int rc = run_forward(n, f, FwdIO{x, x_dtype, sB, sH, sW, x_off_dev, y, y_dtype, y_off_dev});
     if (rc) return rc;
+    if (!plan_matches(f, planned))
+        return fail(MOE_EINVAL, "internal error: the launching pass took %zu bytes of workspace%s, the planning pass %zu (%d planes of %dx%d)", f.ar.off,
+                    f.ar.overflow ? " (beyond the plan: the launches behind that point were not issued)" : "", planned, B, h, w);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MOE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     return MOE_OK;

@@ -14,17 +14,20 @@ const ConvLayer* last_up(const moe_net& n, int br)
     return it == n.conv_index.end() ? nullptr : &n.convs[it->second];
 }
 
-bool can_fuse_tail(const moe_net& n, const Fwd& f, int B, int h, int w)
+bool can_fuse_tail(const moe_net& n, const Fwd& f)
 {
+    const int B = f.B, h = f.h, w = f.w;
     if (!n.opt.fuse_tail || f.x3 || f.direct || n.debug || n.opt.conv_impl != 2 || n.stages < 1) return false;
     if (!(n.arch == MOE_ARCH_NET2X || n.arch == MOE_ARCH_NET3X || n.arch == MOE_ARCH_NET4X)) return false;
-    long long sc = 1;
-    for (int s = 0; s < n.stages; ++s) sc *= n.r;
-    if ((w * (sc / n.r)) % 4 != 0) return false;            // the fused kernel stores tap planes four input columns at a time
     if (sp_bytes_per_pixel(n) * B * h * w > kSpRange) return false;    // (forward_dev keeps every launch set inside this range)
-    for (int br = 0; br < 2; ++br) {
+    int hl = h, wl = w;
+    for (int st = 0; st + 1 < n.stages; ++st) { hl *= n.r; wl *= n.r; }
+    for (int br = 0; br < 2; ++br) {      // the nine-tap-planes form of conv3x3_sp takes both branches' last up-conv (the other forms are chosen among by plan_tail_form)
         const ConvLayer* L = last_up(n, br);
-        if (!L || L->slope > 1.f) return false;
+        if (!L) return false;
+        ConvForm c = f.form(*L, hl, wl);
+        c.tail = true;
+        if (!conv3x3_sp_applicable(c)) return false;
     }
     return true;
 }
@@ -61,17 +64,20 @@ struct ArsbRun {
 void ArsbRun::plan_tail_form()
 {
     sr = n.arch != MOE_ARCH_NETDN;
-    fuse = sr && can_fuse_tail(n, f, B, h, w);      // last upsampler conv + 64->1 tail conv in one kernel
+    fuse = sr && can_fuse_tail(n, f);      // last upsampler conv + 64->1 tail conv in one kernel
     if (sr) {   // form of the fused tail's output: phase-class sums when the last stage is a x2 shuffle the register-weight kernel takes
         int hl = h, wl = w;
         for (int st = 0; st + 1 < n.stages; ++st) { hl *= n.r; wl *= n.r; }
-        bool ok = fuse && n.opt.tail_form == 1 && n.r == 2 && wl % 4 == 0 && tailsum_fits(B, hl, wl) &&
-                  2ll * B * hl * wl * 64 + 2ll * (wl + 1) * 64 < (1ll << 32) - 65536;
+        bool ok = fuse && n.opt.tail_form == 1;
         bool ps4_ok = true;
         bool ps9_ok = true;
         for (int br = 0; br < 2; ++br) {
             const ConvLayer* L = last_up(n, br);
-            ok = ok && L && L->slope < 1.f;
+            if (ok) {      // (fuse: both layers exist) conv3x3_rw's own predicate for its phase-class-sums epilogue
+                ConvForm c = f.form(*L, hl, wl);
+                c.tail = true; c.tail_form = 1;
+                ok = conv3x3_rw_applicable(c);
+            }
             ps4_ok = ps4_ok && L && ps4_tail_applicable(B, hl, wl, L->slope);      // (the launcher's own predicate: common.h)
             ps9_ok = ps9_ok && L && ps9_tail_applicable(B, hl, wl, L->slope);
         }
@@ -108,7 +114,7 @@ int ArsbRun::ps_stage(int br, const std::string& key, const Act& cur, size_t pla
 
 int ArsbRun::run_branch(int br, Act cur)      // launches go to f.s (the caller's stream, or the side stream while the U branch is forked)
 {
-    if (f.mixed) { cur.lo = nullptr; cur.lo8 = false; }      // MIXED: the upsampler convs take the fp16 parts (FP16X3 keeps its pairs)
+    if (f.mixed) { cur.drop_lo(); cur.lo8 = false; }      // MIXED: the upsampler convs take the fp16 parts (FP16X3 keeps its pairs)
     H = h; W = w;
     for (int st = 0; st < n.stages; ++st) {
         const std::string key = std::string(br == 0 ? "convt_R1" : "u") + ".up" + std::to_string(st);
@@ -122,9 +128,8 @@ int ArsbRun::run_branch(int br, Act cur)      // launches go to f.s (the caller'
         }
         if (fuse && st == n.stages - 1) {
             tp[br] = (float*)f.ar.take(f.tail_form == 1 ? (size_t)tailsum_layout(B, H, W).total * 4 + 4096 : (size_t)9 * B * H * n.r * W * n.r * 4 + 4096);
-            const half_t* frag = f.dry() ? nullptr : f.small<half_t>(br == 0 ? "tail_r.frag" : "tail_u.frag");
             ConvExtra tail;
-            tail.tail_w = frag; tail.tplanes = f.dry() ? (float*)16 : tp[br];
+            tail.fuse_tail = true; tail.tail_w = f.small<half_t>(br == 0 ? "tail_r.frag" : "tail_u.frag"); tail.tplanes = tp[br];
             if (!f.conv(key, cur, Act{}, nullptr, H, W, tail))
                 return fail(MOE_EINVAL, "fused tail kernel rejected layer %s", key.c_str());
             H *= n.r; W *= n.r;
@@ -162,27 +167,23 @@ int ArsbRun::run_trunk()
     for (int i = 1; i <= 6; ++i) {
         const bool ex = mixed && i <= nx;
         const std::string k1 = "c1_" + std::to_string(i), k2 = "c2_" + std::to_string(i);
-        if (arsb_fuse && !ex && (!mixed || (cur.lo && oth.lo)) && n.convs[n.conv_index.at(k1)].w_arsb) {
-            bool done = f.dry();
-            if (!done) {
-                const ConvLayer& L1 = n.convs[n.conv_index.at(k1)];
-                const ConvLayer& L2 = n.convs[n.conv_index.at(k2)];
+        const ConvLayer& L1 = n.convs[n.conv_index.at(k1)];
+        const ConvLayer& L2 = n.convs[n.conv_index.at(k2)];
+        const bool trunk64 = L1.w_arsb != 0;      // a bias-free 64 -> 64 trunk conv (weights.cpp packs w_arsb for exactly those)
+        const int cin = (L1.cin == 48 && L2.cin == 48 && n.opt.k48) ? 48 : 64;      // NetDN: channels 48..63 are zeros in activations and weights
+        if (arsb_fuse && !ex && (!mixed || (cur.has_lo && oth.has_lo)) && trunk64 && arsb32c_applicable(B, h, w, L1.slope, mixed, mixed, cin)) {
+            if (!f.dry()) {
                 ArsbArgs q{};
                 q.x_hi = cur.hi; q.x_lo = mixed ? cur.lo : nullptr; q.y_hi = oth.hi; q.y_lo = mixed ? oth.lo : nullptr;
-                q.w1 = f.blob<half_t>(L1.w_arsb); q.w2 = f.blob<half_t>(L2.w_arsb); q.zero = f.small<half_t>("zero");
-                q.slope = L1.slope; q.B = B; q.H = h; q.W = w;
+                q.w1 = f.blob<half_t>(L1.w_hi); q.w2 = f.blob<half_t>(L2.w_hi); q.zero = f.small<half_t>("zero");      // (pack_conv order; conv_2's carry the ScaleLayer factor as well)
+                q.slope = L1.slope; q.B = B; q.H = h; q.W = w; q.cin = cin;
+                q.drop_lo = (mixed && i == 6 && n.arch != MOE_ARCH_NETDN && !n.debug) ? 1 : 0;      // the upsamplers take the fp16 part: nobody reads block 6's low part
                 const bool trace = n.opt.arsb_trace;   // MOE_ARSB_TRACE with a -DARSB_TRACE build: stamps of ARSB 3 -> /tmp/arsb_trace.bin
                 const size_t tb = 8 * 16 * 4 * 40 * 8;
                 if (trace && i == 3 && hipMalloc((void**)&q.trace, tb) == hipSuccess) (void)hipMemsetAsync(q.trace, 0, tb, s);
                 const int rec = f.prof_begin("arsb" + std::to_string(i), 2.0 * 2.0 * (double)B * h * w * L1.cout * L1.cin * 9);
-                {
-                    ArsbArgs q2 = q;
-                    q2.w1 = f.blob<half_t>(L1.w_hi); q2.w2 = f.blob<half_t>(L2.w_hi);      // (pack_conv order; conv_2's carry the ScaleLayer factor as well)
-                    q2.cin = (L1.cin == 48 && L2.cin == 48 && n.opt.k48) ? 48 : 64;      // NetDN: channels 48..63 are zeros in activations and weights
-                    q2.drop_lo = (mixed && i == 6 && n.arch != MOE_ARCH_NETDN && !n.debug) ? 1 : 0;      // the upsamplers take the fp16 part: nobody reads block 6's low part
-                    for (int rep = f.repeats("arsb" + std::to_string(i)); rep > 0; --rep)
-                        done = launch_arsb32c(q2, n.max_groups, s);      // (false: the shape does not fit its 32-bit offsets -- the two-launch form below)
-                }
+                bool done = false;
+                for (int rep = f.repeats("arsb" + std::to_string(i)); rep > 0; --rep) done = launch_arsb32c(q, n.max_groups, s);
                 f.prof_end(rec);
                 if (q.trace) {
                     std::vector<unsigned long long> host(tb / 8);
@@ -191,43 +192,40 @@ int ArsbRun::run_trunk()
                     if (FILE* fp = fopen("/tmp/arsb_trace.bin", "wb")) { fwrite(host.data(), 1, tb, fp); fclose(fp); }
                     (void)hipFree(q.trace);
                 }
+                if (!done) return fail(MOE_EINVAL, "internal error: arsb32c rejected layer %s its predicate took", k1.c_str());
             }
-            if (done) { std::swap(cur, oth); cur.lo8 = oth.lo8 = false; f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C); continue; }      // (fp16 low parts out; the scratch side's form is its next writer's)
+            std::swap(cur, oth); cur.lo8 = oth.lo8 = false; f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C);      // (fp16 low parts out; the scratch side's form is its next writer's)
+            continue;
         }
-        if (ex && chain8 && n.opt.exact_fuse && n.opt.q8_impl == 1 && cur.lo8 && cur.lo && oth.lo) {
+        if (ex && chain8 && n.opt.exact_fuse && n.opt.q8_impl == 1 && cur.lo8 && cur.has_lo && oth.has_lo && L1.wq_hi8 && L2.wq_hi8 && !L1.has_bias && !L2.has_bias && L2.slope == 1.f &&
+            arsb_sq_applicable(B, h, w, L1.slope)) {
             // an exact block of the chain in ONE launch (arsb_sq.hip): x = cur (fp16 + fp8 low words) -> oth; the last exact block writes fp16 low parts (the
             // single-pass ARSB kernels behind it read those)
-            bool done = f.dry();
-            if (!done) {
-                const ConvLayer& L1 = n.convs[n.conv_index.at(k1)];
-                const ConvLayer& L2 = n.convs[n.conv_index.at(k2)];
-                if (L1.wq_hi8 && L2.wq_hi8 && !L1.has_bias && !L2.has_bias && L2.slope == 1.f) {
-                    ArsbSqArgs q{};
-                    q.x_hi = cur.hi; q.x_lo8 = (const unsigned char*)cur.lo; q.y_hi = oth.hi; q.y_lo = oth.lo;
-                    q.w16[0] = f.blob<half_t>(L1.w_hi); q.wh8[0] = f.blob<unsigned char>(L1.wq_hi8); q.wl8[0] = f.blob<unsigned char>(L1.wq_lo8);
-                    q.w16[1] = f.blob<half_t>(L2.w_hi); q.wh8[1] = f.blob<unsigned char>(L2.wq_hi8); q.wl8[1] = f.blob<unsigned char>(L2.wq_lo8);
-                    q.slope = L1.slope; q.B = B; q.H = h; q.W = w; q.out8 = i < nx;
-                    const int rec = f.prof_begin("xpair" + std::to_string(i), 2.0 * 2.0 * 3.0 * (double)B * h * w * L1.cout * L1.cin * 9);
-                    done = launch_arsb_sq(q, n.max_groups, s);
-                    f.prof_end(rec);
-                }
+            if (!f.dry()) {
+                ArsbSqArgs q{};
+                q.x_hi = cur.hi; q.x_lo8 = (const unsigned char*)cur.lo; q.y_hi = oth.hi; q.y_lo = oth.lo;
+                q.w16[0] = f.blob<half_t>(L1.w_hi); q.wh8[0] = f.blob<unsigned char>(L1.wq_hi8); q.wl8[0] = f.blob<unsigned char>(L1.wq_lo8);
+                q.w16[1] = f.blob<half_t>(L2.w_hi); q.wh8[1] = f.blob<unsigned char>(L2.wq_hi8); q.wl8[1] = f.blob<unsigned char>(L2.wq_lo8);
+                q.slope = L1.slope; q.B = B; q.H = h; q.W = w; q.out8 = i < nx;
+                const int rec = f.prof_begin("xpair" + std::to_string(i), 2.0 * 2.0 * 3.0 * (double)B * h * w * L1.cout * L1.cin * 9);
+                const bool done = launch_arsb_sq(q, n.max_groups, s);
+                f.prof_end(rec);
+                if (!done) return fail(MOE_EINVAL, "internal error: arsb_sq rejected layer %s its predicate took", k1.c_str());
             }
-            if (done) {
-                std::swap(cur, oth);
-                cur.lo8 = i < nx;
-                oth.lo8 = false;             // (scratch now: whoever writes it next decides its form)
-                f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C);
-                continue;
-            }
+            std::swap(cur, oth);
+            cur.lo8 = i < nx;
+            oth.lo8 = false;             // (scratch now: whoever writes it next decides its form)
+            f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C);
+            continue;
         }
         Act m = oth;
-        if (mixed && !ex) m.lo = nullptr;                    // single-pass ARSB: conv_1's output is an fp16 operand only
+        if (mixed && !ex) m.drop_lo();                       // single-pass ARSB: conv_1's output is an fp16 operand only
         m.lo8 = ex && chain8;
         Act bin = cur;
-        if (mixed && !ex) bin.lo = nullptr;
+        if (mixed && !ex) bin.drop_lo();
         if (int rc = trunk_conv(k1, bin, m, nullptr, ex)) return rc;
         const Act resid = cur;
-        if (ex && chain8 && i == nx) { cur.lo = lo16x ? lo16x : A.lo; cur.lo8 = false; }      // (see chain8)
+        if (ex && chain8 && i == nx) { cur.lo = lo16x ? lo16x : A.lo; cur.lo8 = false; }      // (see chain8: a low part either way)
         if (int rc = trunk_conv(k2, m, cur, &resid, ex)) return rc;
         f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C);
     }
@@ -286,12 +284,11 @@ int ArsbRun::run()
     // The last conv_2 writes an fp16 low part again -- into the stem's low-part buffer, which conv_input2 was the only reader of (its own buffer still
     // holds the fp8 residual it reads) -- for the fused ARSB kernels behind it.  The stem writes its low part in that form too (conv_input2 is its only
     // reader: the U branch takes the fp16 part).  Debug taps read fp16 low parts: no chain under set_debug.
-    f.Hq = h; f.Wq = w;
     // NetDN (round 6): its tail convs read the stem's hi + lo pair at the very end -- tail3 takes the stem's low part as the same fp8 words (TailArgs::in1_lo8), so the
     // stem writes ONE low-part form here too.  What NetDN cannot share is the buffer: the two-launch fallback of the last exact block writes its fp16 low part into a
     // buffer of its own (lo16x) instead of over the stem's words.
     const bool dn = n.arch == MOE_ARCH_NETDN;
-    chain8 = mixed && f.use_q8() && n.opt.lo8 && !n.debug && !f.direct && nx >= 1 && (f.dry() || (A.lo && Bb.lo && Cc.lo));      // (the planning pass has no pointers: lo16x below must be planned too)
+    chain8 = mixed && f.use_q8() && n.opt.lo8 && !n.debug && !f.direct && nx >= 1 && A.has_lo && Bb.has_lo && Cc.has_lo;      // (flags: lo16x below is planned like everything else)
     if (dn && (int)n.scalars.at("tail_taps") != 9) chain8 = false;      // (the 1x1 tail kernel reads fp16 pairs only)
     for (int i = 0; chain8 && i <= nx; ++i)
         for (int j = (i == 0 ? 2 : 1); chain8 && j <= 2; ++j)
@@ -350,7 +347,7 @@ int ArsbRun::run()
     }
     if (int rc = run_trunk()) return rc;
     if (n.arch == MOE_ARCH_NETDN) { f.tail(&Bb, &A, h, w, false); return MOE_OK; }
-    if (mixed) { A.lo = nullptr; Bb.lo = nullptr; A.lo8 = Bb.lo8 = false; }      // the upsampler convs take the fp16 parts
+    if (mixed) { A.drop_lo(); Bb.drop_lo(); A.lo8 = Bb.lo8 = false; }      // the upsampler convs take the fp16 parts
     if (!forked) { if (int rc = run_branch(0, Bb)) return rc; if (int rc = run_branch(1, A)) return rc; }
     else {
         if (int rc = run_branch(0, Bb)) return rc;

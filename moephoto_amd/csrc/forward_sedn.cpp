@@ -17,9 +17,13 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
     half_t* wplane_lo = f.x3 ? (half_t*)f.ar.take((size_t)B * wel * 2) : nullptr;
     f.stem(A);
     f.tap("stem", A, h, w, 64, 64);
-    // fused block tail (see sedn_fuse in misc_kernels.hip): single-pass precision, fast kernel, planes fit the per-XCD split
-    const bool sfuse = n.opt.sedn_fuse && !f.x3 && !f.direct && !n.debug && n.opt.conv_impl == 2 && B <= n.max_groups &&
-                       2ll * B * h * w * 64 < (1ll << 32) - 8192;
+    // fused block tail (see sedn_fuse in misc_kernels.hip): single-pass precision, fast kernel, planes fit the per-XCD split -- one 3x3 64->64 conv with per-plane
+    // weights, LeakyReLU and the residual: on conv64_s.hip, or on conv3x3_sp<6>
+    ConvForm tf;
+    tf.B = B; tf.H = h; tf.W = w; tf.nchunks = B; tf.py = (h + kTileH - 1) / kTileH; tf.slope = 0.2f; tf.res = true; tf.plane_w = true;
+    tf.G = (int)std::max<long long>(B, std::min<long long>(n.max_groups, (long long)B * ((w + kTileW - 1) / kTileW) * tf.py));   // total workgroups (plane b gets every B-th)
+    const bool s64 = n.opt.s64 && conv64_s_applicable(tf);
+    const bool sfuse = n.opt.sedn_fuse && !f.x3 && !f.direct && !n.debug && n.opt.conv_impl == 2 && B <= n.max_groups && (s64 || conv3x3_sp_applicable(tf));
     float* xpart = (float*)f.ar.take((size_t)B * nslab * 5 * 64 * 4);
     // the channel totals of rblock.2's output come out of that conv's epilogue (conv3x3_rw EPI 4), sedn_xsum then only visits the border
     const int pslabs = 2 * n.max_groups;
@@ -31,7 +35,7 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
         const std::string k = "b" + std::to_string(b);
         f.conv(k + ".rb0", A, Cc, nullptr, h, w);
         ConvExtra rb2;
-        if (sfuse && spool) { rb2.pool_out = xpool; rb2.pool_slabs = pslabs; }      // (the conv writes the first 2 min(G, py) slabs of every plane, all of them: no memset)
+        if (sfuse && spool) { rb2.pool = true; rb2.pool_out = xpool; rb2.pool_slabs = pslabs; }      // (the conv writes the first 2 min(G, py) slabs of every plane, all of them: no memset)
         const bool pooled = f.conv(k + ".rb2", Cc, Dd, nullptr, h, w, rb2).pooled;
         if (sfuse) {
             if (!f.dry()) {
@@ -50,11 +54,10 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
                 a.in = Dd.hi; a.out = A.hi; a.res = A.hi; a.wpk = weff; a.plane_w = 1;
                 a.bias = f.small<float>("zero_bias"); a.bias_img = f.small<float>("zero_bias_img");
                 a.zero = f.small<half_t>("zero"); a.trash = f.small<half_t>("trash");
-                a.B = B; a.H = h; a.W = w; a.in_cs = 64; a.out_cs = 64; a.r = 1; a.nchunks = B;
-                a.px = (w + kTileW - 1) / kTileW; a.py = (h + kTileH - 1) / kTileH;
-                a.G = (int)std::max<long long>(B, std::min<long long>(n.max_groups, (long long)B * a.px * a.py));   // total workgroups (plane b gets every B-th)
-                a.slope = 0.2f; a.scale = 1.f;
-                if (!(n.opt.s64 && launch_conv64_s(a, n.max_groups, s)) && !launch_conv3x3_sp(a, s)) return fail(MOE_EINVAL, "SEDN fused block tail: kernel rejected the layer");
+                a.B = B; a.H = h; a.W = w; a.in_cs = tf.in_cs; a.out_cs = tf.out_cs; a.r = tf.r; a.nchunks = tf.nchunks;
+                a.px = (w + kTileW - 1) / kTileW; a.py = tf.py; a.G = tf.G;
+                a.slope = tf.slope; a.scale = tf.scale;
+                if (!(s64 ? launch_conv64_s(a, n.max_groups, s) : launch_conv3x3_sp(a, s))) return fail(MOE_EINVAL, "internal error: SEDN fused block tail: %s rejected the layer", s64 ? "conv64_s" : "conv3x3_sp");
             }
             continue;
         }

@@ -54,15 +54,24 @@ struct ConvLayer {               // one MFMA convolution
 
 // an activation tensor: fp16 [B][H][W][C] and (split operands / the trunk stream of 'mixed') its low part, (v - fp16(v)) 2^11, as fp16 in the same layout --
 // or, lo8, as the fp8 e4m3 word of that value / 4 (one byte a channel): the form conv64_q8.hip reads and writes between its own layers
-struct Act { half_t* hi = nullptr; half_t* lo = nullptr; bool lo8 = false; };
+// has_lo says whether the tensor HAS a low part: the flag is what decides a route or a buffer -- it is the same on the planning pass, where every pointer is null
+struct Act {
+    half_t* hi = nullptr; half_t* lo = nullptr; bool lo8 = false; bool has_lo = false;
+    void drop_lo() { lo = nullptr; has_lo = false; }      // the reader takes the fp16 part only
+};
 
 struct Arena {                   // bump allocator over the net's workspace (dry run when base == nullptr)
     char* base = nullptr;
     size_t off = 0;
+    size_t limit = 0;            // bytes behind base (what the planning pass sized)
+    bool overflow = false;
     void* take(size_t bytes)
     {
         const size_t a = (off + 255) & ~(size_t)255;
         off = a + bytes;
+        // a buffer the plan did not size: the rest of the sequence only counts (dry), so that no kernel is launched over it; forward_dev_chunk reports it
+        // (inside forward_arsb's fork the side stream is joined by ForkGuard's destructor, as on every early exit)
+        if (base && off > limit) { overflow = true; base = nullptr; }
         return base ? base + a : nullptr;
     }
 };
@@ -228,14 +237,33 @@ struct ConvExtra {
     int pool_slabs = 0;
     bool pool_act = false;       // ... with pool_out: the conv may pool BEHIND its PReLU (conv64_x3 EPI 4: lite's conv_1, whose output's sums make the FRM gate -- frm_pre)
     const float* gate_in = nullptr;   // with a residual: out = gate[plane][channel] * conv + residual (conv64_x3 EPI 5), [2][B][64]
+    // WHAT is asked, as flags: these decide the route (the pointers above are null on the planning pass; they are arguments, never conditions)
+    bool fuse_tail = false, fuse_tail1 = false, pool = false, gate = false;
 };
-// ... and what the kernel that took the layer did
+// ... and what the kernel that takes the layer does with it (the same answer on both passes: it is the route's)
 struct ConvDone {
-    bool ok = true;              // false only when asked for the fused tail (tplanes != nullptr) / an fp8 chain and the fused kernel cannot take the layer
-    bool pooled = false;         // the conv pooled into pool_out
-    bool gated = false;          // the conv applied gate_in
+    bool ok = true;              // false only when asked for the fused tail / an fp8 chain / split operands without a side buffer and no kernel can take the layer
+    bool pooled = false;         // the conv pools into pool_out
+    bool gated = false;          // the conv applies gate_in
+    int tail1_parts = 0;         // fuse_tail1: partial planes per branch the fused 1x1 tail writes (conv_mfma_kernel: 2, conv1x1.hip: 1)
     explicit operator bool() const { return ok; }
 };
+// the kernel a layer resolves to: computed by Fwd::route from the layer, the net's options, the shape and the operands' forms; Fwd::launch fills the arguments of exactly that one
+enum class ConvKernel {
+    none, direct, conv1x1,
+    mfma, sp, rw, ps4_store,     // single-pass layers: the generic kernel, conv3x3_sp, conv3x3_rw, conv3x3_ps4's store form
+    sp_res_lo,                   // MIXED, single pass on the trunk stream: conv3x3_sp with the residual's low part as the addend of its split final epilogue
+    mfma_x3,                     // split operands, 1x1: three products in one launch of the generic kernel (acc_mode 4)
+    x3, q8, sq,                  // split operands, 3x3 64->64 in one launch: conv64_x3, conv64_q8, conv64_sq
+    sp_three, acc32,             // split operands, the fallbacks: three launches of conv3x3_sp through side16; three of the generic kernel through the fp32 side buffer
+};
+struct ConvRoute {
+    ConvKernel kernel = ConvKernel::none;
+    ConvDone done;
+    ConvForm form;               // the ConvArgs kernels' launch: shape, grid, epilogue flags
+    ConvX3Form x3;               // the ConvX3Args kernels'
+};
+const char* kernel_name(ConvKernel k);
 
 struct Fwd {
     moe_net& n;
@@ -249,8 +277,9 @@ struct Fwd {
     size_t acc32_elems = 0;
     half_t* side16 = nullptr;    // fp16 sum of the two low-order products of a 3x3 conv (split precision), output layout
     bool dry() const { return ar.base == nullptr; }
+    int rc = 0;                  // the internal error of a launch (Fwd::launch): the forward turns dry behind it (Fwd::conv), run_forward returns it
     float* lut_capture = nullptr;     // lite: this forward fills the U-branch table -- its input is the image of all fp16 patterns; part[1] is copied here instead of summed
-    int tail1_parts = 2;         // partial planes per branch the fused 1x1 tail wrote (conv_mfma_kernel: 2, conv1x1.hip: 1)
+    bool skips_planned_work = false;   // the launching pass legitimately leaves out buffers the plan had to assume (today: lite's table lookup in place of the U branch)
     int tail_form = 0;           // fused tail of this forward: 0 nine tap planes (conv3x3_sp), 1 phase-class sums (conv3x3_rw + tapsum4)
     FwdIO io;
 
@@ -259,7 +288,7 @@ struct Fwd {
         Act a;
         // + 2 KiB slack: the branch-free conv epilogue parks its predicated-off lanes just behind the last element
         a.hi = (half_t*)ar.take((size_t)pixels * ch * 2 + 2048);
-        if (x3 || want_lo) a.lo = (half_t*)ar.take((size_t)pixels * ch * 2 + 2048);
+        if (x3 || want_lo) { a.lo = (half_t*)ar.take((size_t)pixels * ch * 2 + 2048); a.has_lo = true; }
         return a;
     }
     template <typename T> T* blob(size_t off) const { return (T*)(n.blob + off); }
@@ -309,16 +338,20 @@ struct Fwd {
     // auto: the SR nets, whose all-tile sweep keeps its margin with it (worst 8.1e-4 either way, profiles/r03/m_conv64_q8.txt); the DN nets
     // (dn_lite5 7.2e-4 -> 8.6e-4 of the 1e-3 bar) stay on three fp16 products.
     bool use_q8() const { return mixed && (n.opt.x3_impl == 2 || (n.opt.x3_impl == 0 && (n.scale > 1 || n.arch == MOE_ARCH_NETDN))); }      // (round 6: NetDN too -- dn_lite5 7.6e-4 against 8.1e-4 on conv64_x3, and faster)
-    // what conv() asks of a layer before it hands it to conv64_q8 (besides the tensors' own conditions)
+    // what route() asks of a layer before it hands it to conv64_q8 in a chain of fp8 low parts (besides the tensors' own conditions), at the trunk's resolution
     bool q8_capable(const ConvLayer& L) const
     {
-        return n.opt.x3_fuse && n.opt.conv_impl == 2 && L.k == 3 && L.r == 1 && L.nchunks == 1 && L.nseg == 1 && !L.per_plane && L.wq_hi8 && L.w_arsb_lo && !L.has_bias && L.slope <= 1.f &&
-               (long long)B * Hq * Wq * 128 + (Wq + 1ll) * 128 < (1ll << 32) - 65536;
+        ConvX3Form c;
+        c.B = B; c.H = h; c.W = w; c.slope = L.slope; c.in8 = c.out8 = true;
+        return n.opt.x3_fuse && n.opt.conv_impl == 2 && L.k == 3 && L.r == 1 && L.nchunks == 1 && L.nseg == 1 && !L.per_plane && L.wq_hi8 && L.w_arsb_lo && !L.has_bias && conv64_q8_applicable(c);
     }
-    int Hq = 0, Wq = 0;      // the trunk's resolution (set by forward before it plans the chain)
 
-    // one convolution layer: in [B][H][W][64*nseg] -> out [B][H*r][W*r][r>1 ? 64 : 64*nchunks]
+    // one convolution layer: in [B][H][W][64*nseg] -> out [B][H*r][W*r][r>1 ? 64 : 64*nchunks] = route, then (launching pass) launch
     ConvDone conv(const std::string& key, const Act& in, const Act& out, const Act* res, int H, int W, const ConvExtra& extra = ConvExtra{});
+    // which kernel takes the layer: a pure function of the layer, the options, the shape and the operands' FORMS (Act::has_lo / lo8, ConvExtra's flags) -- no pointer, no launcher
+    ConvRoute route(const std::string& key, const Act& in, const Act& out, const Act* res, int H, int W, const ConvExtra& extra = ConvExtra{}) const;
+    ConvForm form(const ConvLayer& L, int H, int W) const;      // the layer's plain launch at H x W: shape, grid, slope / scale
+    int launch(const ConvRoute& r, const std::string& key, const Act& in, const Act& out, const Act* res, const ConvExtra& extra);
     // the first and the last kernel of every family: x -> stem (lite: + conv_input2's output in closed form), and the unfused tail conv(s) -> y
     void stem(const Act& out, const Act* out2 = nullptr);
     void tail(const Act* r, const Act* u, int H, int W, bool skip);
