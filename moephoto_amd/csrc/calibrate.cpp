@@ -77,7 +77,7 @@ struct CalibSample {
         HIP_TRY(hipStreamSynchronize(s));      // (x leaves scope)
         return MOE_OK;
     }
-    int run(int c, float* out) { return forward_dev(n, xd + (size_t)c * nin, MOE_F32, B, h, w, (long long)h * w, w, 1, nullptr, out, MOE_F32, nullptr, s); }
+    int run(int c, float* out) { return forward_dev(n, FwdIO{xd + (size_t)c * nin, MOE_F32, (long long)h * w, w, 1, nullptr, out, MOE_F32, nullptr}, B, h, w, s, true, own_ctx(n, &n.set)); }
     // the net as it stands, every chunk, into `ref`
     int fill_ref()
     {
@@ -105,7 +105,7 @@ struct CalibSample {
     void give_back_workspace()
     {
         (void)hipStreamSynchronize(s);
-        if (n.ws) { (void)hipFree(n.ws); n.ws = nullptr; n.ws_bytes = 0; }
+        if (n.set.ws) { (void)hipFree(n.set.ws); n.set.ws = nullptr; n.set.ws_bytes = 0; }
     }
 };
 

@@ -9,7 +9,8 @@
 // HOW A LAYER FINDS ITS KERNEL.  Fwd::conv = route, then (launching pass only) launch.  route is a pure function of the layer, the options, the shape and the operands'
 // forms -- flags: Act::has_lo / lo8, ConvExtra's requests -- and asks each candidate kernel's *_applicable predicate (common.h), the very function its launcher refuses
 // by; its answer (kernel, pooled, gated, tail parts, ok) is the same on both passes, so the sequences branch on it freely.  launch fills the arguments of exactly that
-// kernel: a launcher that refuses what its predicate promised is an internal error naming layer and kernel, never a fall-through to another kernel.
+// kernel: a launcher that refuses what its predicate promised is an internal error naming layer and kernel, never a fall-through to another kernel.  What route reads
+// beyond the net is the forward's own: f.groups and its context (FwdCtx: stream set, workgroups, fork, gate, table capture) -- no forward writes the net's configuration.
 //
 // THE CHECK.  The arena of the launching pass carries the planned size as its limit: a take beyond it turns the rest of the sequence dry (nothing is launched over
 // memory the plan did not size) and fails the forward; behind the sequence forward_dev_chunk compares the two passes' final offsets (plan_matches).
@@ -39,8 +40,8 @@ ConvForm Fwd::form(const ConvLayer& L, int H, int W) const
     // Workgroup (chunk, g) is block ((g / 8) * nchunks + chunk) * 8 + g % 8 and blocks go round-robin to the 8 XCDs, so an XCD gets
     // nchunks * ceil(G / 8) persistent workgroups: keep that within its CUs (one 160-KiB workgroup per CU), or some XCDs need a
     // second round (Net3x: 9 chunks x G = 28 put 36 workgroups on four XCDs of 32 CUs -- 0.67 instead of 0.48 ms per launch)
-    const int per_xcd = n.max_groups / 8;
-    int G = per_xcd >= L.nchunks ? 8 * (per_xcd / L.nchunks) : n.max_groups / L.nchunks;
+    const int per_xcd = groups / 8;
+    int G = per_xcd >= L.nchunks ? 8 * (per_xcd / L.nchunks) : groups / L.nchunks;
     if (G < 1) G = 1;
     if (G > items) G = (int)items;
     c.G = G;
@@ -65,16 +66,16 @@ ConvRoute Fwd::route(const std::string& key, const Act& in, const Act& out, cons
     const int px = (W + kTileW - 1) / kTileW;
     c.res = res != nullptr; c.tail1 = e.fuse_tail1;
     c.tail = e.fuse_tail; c.tail_form = e.fuse_tail ? tail_form : 0; c.tail_split = (e.fuse_tail && mixed && tail_split_for(key)) ? 1 : 0;
-    if (e.pool && !x3 && L.r == 1 && L.nchunks == 1 && !res && pooled_groups_ok((long long)c.py, (long long)B * c.py, n.max_groups)) {      // conv3x3_rw's pooled epilogue (SEDN rblock.2)
+    if (e.pool && !x3 && L.r == 1 && L.nchunks == 1 && !res && pooled_groups_ok((long long)c.py, (long long)B * c.py, groups)) {      // conv3x3_rw's pooled epilogue (SEDN rblock.2)
         c.pool = true; c.pool_slabs = e.pool_slabs;
-        c.G = pooled_groups((long long)c.py, (long long)B * c.py, n.max_groups);      // its work items are patch ROWS (conv3x3_rw.hip, EPI 4): slab contents independent of the launch's plane count (common.h)
+        c.G = pooled_groups((long long)c.py, (long long)B * c.py, groups);      // its work items are patch ROWS (conv3x3_rw.hip, EPI 4): slab contents independent of the launch's plane count (common.h)
     }
     const bool fast = fast_layer(n, L);
     if (e.fuse_tail && !(fast && !x3)) return refuse();
     // lite's 1x1 convs (conv_input2, the upsampler stages with or without the folded 48->1 tail): the HBM-bound kernel of conv1x1.hip,
     // in fp16 or with split operands; MOE_CONV1X1=0 keeps them on the generic kernel (A/B)
     if (n.opt.conv1x1 && L.taps == 1 && L.nseg == 1 && !L.per_plane && !res && L.scale == 1.f && !e.fuse_tail && n.opt.conv_impl == 2 && (!x3 || (in.has_lo && L.has_x3)) &&
-        conv1x1_applicable(Conv1x1Form{B, H, W, L.r, L.nchunks, c.out_cs, L.slope, x3, e.fuse_tail1, x3 && out.has_lo}, n.max_groups)) {
+        conv1x1_applicable(Conv1x1Form{B, H, W, L.r, L.nchunks, c.out_cs, L.slope, x3, e.fuse_tail1, x3 && out.has_lo}, groups)) {
         if (e.fuse_tail1) r.done.tail1_parts = 1;
         return take(ConvKernel::conv1x1);
     }
@@ -94,7 +95,7 @@ ConvRoute Fwd::route(const std::string& key, const Act& in, const Act& out, cons
         // 32 four-row blocks: a range recomputes two blocks at its ends, and a launch of three planes of 256 x 256 (the reference's own per-tile loop) would
         // give each of the 256 workgroups six.  conv3x3_rw<1> below produces the same bits (same MFMAs in the same order), so the choice is invisible.
         if (fast && n.opt.up_impl == 1 && !c.tail && !c.pool && c.r == 2 && c.nchunks == 4 && c.in_cs == 64 && !c.res && c.scale == 1.f && !c.dbg && L.has_bias &&
-            (long long)B * px * (H / 4) >= 32ll * n.max_groups && ps4_store_applicable(B, H, W, L.slope))
+            (long long)B * px * (H / 4) >= 32ll * groups && ps4_store_applicable(B, H, W, L.slope))
             return take(ConvKernel::ps4_store);
         // PReLU-only epilogues (first upsampler stage of Net4x, SEDN's rblock convs) run on the register-resident-weights kernel
         // (conv3x3_rw.hip: 6 % faster there); option sp_impl = sp keeps them on conv3x3_sp (A/B)
@@ -111,18 +112,18 @@ ConvRoute Fwd::route(const std::string& key, const Act& in, const Act& out, cons
         ConvX3Form q;
         q.B = B; q.H = H; q.W = W; q.slope = L.slope; q.res = res != nullptr; q.res_lo = res_lo;
         const long long P = (long long)px * c.py;      // (conv64_x3's patches are 8 x 32 outputs, as the launcher counts them)
-        if (e.pool && !res && (L.slope == 1.f || e.pool_act) && pooled_groups_ok(P, (long long)B * P, n.max_groups)) { q.pool = true; q.pool_slabs = e.pool_slabs; }
+        if (e.pool && !res && (L.slope == 1.f || e.pool_act) && pooled_groups_ok(P, (long long)B * P, groups)) { q.pool = true; q.pool_slabs = e.pool_slabs; }
         if (e.gate && res && !use_q8()) q.gate = true;
         r.x3 = q;
         // (use_q8: the two correction products on fp8 operands, conv64_q8.hip; its chain form streamed down a column, conv64_sq.hip)
         if (use_q8() && L.wq_hi8 && !q.pool && (!res || res->lo8 == in.lo8)) {
             r.x3.in8 = in.lo8; r.x3.out8 = out.lo8;
-            if (n.opt.q8_impl == 1 && conv64_sq_applicable(r.x3, n.max_groups)) return take(ConvKernel::sq);
+            if (n.opt.q8_impl == 1 && conv64_sq_applicable(r.x3, groups)) return take(ConvKernel::sq);
             if (conv64_q8_applicable(r.x3)) return take(ConvKernel::q8);
             r.x3 = q;
         }
         if (any8) return refuse();
-        if (conv64_x3_applicable(q, n.max_groups)) { r.done.pooled = q.pool; r.done.gated = q.gate; return take(ConvKernel::x3); }
+        if (conv64_x3_applicable(q, groups)) { r.done.pooled = q.pool; r.done.gated = q.gate; return take(ConvKernel::x3); }
     }
     if (fast && L.nchunks <= 16) {
         // 3x3 conv: the two low-order products run on the fast kernel as ordinary fp16-output convolutions --
@@ -185,7 +186,7 @@ int Fwd::launch(const ConvRoute& r, const std::string& key, const Act& in, const
         if (r.kernel == ConvKernel::ps4_store) {
             Ps4Args q{};
             q.in = ca.in; q.wpk = ca.wpk; q.bias = ca.bias; q.out = ca.out; q.slope = ca.slope; q.B = ca.B; q.H = ca.H; q.W = ca.W;
-            return launch_conv3x3_ps4(q, n.max_groups, s);
+            return launch_conv3x3_ps4(q, groups, s);
         }
         launch_conv_mfma(ca, L.taps, L.nseg, s);
         return true;
@@ -198,7 +199,7 @@ int Fwd::launch(const ConvRoute& r, const std::string& key, const Act& in, const
         q.tail_w = e.tail1_w; q.tail_out = e.tail1_out; q.slope = L.slope;
         q.B = B; q.H = H; q.W = W; q.r = L.r; q.nchunks = L.nchunks; q.out_cs = c.out_cs;
         q.nks = (L.cin <= 48 && n.opt.k48) ? 3 : 4;
-        ok = launch_conv1x1(q, n.max_groups, s);
+        ok = launch_conv1x1(q, groups, s);
         break;
     }
     case ConvKernel::mfma: case ConvKernel::sp: case ConvKernel::rw: case ConvKernel::ps4_store: {
@@ -235,10 +236,10 @@ int Fwd::launch(const ConvRoute& r, const std::string& key, const Act& in, const
         q.slope = L.slope; q.B = B; q.H = H; q.W = W;
         if (r.x3.pool) { q.pool = e.pool_out; q.pool_slabs = e.pool_slabs; }
         if (r.x3.gate) q.gate = e.gate_in;
-        if (r.kernel == ConvKernel::x3) { ok = launch_conv64_x3(q, n.max_groups, s); break; }
+        if (r.kernel == ConvKernel::x3) { ok = launch_conv64_x3(q, groups, s); break; }
         q.wq_hi16 = blob<half_t>(L.w_hi); q.wq_hi8 = blob<unsigned char>(L.wq_hi8); q.wq_lo8 = blob<unsigned char>(L.wq_lo8);
         q.in8 = r.x3.in8; q.out8 = r.x3.out8;
-        ok = r.kernel == ConvKernel::sq ? launch_conv64_sq(q, n.max_groups, s) : launch_conv64_q8(q, n.max_groups, s);
+        ok = r.kernel == ConvKernel::sq ? launch_conv64_sq(q, groups, s) : launch_conv64_q8(q, groups, s);
         break;
     }
     case ConvKernel::sp_three: {      // (see route)
@@ -293,7 +294,7 @@ void Fwd::stem(const Act& out, const Act* out2)
 
 // forwards that run ahead of the caller's stream (moe_net_forward_ex): everything up to here touched the net's own workspace only; the kernel that writes the caller's y
 // must not overtake what the caller enqueued before this call (y's memory may have been in use by it)
-void Fwd::gate() { if (n.out_gate && !dry()) (void)hipStreamWaitEvent(s, n.out_gate, 0); }
+void Fwd::gate() { if (ctx.gate_event && !dry()) (void)hipStreamWaitEvent(s, ctx.gate_event, 0); }
 
 void Fwd::tail(const Act* r, const Act* u, int H, int W, bool skip)
 {
@@ -375,7 +376,7 @@ long long sp_bytes_per_pixel(const moe_net& n)
     return per;
 }
 
-static int run_forward(moe_net& n, Fwd& f, const FwdIO& io)
+static int run_forward(const moe_net& n, Fwd& f, const FwdIO& io)
 {
     const int B = f.B, h = f.h, w = f.w;
     const long long P = (long long)B * h * w;
@@ -399,10 +400,17 @@ static int run_forward(moe_net& n, Fwd& f, const FwdIO& io)
     return rc ? rc : f.rc;      // (f.rc: a launcher refused the layer its route promised -- Fwd::launch)
 }
 
-static size_t workspace_need(moe_net& n, int B, int h, int w)
+// one forward's state: the planning pass (no base in the arena, no stream, no records) and the launching pass are built alike
+static Fwd make_fwd(const moe_net& n, const FwdCtx& ctx, NetRuntime* rt, hipStream_t s, int B, int h, int w, Arena ar)
 {
-    Fwd f{n, nullptr, B, h, w, Arena{}, n.precision == MOE_PREC_FP16X3, n.precision == MOE_PREC_DEBUG_DIRECT};
+    Fwd f{n, ctx, rt, s, B, h, w, ar, ctx.groups, n.precision == MOE_PREC_FP16X3, n.precision == MOE_PREC_DEBUG_DIRECT};
     f.mixed = n.precision == MOE_PREC_MIXED;
+    return f;
+}
+
+static size_t workspace_need(const moe_net& n, const FwdCtx& ctx, int B, int h, int w)
+{
+    Fwd f = make_fwd(n, ctx, nullptr, nullptr, B, h, w, Arena{});
     run_forward(n, f, FwdIO{});
     return f.ar.off + 4096;
 }
@@ -414,30 +422,33 @@ static bool plan_matches(const Fwd& f, size_t planned)
     return f.skips_planned_work ? f.ar.off <= planned : f.ar.off == planned;
 }
 
-static int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
-                             const long long* x_off_dev, void* y, int y_dtype, const long long* y_off_dev, hipStream_t s, bool y_off_mult8);
+static int forward_dev_chunk(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s, bool y_off_mult8, const FwdCtx& ctx);
 
-// The table of lite's U branch (moe_net::lut), filled on the first fp16 forward of a checkpoint: one ordinary forward of the net on a 256 x 256 one-plane image whose pixel
-// (i, j) holds the fp16 bit pattern 256 i + j; run_forward copies the U branch's plane (part[1]) instead of summing.  Not during stream capture (it allocates), not for
+// The table of lite's U branch (moe_net::lut), filled on the first fp16 forward of a checkpoint: one forward of the net on a 256 x 256 one-plane image whose pixel
+// (i, j) holds the fp16 bit pattern 256 i + j, told through its context (FwdCtx::lut_capture) that forward_lite copies the U branch's plane (part[1]) instead of summing.  Not during stream capture (it allocates), not for
 // precisions / options whose fused tail is not the one-part form (then the table stays unavailable and the branch is computed as before).
-static void build_lite_lut_on_device(moe_net& n, hipStream_t s)
+static void build_lite_lut_on_device(moe_net& n, hipStream_t s, const FwdCtx& ctx)
 {
     const int r = n.scale;
     std::vector<unsigned short> pat(65536);
     for (int i = 0; i < 65536; ++i) pat[(size_t)i] = (unsigned short)i;
-    if (hipMalloc((void**)&n.lut_in, 65536 * 2) != hipSuccess || hipMalloc((void**)&n.lut, (size_t)65536 * r * r * 4) != hipSuccess) { (void)hipGetLastError(); drop_lut(n); n.lut_state = -1; return; }
-    if (hipMemcpyAsync(n.lut_in, pat.data(), 65536 * 2, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); drop_lut(n); n.lut_state = -1; return; }
+    half_t* in = nullptr;
     float* scratch = nullptr;
-    if (hipMalloc((void**)&scratch, (size_t)65536 * r * r * 4) != hipSuccess) { (void)hipGetLastError(); drop_lut(n); n.lut_state = -1; return; }
-    n.lut_state = 2;
-    const int rc = forward_dev_chunk(n, n.lut_in, MOE_F16, 1, 256, 256, 65536, 256, 1, nullptr, scratch, MOE_F32, nullptr, s, true);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    if (rc != MOE_OK) { (void)hipGetLastError(); drop_lut(n); n.lut_state = -1; return; }
-    n.lut_state = 1;
+    int rc = MOE_ENOMEM;
+    if (hipMalloc((void**)&in, 65536 * 2) == hipSuccess && hipMalloc((void**)&n.lut, (size_t)65536 * r * r * 4) == hipSuccess && hipMalloc((void**)&scratch, (size_t)65536 * r * r * 4) == hipSuccess &&
+        hipMemcpyAsync(in, pat.data(), 65536 * 2, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
+        FwdCtx capture = ctx;
+        capture.lut_capture = n.lut;
+        rc = forward_dev_chunk(n, FwdIO{in, MOE_F16, 65536, 256, 1, nullptr, scratch, MOE_F32, nullptr}, 1, 256, 256, s, true, capture);
+        (void)hipStreamSynchronize(s);
+    }
+    if (in) (void)hipFree(in);
+    if (scratch) (void)hipFree(scratch);
+    if (rc != MOE_OK) { (void)hipGetLastError(); drop_lut(n); }
+    n.lut_state = rc == MOE_OK ? 1 : -1;      // (-1 while the table's own forward runs, too: it computes the branch it captures -- build_lite_lut)
 }
 
-static void build_lite_lut(moe_net& n, hipStream_t s)
+static void build_lite_lut(moe_net& n, hipStream_t s, const FwdCtx& ctx)
 {
     n.lut_state = -1;
     if (n.arch != MOE_ARCH_LITE || !n.opt.lite_lut || n.debug || !n.opt.fuse_tail || n.precision == MOE_PREC_DEBUG_DIRECT) return;
@@ -446,16 +457,15 @@ static void build_lite_lut(moe_net& n, hipStream_t s)
     // the table, its input and the scratch live on the net's device, whichever device the caller has current; the caller's current device is left as it was
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || (cur != n.device && hipSetDevice(n.device) != hipSuccess)) { (void)hipGetLastError(); n.lut_state = 0; return; }
-    build_lite_lut_on_device(n, s);
+    build_lite_lut_on_device(n, s, ctx);
     if (cur != n.device) (void)hipSetDevice(cur);
 }
 
-int forward_dev(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
-                const long long* x_off_dev, void* y, int y_dtype, const long long* y_off_dev, hipStream_t s, bool y_off_mult8)
+int forward_dev(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s, bool y_off_mult8, const FwdCtx& ctx)
 {
     if (!n.finalized) return fail(MOE_ESTATE, "moe_net_forward: net is not finalized (load_state_dict + to(device) first)");
     if (B < 1 || h < 1 || w < 1) return fail(MOE_EINVAL, "moe_net_forward: bad shape B=%d h=%d w=%d", B, h, w);
-    if ((x_dtype != MOE_F32 && x_dtype != MOE_F16) || (y_dtype != MOE_F32 && y_dtype != MOE_F16))
+    if ((io.x_dtype != MOE_F32 && io.x_dtype != MOE_F16) || (io.y_dtype != MOE_F32 && io.y_dtype != MOE_F16))
         return fail(MOE_EINVAL, "moe_net_forward: x/y dtype must be MOE_F32 or MOE_F16");
     // planes per launch set: whatever the caller batched (whole-image tiles under cropsize 'auto', MOE_TILES_PER_BATCH ...), a launch
     // never leaves the fast kernel's addressing range -- larger batches are run as several launch sets
@@ -463,41 +473,38 @@ int forward_dev(moe_net& n, const void* x, int x_dtype, int B, int h, int w, lon
     if (bmax < 1)
         return fail(MOE_ENOMEM, "a %dx%d tile exceeds the convolution kernels' addressing range (%lld pixels per plane at most for this net): use a smaller cropsize",
                     h, w, kSpRange / sp_bytes_per_pixel(n));
-    if (n.arch == MOE_ARCH_LITE && x_dtype == MOE_F16 && n.lut_state == 0 && n.opt.lite_lut) build_lite_lut(n, s);      // (after the checks: a refused call builds nothing)
-    if (B <= bmax) return forward_dev_chunk(n, x, x_dtype, B, h, w, sB, sH, sW, x_off_dev, y, y_dtype, y_off_dev, s, y_off_mult8);
-    const size_t xe = x_dtype == MOE_F32 ? 4 : 2, ye = y_dtype == MOE_F32 ? 4 : 2;
+    if (n.arch == MOE_ARCH_LITE && io.x_dtype == MOE_F16 && n.lut_state == 0 && n.opt.lite_lut) build_lite_lut(n, s, ctx);      // (after the checks: a refused call builds nothing)
+    if (B <= bmax) return forward_dev_chunk(n, io, B, h, w, s, y_off_mult8, ctx);
+    const size_t xe = io.x_dtype == MOE_F32 ? 4 : 2, ye = io.y_dtype == MOE_F32 ? 4 : 2;
     const long long yplane = (long long)h * n.scale * w * n.scale;
     for (int b0 = 0; b0 < B; b0 += (int)bmax) {
         const int cnt = (int)std::min<long long>(bmax, B - b0);
-        const void* xc = x_off_dev ? x : (const void*)((const char*)x + (size_t)b0 * sB * xe);
-        void* yc = y_off_dev ? y : (void*)((char*)y + (size_t)b0 * yplane * ye);
-        const bool al = y_off_mult8 && (y_off_dev || ((size_t)b0 * yplane * ye) % 16 == 0);
-        int rc = forward_dev_chunk(n, xc, x_dtype, cnt, h, w, sB, sH, sW, x_off_dev ? x_off_dev + b0 : nullptr, yc, y_dtype,
-                                   y_off_dev ? y_off_dev + b0 : nullptr, s, al);
-        if (rc) return rc;
+        FwdIO c = io;      // this launch set's planes: the tables advance, or the base pointers do
+        if (io.x_off) c.x_off += b0; else c.x = (const char*)io.x + (size_t)b0 * io.sB * xe;
+        if (io.y_off) c.y_off += b0; else c.y = (char*)io.y + (size_t)b0 * yplane * ye;
+        const bool al = y_off_mult8 && (io.y_off || ((size_t)b0 * yplane * ye) % 16 == 0);
+        if (int rc = forward_dev_chunk(n, c, cnt, h, w, s, al, ctx)) return rc;
     }
     return MOE_OK;
 }
 
-static int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
-                             const long long* x_off_dev, void* y, int y_dtype, const long long* y_off_dev, hipStream_t s, bool y_off_mult8)
+static int forward_dev_chunk(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s, bool y_off_mult8, const FwdCtx& ctx)
 {
     int cur = -1;
     HIP_TRY(hipGetDevice(&cur));
     if (cur != n.device) HIP_TRY(hipSetDevice(n.device));
-    const size_t need = workspace_need(n, B, h, w);
-    if (need > n.ws_bytes) {
-        if (n.ws) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(n.ws)); n.ws = nullptr; n.ws_bytes = 0; }
-        hipError_t e = hipMalloc((void**)&n.ws, need);
+    const size_t need = workspace_need(n, ctx, B, h, w);
+    StreamSet& set = *ctx.set;
+    if (need > set.ws_bytes) {
+        if (set.ws) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(set.ws)); set.ws = nullptr; set.ws_bytes = 0; }
+        hipError_t e = hipMalloc((void**)&set.ws, need);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(MOE_ENOMEM, "workspace of %zu bytes for %d planes of %dx%d does not fit", need, B, h, w); }
-        n.ws_bytes = need;
+        set.ws_bytes = need;
     }
     const size_t planned = need - 4096;
-    Fwd f{n, s, B, h, w, Arena{n.ws, 0, planned}, n.precision == MOE_PREC_FP16X3, n.precision == MOE_PREC_DEBUG_DIRECT};
-    f.mixed = n.precision == MOE_PREC_MIXED;
-    f.y_vec = y_off_mult8 && ((uintptr_t)y % 16 == 0);   // every output plane starts 16-byte aligned: wide stores allowed
-    if (n.lut_state == 2 && x == (const void*)n.lut_in) f.lut_capture = n.lut;      // (build_lite_lut's own forward)
-    int rc = run_forward(n, f, FwdIO{x, x_dtype, sB, sH, sW, x_off_dev, y, y_dtype, y_off_dev});
+    Fwd f = make_fwd(n, ctx, &n.rt, s, B, h, w, Arena{set.ws, 0, planned});
+    f.y_vec = y_off_mult8 && ((uintptr_t)io.y % 16 == 0);   // every output plane starts 16-byte aligned: wide stores allowed
+    int rc = run_forward(n, f, io);
     if (rc) return rc;
     if (!plan_matches(f, planned))
         return fail(MOE_EINVAL, "internal error: the launching pass took %zu bytes of workspace%s, the planning pass %zu (%d planes of %dx%d)", f.ar.off,
@@ -507,14 +514,33 @@ static int forward_dev_chunk(moe_net& n, const void* x, int x_dtype, int B, int 
     return MOE_OK;
 }
 
+void free_set(StreamSet& set)
+{
+    if (set.side) { (void)hipStreamSynchronize(set.side); (void)hipStreamDestroy(set.side); }
+    for (hipEvent_t e : {set.ev_fork, set.ev_join}) if (e) (void)hipEventDestroy(e);
+    if (set.ws) (void)hipFree(set.ws);
+    set = StreamSet{};
+}
+
+void free_records(NetRuntime& rt)
+{
+    for (auto& ev : rt.prof_ev) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
+    for (auto& sl : rt.off_ring) {
+        if (sl.host) (void)hipHostFree(sl.host);
+        if (sl.dev) (void)hipFree(sl.dev);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+    }
+    for (auto& t : rt.taps) if (t.second.dev) (void)hipFree(t.second.dev);
+    rt = NetRuntime{};
+}
+
 void pipe_destroy(moe_net& n)
 {
     for (auto& ps : n.pipe) {
         if (ps.main) { (void)hipStreamSynchronize(ps.main); (void)hipStreamDestroy(ps.main); }
-        if (ps.side) { (void)hipStreamSynchronize(ps.side); (void)hipStreamDestroy(ps.side); }
-        for (hipEvent_t e : {ps.ev_fork, ps.ev_join, ps.entry, ps.done}) if (e) (void)hipEventDestroy(e);
-        if (ps.ws) (void)hipFree(ps.ws);
-        ps = moe_net::PipeSet{};
+        for (hipEvent_t e : {ps.entry, ps.done}) if (e) (void)hipEventDestroy(e);
+        free_set(ps);
+        ps = PipeSet{};
     }
     n.pipe_prev_valid = false;
     n.pipe_last_stream = nullptr;
@@ -538,8 +564,8 @@ static bool overlap_eligible(const moe_net& n, int B, int h, int w)
 static int forward_pipelined(moe_net* n, const void* x, int x_dtype, int B, int h, int w, int64_t sB, int64_t sH, int64_t sW, void* y, int y_dtype, hipStream_t s, unsigned flags)
 {
     HIP_TRY(hipSetDevice(n->device));
-    moe_net::PipeSet& ps = n->pipe[n->pipe_next];
-    moe_net::PipeSet& prev = n->pipe[n->pipe_next ^ 1];
+    PipeSet& ps = n->pipe[n->pipe_next];
+    PipeSet& prev = n->pipe[n->pipe_next ^ 1];
     if (!ps.main) {
         HIP_TRY(hipStreamCreateWithFlags(&ps.main, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&ps.entry, hipEventDisableTiming));
@@ -549,18 +575,10 @@ static int forward_pipelined(moe_net* n, const void* x, int x_dtype, int B, int 
     const bool since_prev = (flags & MOE_FWD_INPUT_SINCE_PREV) && n->pipe_prev_valid && n->pipe_last_stream == s && prev.entry;
     HIP_TRY(hipStreamWaitEvent(ps.main, since_prev ? prev.entry : ps.entry, 0));
     n->pipe_next ^= 1;
-    auto swap_set = [&]() { std::swap(n->ws, ps.ws); std::swap(n->ws_bytes, ps.ws_bytes); std::swap(n->side, ps.side); std::swap(n->ev_fork, ps.ev_fork); std::swap(n->ev_join, ps.ev_join); };
-    swap_set();
-    const int groups0 = n->max_groups;
-    n->max_groups = n->opt.overlap_groups > 0 ? std::max(16, std::min(n->opt.overlap_groups, groups0)) : std::max(16, groups0 / 2);
-    n->out_gate = since_prev ? ps.entry : nullptr;
-    const int fork0 = n->opt.branch_streams;
-    if (!n->opt.overlap_fork) n->opt.branch_streams = 0;
-    const int rc = forward_dev(*n, x, x_dtype, B, h, w, sB, sH, sW, nullptr, y, y_dtype, nullptr, ps.main, true);
-    n->opt.branch_streams = fork0;
-    n->out_gate = nullptr;
-    n->max_groups = groups0;
-    swap_set();
+    // its own set, its share of the chip (two forwards in flight: half each by default), its last kernel behind this call's entry; forking the U branch as well is an option
+    const int groups = n->opt.overlap_groups > 0 ? std::max(16, std::min(n->opt.overlap_groups, n->max_groups)) : std::max(16, n->max_groups / 2);
+    const FwdCtx ctx{&ps, groups, n->opt.overlap_fork && n->opt.branch_streams, since_prev ? ps.entry : nullptr, nullptr};
+    const int rc = forward_dev(*n, FwdIO{x, x_dtype, sB, sH, sW, nullptr, y, y_dtype, nullptr}, B, h, w, ps.main, true, ctx);
     // the caller's stream continues behind this forward -- also when it failed half-way (kernels may be in flight on the set's streams)
     if (hipEventRecord(ps.done, ps.main) != hipSuccess || hipStreamWaitEvent(s, ps.done, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ps.main); }
     n->pipe_prev_valid = rc == MOE_OK;
@@ -594,13 +612,13 @@ int moe_net_forward(moe_net* n, const void* x, int x_dtype, int B, int h, int w,
     hipStream_t s = (hipStream_t)stream;
     long long* xo = nullptr;
     long long* yo = nullptr;
-    moe_net::OffSlot* slot = nullptr;
+    NetRuntime::OffSlot* slot = nullptr;
     if (x_off || y_off) {
         // The host tables ride to the device on the launch stream: a slot of a small ring (pinned host copy + device copy) per call,
         // reused once the event recorded behind the forward that reads it has fired -- no hipMalloc, no blocking copy, no stream synchronisation.
         HIP_TRY(hipSetDevice(n->device >= 0 ? n->device : 0));
-        moe_net::OffSlot& sl = n->off_ring[n->off_next];
-        n->off_next = (n->off_next + 1) % 4;
+        NetRuntime::OffSlot& sl = n->rt.off_ring[n->rt.off_next];
+        n->rt.off_next = (n->rt.off_next + 1) % 4;
         if (sl.used) HIP_TRY(hipEventSynchronize(sl.done));          // (only when four such forwards are still in flight)
         const size_t need = (size_t)B * 2;
         if (need > sl.cap) {
@@ -622,7 +640,7 @@ int moe_net_forward(moe_net* n, const void* x, int x_dtype, int B, int h, int w,
     }
     bool mult8 = true;
     if (y_off) for (int i = 0; i < B; ++i) mult8 = mult8 && (y_off[i] % 8 == 0);
-    const int rc = forward_dev(*n, x, x_dtype, B, h, w, sB, sH, sW, xo, y, y_dtype, yo, s, mult8);
+    const int rc = forward_dev(*n, FwdIO{x, x_dtype, sB, sH, sW, xo, y, y_dtype, yo}, B, h, w, s, mult8, own_ctx(*n, &n->set));
     // the slot's event covers the copy AND every kernel of this forward that reads the tables: recorded behind them, on their stream, so that a later call on
     // ANOTHER stream cannot overwrite the tables while this forward is still in flight (the host wait above is on this event)
     if (slot && hipEventRecord(slot->done, s) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(s); }
@@ -633,7 +651,7 @@ int64_t moe_net_workspace_bytes(const moe_net* n, int B, int h, int w)
 {
     if (!n || B < 1 || h < 1 || w < 1) return fail(MOE_EINVAL, "moe_net_workspace_bytes: bad argument");
     if (!n->finalized) return fail(MOE_ESTATE, "moe_net_workspace_bytes: net is not finalized");
-    return (int64_t)workspace_need(*const_cast<moe_net*>(n), B, h, w);
+    return (int64_t)workspace_need(*n, own_ctx(*n, nullptr), B, h, w);
 }
 
 int moe_net_set_profile(moe_net* n, const char* layer_substrings)
@@ -649,7 +667,7 @@ int moe_net_set_profile(moe_net* n, const char* layer_substrings)
         if (c == std::string::npos) break;
         pos = c + 1;
     }
-    n->prof_used = 0;
+    n->rt.prof_used = 0;
     return MOE_OK;
 }
 
@@ -658,8 +676,8 @@ int moe_net_get_profile_at(moe_net* n, int index, double* total_ms, int64_t* lau
     if (!n || !total_ms || !launches || !flops) return fail(MOE_EINVAL, "moe_net_get_profile: NULL argument");
     double ms = 0, fl = 0;
     int64_t cnt = 0;
-    for (size_t i = 0; i < n->prof_used; ++i) {
-        const moe_net::ProfRec& r = n->prof_ev[i];
+    for (size_t i = 0; i < n->rt.prof_used; ++i) {
+        const NetRuntime::ProfRec& r = n->rt.prof_ev[i];
         if (r.key != index) continue;
         HIP_TRY(hipEventSynchronize(r.e1));
         float t = 0.f;
@@ -673,7 +691,7 @@ int moe_net_get_profile_at(moe_net* n, int index, double* total_ms, int64_t* lau
 int moe_net_get_profile(moe_net* n, double* total_ms, int64_t* launches, double* flops)
 {
     int rc = moe_net_get_profile_at(n, 0, total_ms, launches, flops);
-    if (rc == MOE_OK) n->prof_used = 0;
+    if (rc == MOE_OK) n->rt.prof_used = 0;
     return rc;
 }
 
@@ -693,8 +711,8 @@ int moe_net_set_debug(moe_net* n, int enable)
 int64_t moe_net_debug_tap(moe_net* n, const char* tap, float* host, int64_t capacity, int64_t shape[4], void* stream)
 {
     if (!n || !tap) return fail(MOE_EINVAL, "moe_net_debug_tap: NULL argument");
-    auto it = n->taps.find(tap);
-    if (it == n->taps.end() || !it->second.dev) return fail(MOE_EINVAL, "no tap named \"%s\" (enable moe_net_set_debug before the forward)", tap);
+    auto it = n->rt.taps.find(tap);
+    if (it == n->rt.taps.end() || !it->second.dev) return fail(MOE_EINVAL, "no tap named \"%s\" (enable moe_net_set_debug before the forward)", tap);
     const auto& t = it->second;
     const int64_t nel = t.shape[0] * t.shape[1] * t.shape[2] * t.shape[3];
     if (shape) for (int d = 0; d < 4; ++d) shape[d] = t.shape[d];

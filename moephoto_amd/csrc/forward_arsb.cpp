@@ -34,7 +34,7 @@ bool can_fuse_tail(const moe_net& n, const Fwd& f)
 
 // one forward: what its paragraphs share
 struct ArsbRun {
-    moe_net& n;
+    const moe_net& n;
     Fwd& f;
     const int B, h, w;
     bool mixed = false;                  // MIXED: the stem output and the trunk stream as hi + lo pairs
@@ -85,7 +85,7 @@ void ArsbRun::plan_tail_form()
         // the same layer with all four phases in one workgroup (conv3x3_ps4.hip): one fp32 plane + column aprons per branch, added by tailadd
         ps4 = ok && n.opt.up_impl == 1 && ps4_ok && (2 * wl) % 8 == 0;
         // x3 nets: the phase-row form of the same kernel (conv3x3_ps9.hip): three fp32 planes S[dy] + column aprons per branch, added by tailadd3
-        ps9 = fuse && n.opt.up_impl == 1 && n.r == 3 && n.max_groups >= 3 && ps9_ok;
+        ps9 = fuse && n.opt.up_impl == 1 && n.r == 3 && f.groups >= 3 && ps9_ok;
     }
 }
 
@@ -104,7 +104,7 @@ int ArsbRun::ps_stage(int br, const std::string& key, const Act& cur, size_t pla
         q.split = (f.mixed && f.tail_split_for(key)) ? 1 : 0;
         const int rec = f.prof_begin(key, 2.0 * (double)B * H * W * L.cout * L.cin * L.taps);
         bool done = false;
-        for (int rep = f.repeats(key); rep > 0; --rep) done = launch(q, n.max_groups, f.s);
+        for (int rep = f.repeats(key); rep > 0; --rep) done = launch(q, f.groups, f.s);
         f.prof_end(rec);
         if (!done) return fail(MOE_EINVAL, "fused tail kernel (%s) rejected layer %s", name, key.c_str());
     }
@@ -183,7 +183,7 @@ int ArsbRun::run_trunk()
                 if (trace && i == 3 && hipMalloc((void**)&q.trace, tb) == hipSuccess) (void)hipMemsetAsync(q.trace, 0, tb, s);
                 const int rec = f.prof_begin("arsb" + std::to_string(i), 2.0 * 2.0 * (double)B * h * w * L1.cout * L1.cin * 9);
                 bool done = false;
-                for (int rep = f.repeats("arsb" + std::to_string(i)); rep > 0; --rep) done = launch_arsb32c(q, n.max_groups, s);
+                for (int rep = f.repeats("arsb" + std::to_string(i)); rep > 0; --rep) done = launch_arsb32c(q, f.groups, s);
                 f.prof_end(rec);
                 if (q.trace) {
                     std::vector<unsigned long long> host(tb / 8);
@@ -208,7 +208,7 @@ int ArsbRun::run_trunk()
                 q.w16[1] = f.blob<half_t>(L2.w_hi); q.wh8[1] = f.blob<unsigned char>(L2.wq_hi8); q.wl8[1] = f.blob<unsigned char>(L2.wq_lo8);
                 q.slope = L1.slope; q.B = B; q.H = h; q.W = w; q.out8 = i < nx;
                 const int rec = f.prof_begin("xpair" + std::to_string(i), 2.0 * 2.0 * 3.0 * (double)B * h * w * L1.cout * L1.cin * 9);
-                const bool done = launch_arsb_sq(q, n.max_groups, s);
+                const bool done = launch_arsb_sq(q, f.groups, s);
                 f.prof_end(rec);
                 if (!done) return fail(MOE_EINVAL, "internal error: arsb_sq rejected layer %s its predicate took", k1.c_str());
             }
@@ -303,45 +303,46 @@ int ArsbRun::run()
     // forks here onto a second stream behind the stem and joins in front of the branch sum; its workgroups take the CUs the trunk's launches leave.  Same kernels, same
     // bits (tests); the predicate is a function of the shape alone, so the workspace plan (dry run) allocates in the same order.
     // (not under FP16X3: its three-launch fallback shares one side buffer between the layers)
-    const bool forked = sr && n.opt.branch_streams && !n.debug && !f.direct && !f.x3 && n.opt.conv_impl == 2 && (long long)B * h * w <= 4ll * 65536;      // (up to four planes of 256 x 256: the per-tile call
+    const bool forked = sr && f.ctx.fork && !n.debug && !f.direct && !f.x3 && n.opt.conv_impl == 2 && (long long)B * h * w <= 4ll * 65536;      // (up to four planes of 256 x 256: the per-tile call
                                                                                                                                       // with or without alpha; a ragged group of 21 planes of 88 x 256 inside a
                                                                                                                                       // batched frame is NOT small: forked, the headline frame lost 0.5 ms)
-    // ... each branch on its own share of the chip: side stream g_side persistent workgroups per launch, the caller's stream the rest (restored at scope exit)
-    struct GroupsGuard { moe_net& n; int all; ~GroupsGuard() { n.max_groups = all; } } groups_guard{n, n.max_groups};
     // every exit behind the fork joins the side stream back into the caller's: an early return (a refused layer, a failed HIP call) must not leave kernels in flight on
-    // n.side that the caller's stream never waits for -- the caller may synchronize its own stream and reuse or free the workspace (forward_dev_chunk's regrow does), and
-    // an unjoined fork makes hipStreamEndCapture fail.  Disarmed by the regular join in front of the branch sum.
+    // the side stream that the caller's stream never waits for -- the caller may synchronize its own stream and reuse or free the workspace (forward_dev_chunk's regrow does),
+    // and an unjoined fork makes hipStreamEndCapture fail.  Disarmed by the regular join in front of the branch sum.
     struct ForkGuard {
-        moe_net& n; hipStream_t s; bool armed = false;
+        StreamSet* set; hipStream_t s; bool armed = false;
         ~ForkGuard()
         {
             if (!armed) return;
-            if (hipEventRecord(n.ev_join, n.side) != hipSuccess || hipStreamWaitEvent(s, n.ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(n.side);
+            if (hipEventRecord(set->ev_join, set->side) != hipSuccess || hipStreamWaitEvent(s, set->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(set->side);
         }
-    } fork_guard{n, s};
+    } fork_guard{f.ctx.set, s};
+    // ... each branch on its own share of the chip: side stream g_side persistent workgroups per launch, the caller's stream the rest (f.groups: this forward's own)
+    const int all = f.groups;
     int g_side = 0;
-    if (forked && n.max_groups >= 32) {
-        g_side = n.opt.branch_groups > 0 ? n.opt.branch_groups : (n.stages >= 2 ? 5 * n.max_groups / 16 : 3 * n.max_groups / 16);
-        g_side = std::max(8, std::min(g_side, n.max_groups - 8) / 8 * 8);
+    if (forked && all >= 32) {
+        g_side = n.opt.branch_groups > 0 ? n.opt.branch_groups : (n.stages >= 2 ? 5 * all / 16 : 3 * all / 16);
+        g_side = std::max(8, std::min(g_side, all - 8) / 8 * 8);
     }
     if (forked) {
-        if (g_side) n.max_groups = g_side;
+        if (g_side) f.groups = g_side;
         if (!f.dry()) {
-            if (!n.side) {
-                HIP_TRY(hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&n.ev_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&n.ev_join, hipEventDisableTiming));
+            StreamSet& set = *f.ctx.set;
+            if (!set.side) {
+                HIP_TRY(hipStreamCreateWithFlags(&set.side, hipStreamNonBlocking));
+                HIP_TRY(hipEventCreateWithFlags(&set.ev_fork, hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(&set.ev_join, hipEventDisableTiming));
             }
-            HIP_TRY(hipEventRecord(n.ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(n.side, n.ev_fork, 0));      // behind the stem (and everything before it on the caller's stream: the previous forward's reads of the workspace)
-            f.s = n.side;
+            HIP_TRY(hipEventRecord(set.ev_fork, s));
+            HIP_TRY(hipStreamWaitEvent(set.side, set.ev_fork, 0));      // behind the stem (and everything before it on the caller's stream: the previous forward's reads of the workspace)
+            f.s = set.side;
             fork_guard.armed = true;
         }
         const int rc = run_branch(1, A);
-        if (g_side) n.max_groups = groups_guard.all - g_side;      // the trunk and the R branch: the other CUs
+        if (g_side) f.groups = all - g_side;      // the trunk and the R branch: the other CUs
         if (!f.dry()) {
             f.s = s;
-            if (!rc) HIP_TRY(hipEventRecord(n.ev_join, n.side));
+            if (!rc) HIP_TRY(hipEventRecord(f.ctx.set->ev_join, f.ctx.set->side));
         }
         if (rc) return rc;
     }
@@ -351,15 +352,15 @@ int ArsbRun::run()
     if (!forked) { if (int rc = run_branch(0, Bb)) return rc; if (int rc = run_branch(1, A)) return rc; }
     else {
         if (int rc = run_branch(0, Bb)) return rc;
-        if (!f.dry()) { HIP_TRY(hipStreamWaitEvent(s, n.ev_join, 0)); fork_guard.armed = false; }      // the branch sum below reads both branches
-        n.max_groups = groups_guard.all;
+        if (!f.dry()) { HIP_TRY(hipStreamWaitEvent(s, f.ctx.set->ev_join, 0)); fork_guard.armed = false; }      // the branch sum below reads both branches
+        f.groups = all;
     }
     return branch_sum();
 }
 
 }  // namespace
 
-int moe::forward_arsb(moe_net& n, Fwd& f)
+int moe::forward_arsb(const moe_net& n, Fwd& f)
 {
     ArsbRun r{n, f, f.B, f.h, f.w};
     return r.run();

@@ -3,7 +3,7 @@
 
 using namespace moe;
 
-int moe::forward_lite(moe_net& n, Fwd& f)
+int moe::forward_lite(const moe_net& n, Fwd& f)
 {
     const int B = f.B, h = f.h, w = f.w;
     const long long P = (long long)B * h * w;
@@ -13,7 +13,7 @@ int moe::forward_lite(moe_net& n, Fwd& f)
     const int nslab = (int)std::min<long long>(64, std::max<long long>(1, ((long long)h * w) / 256));
     // the pooled sums of conv_2's output come out of conv64_x3's epilogue, one slab per workgroup (fp16x3, the default of lite); in the
     // other modes a separate pass (pool_partial) forms nslab slabs per plane
-    const int pslabs = n.max_groups;
+    const int pslabs = f.groups;
     const bool poolfuse = n.opt.pool_fuse;
     float* partial = (float*)f.ar.take((size_t)B * std::max(nslab, pslabs) * 64 * 4);
     float* gate = (float*)f.ar.take((size_t)B * 64 * 4);
@@ -85,7 +85,7 @@ int moe::forward_lite(moe_net& n, Fwd& f)
         const ConvLayer& LA = n.convs[n.conv_index.at(up_key(br, st))];
         const ConvLayer& LB = n.convs[n.conv_index.at(up_key(br, st + 1))];
         return LA.taps == 1 && LB.taps == 1 && LA.cin <= 48 && LB.cin <= 48 && LA.r == 2 && LB.r == 2 && LA.nchunks == 4 && LB.nchunks == 4 && LA.w_lo && LB.w_lo &&
-               LA.scale == 1.f && LB.scale == 1.f && conv1x1_f2_applicable(B, H, W, LA.slope, LB.slope, n.max_groups);
+               LA.scale == 1.f && LB.scale == 1.f && conv1x1_f2_applicable(B, H, W, LA.slope, LB.slope, f.groups);
     };
     ConvExtra last;      // what the last stage is asked for under fuse1 (the pointers follow per branch)
     last.fuse_tail1 = true;
@@ -99,7 +99,7 @@ int moe::forward_lite(moe_net& n, Fwd& f)
     const int nparts = fuse1 ? tail_parts(0) : 0;
     // fp16 input and the table of this checkpoint's U branch at hand (moe_net::lut): the U branch is not run, the final sum looks its value up (the table holds
     // complete dot products: a launch set whose R tail comes out in the two-part form computes the U branch as well).  The planning pass has no input: it plans the branch.
-    const bool use_lut = !f.lut_capture && fuse1 && io.x_dtype == MOE_F16 && n.lut_state == 1 && n.lut && n.opt.lite_lut && nparts == 1;
+    const bool use_lut = !f.ctx.lut_capture && fuse1 && io.x_dtype == MOE_F16 && n.lut_state == 1 && n.lut && n.opt.lite_lut && nparts == 1;
     if (fuse1 && !use_lut && tail_parts(1) != nparts) return fail(MOE_EINVAL, "internal error: lite's two branches routed their fused tails to different forms");
     f.skips_planned_work = use_lut;
     for (int br = 0; br < (use_lut ? 1 : 2); ++br) {
@@ -119,7 +119,7 @@ int moe::forward_lite(moe_net& n, Fwd& f)
                     q.tail_w = f.small<float>(br == 0 ? "tail_r.f32" : "tail_u.f32"); q.tail_out = part[br];
                     q.slope_a = LA.slope; q.slope_b = LB.slope; q.B = B; q.H = H; q.W = W;
                     const int rec = f.prof_begin(ckey, 3.0 * 2.0 * (double)B * H * W * (LA.cout * LA.cin + 4.0 * LB.cout * LB.cin));
-                    const bool ok = launch_conv1x1_f2(q, n.max_groups, s);
+                    const bool ok = launch_conv1x1_f2(q, f.groups, s);
                     f.prof_end(rec);
                     if (!ok) return fail(MOE_EINVAL, "internal error: fused upsampler stages (conv1x1_f2) rejected layer %s", ckey.c_str());
                 }
@@ -143,9 +143,9 @@ int moe::forward_lite(moe_net& n, Fwd& f)
     }
     if (fuse1) {
         if (!f.dry()) {
-            if (f.lut_capture) {      // (B = 1, the 256 x 256 image of all patterns: part[1] IS the table)
+            if (f.ctx.lut_capture) {      // (B = 1, the 256 x 256 image of all patterns: part[1] IS the table)
                 if (nparts != 1 || !part[1]) return MOE_EINVAL;
-                HIP_TRY(hipMemcpyAsync(f.lut_capture, part[1], (size_t)H * W * 4, hipMemcpyDeviceToDevice, s));
+                HIP_TRY(hipMemcpyAsync(f.ctx.lut_capture, part[1], (size_t)H * W * 4, hipMemcpyDeviceToDevice, s));
                 return MOE_OK;
             }
             Tail1SumArgs t{};
@@ -155,7 +155,7 @@ int moe::forward_lite(moe_net& n, Fwd& f)
         }
         return MOE_OK;
     }
-    if (f.lut_capture) return MOE_EINVAL;      // (no fused tail: no table -- build_lite_lut marks it unavailable)
+    if (f.ctx.lut_capture) return MOE_EINVAL;      // (no fused tail: no table -- build_lite_lut marks it unavailable)
     f.tail(&fin[0], &fin[1], H, W, false);
     return MOE_OK;
 }

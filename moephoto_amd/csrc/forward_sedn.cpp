@@ -3,7 +3,7 @@
 
 using namespace moe;
 
-int moe::forward_sedn(moe_net& n, Fwd& f)
+int moe::forward_sedn(const moe_net& n, Fwd& f)
 {
     const int B = f.B, h = f.h, w = f.w;
     const long long P = (long long)B * h * w;
@@ -21,12 +21,12 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
     // weights, LeakyReLU and the residual: on conv64_s.hip, or on conv3x3_sp<6>
     ConvForm tf;
     tf.B = B; tf.H = h; tf.W = w; tf.nchunks = B; tf.py = (h + kTileH - 1) / kTileH; tf.slope = 0.2f; tf.res = true; tf.plane_w = true;
-    tf.G = (int)std::max<long long>(B, std::min<long long>(n.max_groups, (long long)B * ((w + kTileW - 1) / kTileW) * tf.py));   // total workgroups (plane b gets every B-th)
+    tf.G = (int)std::max<long long>(B, std::min<long long>(f.groups, (long long)B * ((w + kTileW - 1) / kTileW) * tf.py));   // total workgroups (plane b gets every B-th)
     const bool s64 = n.opt.s64 && conv64_s_applicable(tf);
-    const bool sfuse = n.opt.sedn_fuse && !f.x3 && !f.direct && !n.debug && n.opt.conv_impl == 2 && B <= n.max_groups && (s64 || conv3x3_sp_applicable(tf));
+    const bool sfuse = n.opt.sedn_fuse && !f.x3 && !f.direct && !n.debug && n.opt.conv_impl == 2 && B <= f.groups && (s64 || conv3x3_sp_applicable(tf));
     float* xpart = (float*)f.ar.take((size_t)B * nslab * 5 * 64 * 4);
     // the channel totals of rblock.2's output come out of that conv's epilogue (conv3x3_rw EPI 4), sedn_xsum then only visits the border
-    const int pslabs = 2 * n.max_groups;
+    const int pslabs = 2 * f.groups;
     float* xpool = (float*)f.ar.take((size_t)B * pslabs * 64 * 4);
     const bool spool = n.opt.pool_fuse;
     float* fgate = (float*)f.ar.take((size_t)B * 256 * 4);
@@ -44,7 +44,7 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
                 if (pooled) {
                     const int py = (h + kTileH - 1) / kTileH;
                     fa.pooled = xpool; fa.pooled_slabs = pslabs;
-                    fa.pooled_count = 2 * std::min(pooled_groups((long long)py, (long long)B * py, n.max_groups), py);      // conv3x3_rw EPI 4: slab 2 (g % py) + wave half
+                    fa.pooled_count = 2 * std::min(pooled_groups((long long)py, (long long)B * py, f.groups), py);      // conv3x3_rw EPI 4: slab 2 (g % py) + wave half
                 }
                 fa.w256t = f.small<float>(k + ".w256t"); fa.w256 = f.small<float>(k + ".w256"); fa.wt = f.small<float>(k + ".wt");
                 fa.w_down = f.small<float>(k + ".down"); fa.w_up = f.small<float>(k + ".up");
@@ -57,7 +57,7 @@ int moe::forward_sedn(moe_net& n, Fwd& f)
                 a.B = B; a.H = h; a.W = w; a.in_cs = tf.in_cs; a.out_cs = tf.out_cs; a.r = tf.r; a.nchunks = tf.nchunks;
                 a.px = (w + kTileW - 1) / kTileW; a.py = tf.py; a.G = tf.G;
                 a.slope = tf.slope; a.scale = tf.scale;
-                if (!(s64 ? launch_conv64_s(a, n.max_groups, s) : launch_conv3x3_sp(a, s))) return fail(MOE_EINVAL, "internal error: SEDN fused block tail: %s rejected the layer", s64 ? "conv64_s" : "conv3x3_sp");
+                if (!(s64 ? launch_conv64_s(a, f.groups, s) : launch_conv3x3_sp(a, s))) return fail(MOE_EINVAL, "internal error: SEDN fused block tail: %s rejected the layer", s64 ? "conv64_s" : "conv3x3_sp");
             }
             continue;
         }

@@ -142,6 +142,27 @@ struct NetOptions {
     void from_env();
 };
 
+// the device resources one forward at a time runs on (the forward grows / creates them on demand): its workspace, and the second stream of small launch sets (option
+// branch_streams) -- the U branch forks behind the stem and joins in front of the branch sum
+struct StreamSet { char* ws = nullptr; size_t ws_bytes = 0; hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; };
+// ... with a stream of its own: one of the two sets consecutive small forwards alternate between when the caller declares them independent (option overlap_calls, moe_net_forward_ex)
+struct PipeSet : StreamSet { hipStream_t main = nullptr; hipEvent_t entry = nullptr, done = nullptr; };
+
+// what a forward WRITES of its net besides its stream set -- records, never configuration (a sequence sees the net itself as const)
+struct NetRuntime {
+    // live kernel timing of selected conv layers (bench.py's roofline leg): hipEvent pairs on the launch stream
+    struct ProfRec { hipEvent_t e0 = nullptr, e1 = nullptr; int key = 0; double flops = 0; };
+    std::vector<ProfRec> prof_ev;                // event pairs, reused across steps
+    size_t prof_used = 0;
+    // debug taps
+    struct Tap { float* dev = nullptr; int64_t shape[4] = {0, 0, 0, 0}; };
+    std::map<std::string, Tap> taps;
+    // moe_net_forward's host offset tables: a ring of pinned host slots + device slots, copied asynchronously on the launch stream
+    struct OffSlot { long long* host = nullptr; long long* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
+    OffSlot off_ring[4];
+    int off_next = 0;
+};
+
 }  // namespace moe
 
 struct moe_net {
@@ -158,8 +179,8 @@ struct moe_net {
     bool calib_valid = false;
     // lite, fp16 inputs (round 6): the U branch (MoeNet_lite2.py:47,50: conv_input, uim, convt_I1) is POINTWISE -- 1x1 convs, pixel shuffles, PReLUs on a one-channel input -- so its
     // output at an HR pixel is a function of ONE input value and the pixel's phase: a table over the 65,536 fp16 bit patterns, filled once per checkpoint by the U branch's own
-    // kernels run on an image of all patterns (bit-identical to computing it), [256 r][256 r] fp32.  lut_state: 0 not tried, 1 ready, -1 not available, 2 being built
-    float* lut = nullptr; half_t* lut_in = nullptr; int lut_state = 0;
+    // kernels run on an image of all patterns (bit-identical to computing it), [256 r][256 r] fp32.  lut_state: 0 not tried, 1 ready, -1 not available
+    float* lut = nullptr; int lut_state = 0;
     int calib_blocks = -1;       // smallest count of split-operand ARSBs whose worst noise-tile error against the exact mode is within the target (-1: none is -> FP16X3);
                                  // SEDN: 0 = plain fp16 is within it, -1 = it is not -> FP16X3
     double calib_err = 0.0;      // that error, as predicted for the worst tile of a full frame (measured x the family's inflation factor)
@@ -171,34 +192,16 @@ struct moe_net {
     std::map<std::string, int> conv_index;
     std::map<std::string, size_t> small;     // name -> blob offset of small fp32 / fp16 tables
     std::map<std::string, float> scalars;
-    // workspace
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    int max_groups = 256;
-    // live kernel timing of selected conv layers (bench.py's roofline leg): hipEvent pairs on the launch stream
+    int max_groups = 256;        // persistent workgroups per launch (one per CU, or option max_groups): set at finalize
     std::vector<std::string> prof_keys;          // comma-separated substrings of moe_net_set_profile
-    struct ProfRec { hipEvent_t e0 = nullptr, e1 = nullptr; int key = 0; double flops = 0; };
-    std::vector<ProfRec> prof_ev;                // event pairs, reused across steps
-    size_t prof_used = 0;
-    // moe_net_forward's host offset tables: a ring of pinned host slots + device slots, copied asynchronously on the launch stream
-    struct OffSlot { long long* host = nullptr; long long* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
-    OffSlot off_ring[4];
-    int off_next = 0;
-    // second stream of small launch sets (option branch_streams): the U branch forks behind the stem and joins in front of the branch sum
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // two (stream, workspace, side stream) sets for consecutive small forwards the caller declares independent (option overlap_calls, moe_net_forward_ex): a set's members are
-    // swapped into ws / side / ev_* for the duration of its forward
-    struct PipeSet { hipStream_t main = nullptr, side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, entry = nullptr, done = nullptr; char* ws = nullptr; size_t ws_bytes = 0; };
-    PipeSet pipe[2];
+    bool debug = false;          // debug taps wanted (moe_net_set_debug)
+    // what forwards write: the stream set of ordinary forwards, the two sets of forwards that run ahead of the caller's stream, the records
+    moe::StreamSet set;
+    moe::PipeSet pipe[2];
     int pipe_next = 0;
     bool pipe_prev_valid = false;
     hipStream_t pipe_last_stream = nullptr;
-    hipEvent_t out_gate = nullptr;       // set around such a forward: the kernel that writes the caller's y waits for this event (the caller's stream position at THIS call)
-    // debug taps
-    bool debug = false;
-    struct Tap { float* dev = nullptr; int64_t shape[4] = {0, 0, 0, 0}; };
-    std::map<std::string, Tap> taps;
+    moe::NetRuntime rt;
 
     const moe::Param* get(const std::string& n) const
     {
@@ -223,6 +226,17 @@ struct FwdIO {
     const void* x = nullptr; int x_dtype = MOE_F32; long long sB = 0, sH = 0, sW = 0; const long long* x_off = nullptr;
     void* y = nullptr; int y_dtype = MOE_F32; const long long* y_off = nullptr;
 };
+
+// what a forward is told from outside that is not the net's configuration.  Every forward gets one and none changes the net's: Fwd::route reads the net, f.groups and this.
+struct FwdCtx {
+    StreamSet* set = nullptr;         // the workspace and side stream it runs on (null: a planning pass alone -- moe_net_workspace_bytes)
+    int groups = 0;                   // persistent workgroups per launch
+    bool fork = false;                // a small launch set may run its U branch on the set's side stream
+    hipEvent_t gate_event = nullptr;  // a forward ahead of the caller's stream: the kernel that writes the caller's y waits for this event (the caller's stream position at THIS call)
+    float* lut_capture = nullptr;     // lite: this forward fills the U-branch table -- its input is the image of all fp16 patterns; part[1] is copied here instead of summed
+};
+// the ordinary forward: the given set (the net's own), every workgroup, the fork as option branch_streams says
+inline FwdCtx own_ctx(const moe_net& n, StreamSet* set) { return FwdCtx{set, n.max_groups, n.opt.branch_streams != 0, nullptr, nullptr}; }
 
 // what a layer is asked for beyond in / out / residual, named per call (all null: a plain convolution) ...
 struct ConvExtra {
@@ -266,10 +280,13 @@ struct ConvRoute {
 const char* kernel_name(ConvKernel k);
 
 struct Fwd {
-    moe_net& n;
+    const moe_net& n;
+    const FwdCtx& ctx;
+    NetRuntime* rt;              // (null on a planning pass, which launches and records nothing)
     hipStream_t s;
     int B, h, w;
     Arena ar;
+    int groups;                  // persistent workgroups per launch, from ctx; forward_arsb gives each of its two streams a share while the U branch is forked
     bool x3, direct;
     bool mixed = false;          // MOE_PREC_MIXED: fp16 operands, fp32-equivalent (hi + lo) trunk stream, split operands on selected layers
     bool y_vec = false;
@@ -278,7 +295,6 @@ struct Fwd {
     half_t* side16 = nullptr;    // fp16 sum of the two low-order products of a 3x3 conv (split precision), output layout
     bool dry() const { return ar.base == nullptr; }
     int rc = 0;                  // the internal error of a launch (Fwd::launch): the forward turns dry behind it (Fwd::conv), run_forward returns it
-    float* lut_capture = nullptr;     // lite: this forward fills the U-branch table -- its input is the image of all fp16 patterns; part[1] is copied here instead of summed
     bool skips_planned_work = false;   // the launching pass legitimately leaves out buffers the plan had to assume (today: lite's table lookup in place of the U branch)
     int tail_form = 0;           // fused tail of this forward: 0 nine tap planes (conv3x3_sp), 1 phase-class sums (conv3x3_rw + tapsum4)
     FwdIO io;
@@ -297,7 +313,7 @@ struct Fwd {
     void tap(const std::string& name, const Act& a, int H, int W, int cs, int C)
     {
         if (!n.debug || dry()) return;
-        auto& t = n.taps[name];
+        auto& t = rt->taps[name];
         if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
         const size_t nel = (size_t)B * C * H * W;
         if (hipMalloc((void**)&t.dev, nel * 4) != hipSuccess) return;
@@ -319,19 +335,19 @@ struct Fwd {
     {
         for (size_t i = 0; i < n.prof_keys.size(); ++i) {
             if (key.find(n.prof_keys[i]) == std::string::npos) continue;
-            if (n.prof_used == n.prof_ev.size()) {
-                moe_net::ProfRec r;
+            if (rt->prof_used == rt->prof_ev.size()) {
+                NetRuntime::ProfRec r;
                 if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return -1;
-                n.prof_ev.push_back(r);
+                rt->prof_ev.push_back(r);
             }
-            moe_net::ProfRec& r = n.prof_ev[n.prof_used];
+            NetRuntime::ProfRec& r = rt->prof_ev[rt->prof_used];
             r.key = (int)i; r.flops = flops;
             (void)hipEventRecord(r.e0, s);
-            return (int)n.prof_used++;
+            return (int)rt->prof_used++;
         }
         return -1;
     }
-    void prof_end(int rec) { if (rec >= 0) (void)hipEventRecord(n.prof_ev[rec].e1, s); }
+    void prof_end(int rec) { if (rec >= 0) (void)hipEventRecord(rt->prof_ev[rec].e1, s); }
     int repeats(const std::string& key) const { return (!n.opt.repeat_key.empty() && key.find(n.opt.repeat_key) != std::string::npos) ? n.opt.repeat_n : 1; }
 
     // The two correction products on fp8 operands (conv64_q8.hip): 'mixed' only -- 'fp16x3' promises 2e-5, fp8 corrections deliver ~15 bits.
@@ -359,18 +375,19 @@ struct Fwd {
 };
 
 // the families' sequences (run_forward dispatches; each takes its workspace from f.ar in the SAME order on the planning pass and on the launching one: forward.cpp)
-int forward_arsb(moe_net& n, Fwd& f);
-int forward_sedn(moe_net& n, Fwd& f);
-int forward_lite(moe_net& n, Fwd& f);
+int forward_arsb(const moe_net& n, Fwd& f);
+int forward_sedn(const moe_net& n, Fwd& f);
+int forward_lite(const moe_net& n, Fwd& f);
 
 // forward.cpp
 int exact_blocks_of(const moe_net& n);
 int default_exact_blocks(int arch);
 long long sp_bytes_per_pixel(const moe_net& n);
 constexpr long long kSpRange = (1ll << 32) - (1ll << 16);
-int forward_dev(moe_net& n, const void* x, int x_dtype, int B, int h, int w, long long sB, long long sH, long long sW,
-                const long long* x_off_dev, void* y, int y_dtype, const long long* y_off_dev, hipStream_t s, bool y_off_mult8 = true);
+int forward_dev(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s, bool y_off_mult8, const FwdCtx& ctx);
+void free_set(StreamSet& set);      // (synchronizes its side stream first)
 void pipe_destroy(moe_net& n);
+void free_records(NetRuntime& rt);
 // weights.cpp
 int build_device_weights(moe_net& n, int precision);
 void drop_lut(moe_net& n);

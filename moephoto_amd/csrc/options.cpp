@@ -118,7 +118,7 @@ extern "C" int moe_net_set_option(moe_net* n, const char* key, const char* value
 {
     if (!n || !key || !value) return fail(MOE_EINVAL, "moe_net_set_option: NULL argument");
     if (!n->opt.set(key, value)) return fail(MOE_EINVAL, "moe_net_set_option: unknown option or value \"%s\" = \"%s\"", key, value);
-    if (n->lut_state != 2) drop_lut(*n);      // (a kernel-form switch may change the U branch's bits: the table is refilled by the next fp16 forward)
+    drop_lut(*n);      // (a kernel-form switch may change the U branch's bits: the table is refilled by the next fp16 forward)
     if (!strcmp(key, "max_groups") && n->finalized) n->max_groups = n->opt.max_groups > 0 ? n->opt.max_groups : conv_mfma_max_groups();
     return MOE_OK;
 }

@@ -367,7 +367,7 @@ int moe_run_plan_ex(moe_net* n, const moe_plan* pl, const void* img, int img_dty
         for (int t0 = 0; t0 < nt; t0 += per) {
             const int cnt = std::min(per, nt - t0);
             const long long slot = (long long)(d->group_first[gi] + t0) * C;
-            rc = forward_dev(*n, img, img_dtype, cnt * C, g.th, g.tw, 0, sH, sW, d->x_off + slot, pool, MOE_F32, d->y_off + slot, s, d->y_mult8);
+            rc = forward_dev(*n, FwdIO{img, img_dtype, 0, sH, sW, d->x_off + slot, pool, MOE_F32, d->y_off + slot}, cnt * C, g.th, g.tw, s, d->y_mult8, own_ctx(*n, &n->set));
             if (rc) return rc;
         }
     }
@@ -449,7 +449,7 @@ int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img
         for (int t0 = 0; t0 < ntl; t0 += per) {
             const int cnt = std::min(per, ntl - t0);
             const long long slot = (long long)(d->group_first[gi] + t0) * C;
-            int rc = forward_dev(*n, imgs, img_dtype, cnt * C, g.th, g.tw, 0, sH, sW, d->x_off + slot, dst, MOE_F32, d->y_off + slot, s, d->y_mult8);
+            int rc = forward_dev(*n, FwdIO{imgs, img_dtype, 0, sH, sW, d->x_off + slot, dst, MOE_F32, d->y_off + slot}, cnt * C, g.th, g.tw, s, d->y_mult8, own_ctx(*n, &n->set));
             if (rc) return rc;
         }
     }

@@ -241,10 +241,8 @@ static float scalar_of(const moe_net& n, const std::string& name) { return n.get
 
 void moe::drop_lut(moe_net& n)
 {
-    if (n.lut || n.lut_in) (void)hipDeviceSynchronize();      // (a forward reading the table may be in flight; rare: weights or options changed)
-    if (n.lut) (void)hipFree(n.lut);
-    if (n.lut_in) (void)hipFree(n.lut_in);
-    n.lut = nullptr; n.lut_in = nullptr; n.lut_state = 0;
+    if (n.lut) { (void)hipDeviceSynchronize(); (void)hipFree(n.lut); }      // (a forward reading the table may be in flight; rare: weights or options changed)
+    n.lut = nullptr; n.lut_state = 0;
 }
 
 namespace {
@@ -514,18 +512,9 @@ void moe_net_destroy(moe_net* n)
     if (!n) return;
     drop_lut(*n);
     if (n->blob) (void)hipFree(n->blob);
-    if (n->ws) (void)hipFree(n->ws);
-    for (auto& t : n->taps) if (t.second.dev) (void)hipFree(t.second.dev);
-    for (auto& ev : n->prof_ev) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
     pipe_destroy(*n);
-    if (n->side) (void)hipStreamDestroy(n->side);
-    if (n->ev_fork) (void)hipEventDestroy(n->ev_fork);
-    if (n->ev_join) (void)hipEventDestroy(n->ev_join);
-    for (auto& sl : n->off_ring) {
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.dev) (void)hipFree(sl.dev);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
+    free_set(n->set);
+    free_records(n->rt);
     delete n;
 }
 
@@ -603,22 +592,11 @@ int moe_net_finalize(moe_net* n, int device, int precision)
         // the net moves to another device: its streams, events and workspace belong to the old one (the side stream of small launch sets was created once and
         // would have been used on the new device's forwards); the weight blob is rebuilt below
         (void)hipSetDevice(n->device);
+        (void)hipDeviceSynchronize();
         pipe_destroy(*n);
-        if (n->side) { (void)hipStreamSynchronize(n->side); (void)hipStreamDestroy(n->side); n->side = nullptr; }
-        if (n->ev_fork) { (void)hipEventDestroy(n->ev_fork); n->ev_fork = nullptr; }
-        if (n->ev_join) { (void)hipEventDestroy(n->ev_join); n->ev_join = nullptr; }
-        if (n->ws) { (void)hipDeviceSynchronize(); (void)hipFree(n->ws); n->ws = nullptr; n->ws_bytes = 0; }
+        free_set(n->set);
+        free_records(n->rt);
         if (n->blob) { (void)hipFree(n->blob); n->blob = nullptr; n->blob_bytes = 0; }
-        for (auto& ev : n->prof_ev) { (void)hipEventDestroy(ev.e0); (void)hipEventDestroy(ev.e1); }
-        n->prof_ev.clear(); n->prof_used = 0;
-        for (auto& sl : n->off_ring) {
-            if (sl.host) (void)hipHostFree(sl.host);
-            if (sl.dev) (void)hipFree(sl.dev);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            sl = moe_net::OffSlot{};
-        }
-        for (auto& t : n->taps) if (t.second.dev) (void)hipFree(t.second.dev);
-        n->taps.clear();
         n->calib_valid = false;      // (measured on the other device: the arithmetic is the same, but the rule is one measurement per checkpoint AND device)
     }
     HIP_TRY(hipSetDevice(device));

@@ -1534,6 +1534,47 @@ def test_consecutive_forwards_on_slices_of_one_image_overlap_and_keep_their_bits
         assert torch.equal(got, want_bt)
 
 
+def test_overlapped_forwards_keep_their_bits_under_every_split_of_the_workgroups(dev):
+    """The group arithmetic of a forward that runs ahead of the caller's stream: its persistent workgroups per launch are half of the chip or option overlap_groups (clamped
+    to 16 .. all), and when it forks its U branch as well (overlap_fork) that share is split again between the side stream (branch_groups, or 5/16 of it) and the trunk +
+    R branch.  Every kernel's result is independent of its workgroup count, so each tile of the loop must come out with the bits of a plain call on one stream -- under
+    the default split, under both options at once and at the floor of the clamp -- and a forward must leave the net as it found it: the next plain call and the
+    workspace a shape needs are what they were before the bursts."""
+    from moephoto_amd import _lib
+    defaults = (('overlap_calls', 1), ('overlap_fork', 0), ('overlap_groups', 0), ('branch_groups', 0), ('branch_streams', 1))
+    m = module_for('a4', 'auto')
+    img = torch.from_numpy(gd.noise_image(78, (3, 136, 200))).to(dev).half().unsqueeze(1)
+    tiles = [(0, 64, 0, 96), (40, 104, 72, 168), (72, 136, 104, 200), (0, 8, 0, 16), (0, 64, 0, 96)]
+    try:
+        m.set_option('overlap_calls', 0).set_option('branch_streams', 0)
+        want = [m(img[..., t:b, l:r])[-1].clone() for (t, b, l, r) in tiles]
+        torch.cuda.synchronize()
+        ws = _lib.check(_lib.lib().moe_net_workspace_bytes(m._h, 1, 64, 96))
+        m.set_option('overlap_calls', 1).set_option('branch_streams', 1)
+        for setting in ((('overlap_fork', 1),), (('overlap_fork', 1), ('overlap_groups', 64), ('branch_groups', 16)), (('overlap_fork', 0), ('overlap_groups', 16))):
+            for k, v in setting:
+                m.set_option(k, v)
+            acc, flags = [], []
+            for rep in range(3):                                          # one burst: nothing synchronises in between
+                for (t, b, l, r) in tiles:
+                    y = m(img[..., t:b, l:r])[-1]
+                    flags.append(m._last_flag)
+                    acc.append(y * 1.0)                                   # consumed on the caller's stream at once; y's memory is reused by the next calls
+                    del y
+            for i, g in enumerate(acc):
+                w = want[i % len(tiles)]
+                assert torch.equal(g, w), (setting, i, float((g.float() - w.float()).abs().max()))
+            assert flags[1:] == [_lib.FWD_INPUT_SINCE_PREV] * (len(flags) - 1), (setting, flags)
+            for k, v in defaults:
+                m.set_option(k, v)
+        t, b, l, r = tiles[0]
+        assert torch.equal(m(img[..., t:b, l:r])[-1], want[0])
+        assert _lib.check(_lib.lib().moe_net_workspace_bytes(m._h, 1, 64, 96)) == ws
+    finally:
+        for k, v in defaults:
+            m.set_option(k, v)
+
+
 def test_forward_takes_part_in_a_hip_graph_capture(dev):
     """A forward is plain stream work: captured into a hipGraph (torch.cuda.CUDAGraph) and replayed on new input data it gives the eager bits -- with the U branch's fork / join
     as event edges inside the capture (branch_streams) and without; the overlap path of moe_net_forward_ex stands aside while its stream captures.  (tools/graph_probe.py:
