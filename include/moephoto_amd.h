@@ -17,6 +17,7 @@
  *   moe_stitch            the blend + slice-assign part of doCrop (python/imageProcess.py:120-131,167-170)
  *   moe_run_plan          doCrop as a whole (python/imageProcess.py:157-172): tile gather -> net -> stitch,
  *                         device resident, batched over same-shaped tiles
+ *   moe_run_plan_ens      the SR self-ensemble around doCrop (python/imageProcess.py:563-572, runSR.py:26): moe_sym_pad / moe_sym_fold are its two passes
  *   moe_to_float/_output  toTorch / toOutput (python/imageProcess.py:245-263)
  *
  * All functions return 0 on success or a negative MOE_E* code; moe_last_error() returns a
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MOE_ABI_VERSION 4      /* 4: moe_net_forward_ex / MOE_FWD_INPUT_SINCE_PREV (round 6); 3: moe_net_calibrate / moe_net_exact_blocks, MOE_PREC_AUTO measures the checkpoint at finalize, moe_blend_tile (round 5); 2: MOE_PREC_AUTO, moe_net_resolved_precision, moe_plan_rows / moe_stitch_band, moe_plan_seams / moe_wire_* (round 4); 1 also lacked a bump for moe_net_set_option / moe_device_info / moe_stitch_dev */
+#define MOE_ABI_VERSION 4      /* 4: moe_net_forward_ex / MOE_FWD_INPUT_SINCE_PREV (round 6); still 4 with moe_sym_pad / moe_sym_fold / moe_run_plan_ens: additions only, every earlier entry point is unchanged, so a caller built against the earlier 4 runs as before (a caller of the new ones looks the symbols up); 3: moe_net_calibrate / moe_net_exact_blocks, MOE_PREC_AUTO measures the checkpoint at finalize, moe_blend_tile (round 5); 2: MOE_PREC_AUTO, moe_net_resolved_precision, moe_plan_rows / moe_stitch_band, moe_plan_seams / moe_wire_* (round 4); 1 also lacked a bump for moe_net_set_option / moe_device_info / moe_stitch_dev */
 
 /* error codes */
 #define MOE_OK 0
@@ -280,6 +281,33 @@ int moe_run_plan_tiles(moe_net* net, const moe_plan* plan, const void* imgs, int
  * tile k = C contiguous planes of its HR extent, tiles in raster order) */
 int64_t moe_plan_pool_elems(const moe_plan* plan, int C);
 int moe_plan_tile_offsets(const moe_plan* plan, int C, int64_t* off);
+
+/* ---- self-ensemble ------------------------------------------------------------------------------ */
+/* The reference's ensemble (python/imageProcess.py:563-572) with runSR.sr's average (python/runSR.py:26):
+ *     v = doCrop(opt, x);  for i < n: v = v + transInv[i](doCrop(opt, trans[i](x)));  v / (n + 1)
+ * Symmetry index sym = 0..6 follows the `trans` list (python/imageProcess.py:563-569): transpose, flip, flip2, flip.transpose, transpose.flip,
+ * transpose.flip.transpose, flip2.transpose ("a.b" applies a first; flip reverses the width, flip2 width and height).
+ *
+ * moe_sym_pad: dst = padImage(trans[sym](src)) in one pass -- trans[i](x) (python/imageProcess.py:570) and the right / bottom padding doCrop applies to its input
+ * (getPad, python/imageProcess.py:47-56, 160: per axis a reflection with the edge not repeated, up to len - 1 samples, then zeros).  src: C planes of H x W, element
+ * (c,i,j) at src + c*sC + i*sH + j*sW (strides in elements); dst: C contiguous planes of Hp x Wp, Hp >= Ht and Wp >= Wt with (Ht, Wt) = (W, H) for the symmetries
+ * that transpose (0, 3, 4, 6) and (H, W) otherwise; Hp == Ht and Wp == Wt: a pure transform.  Values are copied, never converted (dtype MOE_F32 / MOE_F16). */
+int moe_sym_pad(const void* src, int dtype, int C, int H, int W, int64_t sC, int64_t sH, int64_t sW,
+                int sym, void* dst, int Hp, int Wp, int device, void* stream);
+/* moe_sym_fold: acc <- acc + transInv[sym](t) in place -- one step of `v + transInv[i](..)` (python/imageProcess.py:571).  acc: C contiguous planes of H x W;
+ * t: C contiguous planes of Ht x Wt, the canvas doCrop returned for the transformed image; both of `dtype`.  Each element is formed as torch forms `v + view` in that
+ * dtype: operands widened to fp32, added once, rounded once.  final_div = n + 1 > 1 also applies the closing `/ (n + 1)` of python/runSR.py:26 to the freshly rounded
+ * sum, with the bits torch produces for tensor / python_int in that dtype; 0 or 1: no division. */
+int moe_sym_fold(void* acc, const void* t, int dtype, int C, int H, int W, int sym, int final_div,
+                 int device, void* stream);
+/* The whole of sr(opt)(x) for ensemble = n_sym (0..7; python/runSR.py:26 around python/imageProcess.py:563-572) on the device: img is the UNPADDED (C, H, W) image with
+ * element strides, plan the plan of (C, H, W), plan_t the plan of (C, W, H) (may be NULL for n_sym == 0 only: symmetry 0 transposes), out = (C, out_h, out_w) of plan.
+ * Pads with the identity and runs moe_run_plan into out; then per symmetry: pad, moe_run_plan with the matching plan into a scratch canvas, fold into out, the last
+ * fold dividing by n_sym + 1 (n_sym == 0: nothing is divided).  The two scratch buffers belong to the net and only grow (a growth waits for `stream`, as the tile pool's
+ * does); otherwise everything is asynchronous on `stream`.  Plans whose output shapes are not each other's transpose are refused.  The caller's current device is restored. */
+int moe_run_plan_ens(moe_net* net, const moe_plan* plan, const moe_plan* plan_t, int n_sym,
+                     const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     void* out, int out_dtype, int max_tiles_per_batch, void* stream);
 
 /* ---- image I/O edges ---------------------------------------------------------------------------- */
 /* src: H x W x C interleaved MOE_U8 (v/255) or MOE_U16 (v/2^bits); dst: C planes H x W, MOE_F32/MOE_F16 */

@@ -19,6 +19,7 @@ class Config(object):
         self.maxGraphicMemoryUsage = 0
         self.modelRoot = '.'        # directory that holds ./model/<name>/model_new.pth
         self.tilesPerBatch = 0      # 0: engine default
+        self.ensembleOnDevice = True   # SR self-ensemble: symmetries, sums and average as engine passes (moe_run_plan_ens); False: the torch expressions (same bits)
 
     def getConfig(self):
         g = lambda v: 0 if v == 'auto' else int(v)

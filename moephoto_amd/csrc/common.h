@@ -459,6 +459,20 @@ struct BlendTileArgs {
 };
 void launch_blend_tile(const BlendTileArgs& a, bool f16, hipStream_t s);
 
+// sym.hip: the self-ensemble's passes around doCrop (moe_sym_pad / moe_sym_fold) as ONE index map.  dst: C contiguous planes of Hd x Wd.  A destination row i
+// shows sample mapR(i) of an axis of nR samples -- i < nR: itself; then the reflection nR - 2, nR - 3, .. (at most nR - 1 of them); then zeros -- reversed when flipR;
+// columns likewise with (nC, flipC).  The source element is src[c sC + mapR(i) sH + mapC(j) sW], or with tr src[c sC + mapC(j) sH + mapR(i) sW] (elements).
+// fold: dst <- dst + that (and, with div, times inv) in the dtype; else dst <- that.
+struct SymArgs {
+    const void* src; void* dst;
+    long long sC, sH, sW;
+    int C, Hd, Wd;
+    int nR, nC, flipR, flipC;
+    int src_vec;                                     // set by launch_sym: source rows may be read as 16-byte vectors
+    int div; float inv;                              // fold: multiply the rounded sum by inv = 1 / divisor (fp32)
+};
+void launch_sym(SymArgs a, bool f16, bool fold, bool tr, hipStream_t s);
+
 // One record of the inter-rank wire format (moe_wire_pack / moe_wire_unpack; the public moe_wire_rec has the same layout): a tile (or strip) of C planes of
 // th x tw fp32 values <-> [fp16 image of all values | fp32 seam rows | fp32 seam columns], offsets in 4-byte words.
 struct WireRec {

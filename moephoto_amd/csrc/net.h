@@ -202,6 +202,9 @@ struct moe_net {
     bool pipe_prev_valid = false;
     hipStream_t pipe_last_stream = nullptr;
     moe::NetRuntime rt;
+    // moe_run_plan_ens: the padded transformed image and the canvas of one symmetry's doCrop (device, grow-only like the workspace)
+    void* ens_pad = nullptr; size_t ens_pad_bytes = 0;
+    void* ens_canvas = nullptr; size_t ens_canvas_bytes = 0;
 
     const moe::Param* get(const std::string& n) const
     {
@@ -388,6 +391,8 @@ int forward_dev(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s,
 void free_set(StreamSet& set);      // (synchronizes its side stream first)
 void pipe_destroy(moe_net& n);
 void free_records(NetRuntime& rt);
+// plan_run.cpp
+void free_ens_scratch(moe_net& n);
 // weights.cpp
 int build_device_weights(moe_net& n, int precision);
 void drop_lut(moe_net& n);

@@ -479,6 +479,151 @@ int moe_run_plan(moe_net* n, const moe_plan* pl, const void* img, int img_dtype,
     return moe_run_plan_ex(n, pl, img, img_dtype, sC, sH, sW, out, out_dtype, max_tiles, nullptr, 0, 1, 1, stream);
 }
 
+// ---- self-ensemble (python/imageProcess.py:563-572, runSR.py:26) ------------------------------------------
+// symmetry s = 0..6 in the order of the reference's `trans` list as (transpose first, flip width, flip height); -1 = the identity
+struct Sym { int t, fh, fv; };
+static Sym sym_of(int s)
+{
+    static const Sym tab[7] = {{1, 0, 0}, {0, 1, 0}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}, {0, 0, 1}, {1, 1, 1}};
+    return s < 0 ? Sym{0, 0, 0} : tab[s];
+}
+
+static int sym_launched(const char* who)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MOE_EHIP, "%s launch failed: %s", who, hipGetErrorString(e));
+    return MOE_OK;
+}
+
+// dst (C, Hp, Wp) = padImage(trans_s(src)); src = (C, H, W) with element strides
+static int sym_pad(const void* src, bool f16, int C, int H, int W, int64_t sC, int64_t sH, int64_t sW, int s, void* dst, int Hp, int Wp, hipStream_t st)
+{
+    const Sym y = sym_of(s);
+    SymArgs a{};
+    a.src = src; a.dst = dst; a.sC = sC; a.sH = sH; a.sW = sW; a.C = C; a.Hd = Hp; a.Wd = Wp;
+    a.nR = y.t ? W : H; a.nC = y.t ? H : W; a.flipR = y.fv; a.flipC = y.fh;
+    launch_sym(a, f16, false, y.t != 0, st);
+    return sym_launched("moe_sym_pad");
+}
+
+// acc (C, H, W) += transInv_s(t); t = (C, Ht, Wt) contiguous, the canvas of the transformed image
+static int sym_fold(void* acc, const void* t, bool f16, int C, int H, int W, int s, int final_div, hipStream_t st)
+{
+    const Sym y = sym_of(s);
+    const int Wt = y.t ? H : W;
+    SymArgs a{};
+    a.src = t; a.dst = acc; a.sC = (long long)H * W; a.sH = Wt; a.sW = 1; a.C = C; a.Hd = H; a.Wd = W;
+    a.nR = H; a.nC = W;
+    a.flipR = y.t ? y.fh : y.fv; a.flipC = y.t ? y.fv : y.fh;       // (transposed, acc's rows run along t's columns: the flip of t's width reverses them)
+    a.div = final_div > 1; a.inv = 1.0f / (float)(final_div > 1 ? final_div : 1);
+    launch_sym(a, f16, true, y.t != 0, st);
+    return sym_launched("moe_sym_fold");
+}
+
+static bool sym_dtype(int dtype) { return dtype == MOE_F32 || dtype == MOE_F16; }
+
+int moe_sym_pad(const void* src, int dtype, int C, int H, int W, int64_t sC, int64_t sH, int64_t sW, int sym, void* dst, int Hp, int Wp, int device, void* stream)
+{
+    if (!src || !dst) return fail(MOE_EINVAL, "moe_sym_pad: NULL argument");
+    if (!sym_dtype(dtype)) return fail(MOE_EINVAL, "moe_sym_pad: dtype must be MOE_F32 or MOE_F16");
+    if (sym < 0 || sym > 6) return fail(MOE_EINVAL, "moe_sym_pad: sym %d is not one of the seven symmetries 0..6", sym);
+    if (C < 1 || H < 1 || W < 1) return fail(MOE_EINVAL, "moe_sym_pad: size %d x %d x %d must be positive", C, H, W);
+    const Sym y = sym_of(sym);
+    const int Ht = y.t ? W : H, Wt = y.t ? H : W;
+    if (Hp < Ht || Wp < Wt) return fail(MOE_EINVAL, "moe_sym_pad: padded size %d x %d is smaller than the transformed image %d x %d", Hp, Wp, Ht, Wt);
+    HIP_TRY(hipSetDevice(device));
+    return sym_pad(src, dtype == MOE_F16, C, H, W, sC, sH, sW, sym, dst, Hp, Wp, (hipStream_t)stream);
+}
+
+int moe_sym_fold(void* acc, const void* t, int dtype, int C, int H, int W, int sym, int final_div, int device, void* stream)
+{
+    if (!acc || !t) return fail(MOE_EINVAL, "moe_sym_fold: NULL argument");
+    if (!sym_dtype(dtype)) return fail(MOE_EINVAL, "moe_sym_fold: dtype must be MOE_F32 or MOE_F16");
+    if (sym < 0 || sym > 6) return fail(MOE_EINVAL, "moe_sym_fold: sym %d is not one of the seven symmetries 0..6", sym);
+    if (C < 1 || H < 1 || W < 1) return fail(MOE_EINVAL, "moe_sym_fold: size %d x %d x %d must be positive", C, H, W);
+    if (final_div < 0) return fail(MOE_EINVAL, "moe_sym_fold: final_div %d is negative (0 or 1: no division)", final_div);
+    HIP_TRY(hipSetDevice(device));
+    return sym_fold(acc, t, dtype == MOE_F16, C, H, W, sym, final_div, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+void moe::free_ens_scratch(moe_net& n)
+{
+    if (n.ens_pad) (void)hipFree(n.ens_pad);
+    if (n.ens_canvas) (void)hipFree(n.ens_canvas);
+    n.ens_pad = n.ens_canvas = nullptr;
+    n.ens_pad_bytes = n.ens_canvas_bytes = 0;
+}
+
+// grow-only, like the workspace: work enqueued on `s` may still read the old block
+static int ens_grow(void*& buf, size_t& have, size_t need, hipStream_t s, const char* what)
+{
+    if (need <= have) return MOE_OK;
+    if (buf) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(buf)); buf = nullptr; have = 0; }
+    if (hipMalloc(&buf, need) != hipSuccess) { (void)hipGetLastError(); buf = nullptr; return fail(MOE_ENOMEM, "moe_run_plan_ens: %s of %zu bytes does not fit", what, need); }
+    have = need;
+    return MOE_OK;
+}
+
+static int run_plan_ens(moe_net* n, const moe_plan* pl, const moe_plan* pl_t, int n_sym, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                        void* out, int out_dtype, int max_tiles, hipStream_t s)
+{
+    const Plan& p = pl->p;
+    const bool f16_in = img_dtype == MOE_F16, f16_out = out_dtype == MOE_F16;
+    const size_t es_in = f16_in ? 2 : 4, es_out = f16_out ? 2 : 4;
+    auto padded = [](const Plan& q, int& hp, int& wp) { hp = std::max(q.H, q.pad_h_to); wp = std::max(q.W, q.pad_w_to); };
+    int hp, wp, hpt = 0, wpt = 0;
+    padded(p, hp, wp);
+    size_t pad_need = (size_t)p.C * hp * wp * es_in, canvas_need = 0;
+    if (n_sym > 0) {
+        canvas_need = (size_t)p.C * p.out_h * p.out_w * es_out;
+        padded(pl_t->p, hpt, wpt);
+        pad_need = std::max(pad_need, (size_t)p.C * hpt * wpt * es_in);
+    }
+    int rc = ens_grow(n->ens_pad, n->ens_pad_bytes, pad_need, s, "the padded image");
+    if (!rc && canvas_need) rc = ens_grow(n->ens_canvas, n->ens_canvas_bytes, canvas_need, s, "a symmetry's canvas");
+    if (rc) return rc;
+    // v = doCrop(x)
+    rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, -1, n->ens_pad, hp, wp, s);
+    if (!rc) rc = moe_run_plan(n, pl, n->ens_pad, img_dtype, (int64_t)hp * wp, wp, 1, out, out_dtype, max_tiles, s);
+    // v = v + transInv[i](doCrop(trans[i](x))), the closing / (n + 1) inside the last fold
+    for (int i = 0; i < n_sym && !rc; ++i) {
+        const bool t = sym_of(i).t != 0;
+        const int h = t ? hpt : hp, w = t ? wpt : wp;
+        rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, i, n->ens_pad, h, w, s);
+        if (!rc) rc = moe_run_plan(n, t ? pl_t : pl, n->ens_pad, img_dtype, (int64_t)h * w, w, 1, n->ens_canvas, out_dtype, max_tiles, s);
+        if (!rc) rc = sym_fold(out, n->ens_canvas, f16_out, p.C, p.out_h, p.out_w, i, i == n_sym - 1 ? n_sym + 1 : 0, s);
+    }
+    return rc;
+}
+
+extern "C" {
+
+int moe_run_plan_ens(moe_net* n, const moe_plan* pl, const moe_plan* pl_t, int n_sym, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     void* out, int out_dtype, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img || !out) return fail(MOE_EINVAL, "moe_run_plan_ens: NULL argument");
+    if (n_sym < 0 || n_sym > 7) return fail(MOE_EINVAL, "moe_run_plan_ens: n_sym %d is not in 0..7", n_sym);
+    if (!sym_dtype(img_dtype) || !sym_dtype(out_dtype)) return fail(MOE_EINVAL, "moe_run_plan_ens: dtype must be MOE_F32 or MOE_F16");
+    const Plan& p = pl->p;
+    if (n_sym > 0) {       // (symmetry 0 is the transpose: every ensemble needs the transposed shape's plan)
+        if (!pl_t) return fail(MOE_EINVAL, "moe_run_plan_ens: plan_t is NULL (n_sym %d needs the plan of the transposed shape)", n_sym);
+        const Plan& q = pl_t->p;
+        if (q.C != p.C || q.H != p.W || q.W != p.H || q.sc != p.sc)
+            return fail(MOE_EINVAL, "moe_run_plan_ens: plan_t is for %d x %d x %d (scale %d), not the transpose of %d x %d x %d (scale %d)", q.C, q.H, q.W, q.sc, p.C, p.H, p.W, p.sc);
+        if (q.out_h != p.out_w || q.out_w != p.out_h)
+            return fail(MOE_EINVAL, "moe_run_plan_ens: the two plans disagree on the output shape (%d x %d against %d x %d transposed)", p.out_h, p.out_w, q.out_h, q.out_w);
+    }
+    if (!n->finalized) return fail(MOE_ESTATE, "moe_run_plan_ens: net is not finalized");
+    int prev = -1;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(n->device));
+    const int rc = run_plan_ens(n, pl, pl_t, n_sym, img, img_dtype, sC, sH, sW, out, out_dtype, max_tiles, (hipStream_t)stream);
+    if (prev >= 0 && prev != n->device) (void)hipSetDevice(prev);      // (the scratch is allocated on the net's device; the caller's current device is as it was)
+    return rc;
+}
+
 // ---- image edges ---------------------------------------------------------------------------------------
 int moe_to_float(const void* src, int src_dtype, int bits, int H, int W, int C, void* dst, int dst_dtype, int device, void* stream)
 {

@@ -515,6 +515,7 @@ void moe_net_destroy(moe_net* n)
     pipe_destroy(*n);
     free_set(n->set);
     free_records(n->rt);
+    free_ens_scratch(*n);
     delete n;
 }
 
@@ -596,6 +597,7 @@ int moe_net_finalize(moe_net* n, int device, int precision)
         pipe_destroy(*n);
         free_set(n->set);
         free_records(n->rt);
+        free_ens_scratch(*n);
         if (n->blob) { (void)hipFree(n->blob); n->blob = nullptr; n->blob_bytes = 0; }
         n->calib_valid = false;      // (measured on the other device: the arithmetic is the same, but the rule is one measurement per checkpoint AND device)
     }

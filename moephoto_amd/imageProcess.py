@@ -6,7 +6,7 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   Option, initModel, getStateDict      python/imageProcess.py:304-334, 379-395
   prepare / getAnchors / TilePlan      :19-35, 73-118   -> C planner (moe_plan_create)
   prepareOpt, doCrop                   :133-172         -> moe_run_plan (tile gather, net, stitch on device)
-  ensemble, trans/transInv             :563-572
+  ensemble, trans/transInv             :563-572         -> moe_run_plan_ens (symmetry + pad, doCrop, fold + average on device)
   RGBFilter, strengthOp, alpha helpers :350-377, 562
   toTorch / toFloat / toOutput         :238-263         -> moe_to_float / moe_to_output kernels
   readFile / writeFile                 :265-302         (PIL, host)
@@ -402,15 +402,52 @@ trans = [f for f, _ in _SYMMETRIES]
 transInv = [g for _, g in _SYMMETRIES]
 
 
-def ensemble(opt):
+def _ensembleOnDevice(opt, x):
+    """The whole averaged ensemble as one call (moe_run_plan_ens): per symmetry one pass that transforms and pads x, doCrop on the device into a canvas the net owns,
+    and one pass that folds it into the result in place -- the last one dividing by opt.ensemble + 1.  Bit for bit what the torch expressions of `ensemble` give."""
+    if x.dim() != 3:
+        raise ValueError('doCrop expects a (C,H,W) image')
+    model = opt.modelCached
+    if x.dtype not in _DT:
+        x = x.to(config.dtype())
+    C, H, W = x.shape
+    plan = _plan_for(opt, (C, H, W))
+    planT = _plan_for(opt, (C, W, H))          # (symmetry 0 is the transpose: every ensemble needs it)
+    model.to(device=x.device)
+    out = x.new_empty((C, plan.outH, plan.outW))
+    sC, sH, sW = x.stride()
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+
+    def run():
+        _lib.check(_lib.lib().moe_run_plan_ens(model._h, plan._h, planT._h, int(opt.ensemble), x.data_ptr(), _DT[x.dtype], sC, sH, sW,
+                                               out.data_ptr(), _DT[out.dtype], int(config.tilesPerBatch), stream))
+    try:
+        run()
+    except MemoryError:              # (as doCrop: the engine's buffers are hipMalloc'ed beside torch's caching allocator)
+        torch.cuda.empty_cache()
+        run()
+    x.record_stream(torch.cuda.current_stream(x.device))      # the engine reads x asynchronously
+    return out
+
+
+def ensemble(opt, average=False):
     """x -> doCrop(x) + sum_i transInv_i(doCrop(trans_i(x))) for the first opt.ensemble transforms.
-    (The reference keeps a second Option for transposed shapes; here plans are keyed by shape.)"""
+    (The reference keeps a second Option for transposed shapes; here plans are keyed by shape.)
+    average: the result is also divided by opt.ensemble + 1 (runSR.sr; nothing is divided when opt.ensemble is 0).  With config.ensembleOnDevice the transforms,
+    the sums and that division run as the engine's own passes (_ensembleOnDevice: the average is its last fold's, so the plain sum stays with torch); the torch
+    expressions below are the other form of the same bits."""
     def f(x):
         v = doCrop(opt, x)
         for i in range(opt.ensemble):
             v = v + transInv[i](doCrop(opt, trans[i](x)))
         return v
-    return f
+
+    def g(x):
+        if average and opt.ensemble > 0 and config.ensembleOnDevice and isinstance(opt.modelCached, EngineModule) and x.device.type == 'cuda':
+            return _ensembleOnDevice(opt, x)
+        v = f(x)
+        return v / (opt.ensemble + 1) if average and opt.ensemble else v
+    return g
 
 
 # ---- DN wrapper (python/imageProcess.py:336-377, 562) -----------------------------------------------

@@ -33,7 +33,8 @@ def engineRamCoef(model, scale, ref=128):
     return 0.9 / per_px
 
 
-sr = lambda opt: (lambda x: ensemble(opt)(x) / (opt.ensemble + 1)) if opt.ensemble else ensemble(opt)
+# python/runSR.py:26: the ensemble's average; the division is the ensemble's own last step (on the device path: inside its last fold), never a second one here
+sr = lambda opt: ensemble(opt, average=True)
 
 
 def getOpt(optSR):
