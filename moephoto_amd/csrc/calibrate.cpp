@@ -105,7 +105,7 @@ struct CalibSample {
     void give_back_workspace()
     {
         (void)hipStreamSynchronize(s);
-        if (n.set.ws) { (void)hipFree(n.set.ws); n.set.ws = nullptr; n.set.ws_bytes = 0; }
+        n.set.ws.release();
     }
 };
 

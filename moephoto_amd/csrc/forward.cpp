@@ -495,14 +495,9 @@ static int forward_dev_chunk(moe_net& n, const FwdIO& io, int B, int h, int w, h
     if (cur != n.device) HIP_TRY(hipSetDevice(n.device));
     const size_t need = workspace_need(n, ctx, B, h, w);
     StreamSet& set = *ctx.set;
-    if (need > set.ws_bytes) {
-        if (set.ws) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(set.ws)); set.ws = nullptr; set.ws_bytes = 0; }
-        hipError_t e = hipMalloc((void**)&set.ws, need);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(MOE_ENOMEM, "workspace of %zu bytes for %d planes of %dx%d does not fit", need, B, h, w); }
-        set.ws_bytes = need;
-    }
+    if (int rc = set.ws.grow(need, s, "workspace of %zu bytes for %d planes of %dx%d does not fit", need, B, h, w)) return rc;
     const size_t planned = need - 4096;
-    Fwd f = make_fwd(n, ctx, &n.rt, s, B, h, w, Arena{set.ws, 0, planned});
+    Fwd f = make_fwd(n, ctx, &n.rt, s, B, h, w, Arena{(char*)set.ws.p, 0, planned});
     f.y_vec = y_off_mult8 && ((uintptr_t)io.y % 16 == 0);   // every output plane starts 16-byte aligned: wide stores allowed
     int rc = run_forward(n, f, io);
     if (rc) return rc;
@@ -518,7 +513,7 @@ void free_set(StreamSet& set)
 {
     if (set.side) { (void)hipStreamSynchronize(set.side); (void)hipStreamDestroy(set.side); }
     for (hipEvent_t e : {set.ev_fork, set.ev_join}) if (e) (void)hipEventDestroy(e);
-    if (set.ws) (void)hipFree(set.ws);
+    set.ws.release();
     set = StreamSet{};
 }
 

@@ -12,6 +12,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <utility>
 
 namespace moe {
 
@@ -25,6 +28,22 @@ int fail(int code, const char* fmt, ...);      // the message moe_last_error ret
         hipError_t e_ = (expr);                                                                          \
         if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? MOE_ENOMEM : MOE_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// A grow-only device buffer (the forwards' workspace, the plan's tile pool, the ensemble's scratch).  Work already enqueued on `s` may still read the old block:
+// growing synchronises that stream before it frees.  A block that does not fit is MOE_ENOMEM with the caller's own message, and the buffer is empty.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <typename... A> int grow(size_t need, hipStream_t s, const char* does_not_fit, A... a)
+    {
+        if (need <= bytes) return MOE_OK;
+        if (p) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(p)); p = nullptr; bytes = 0; }
+        if (hipMalloc(&p, need) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return fail(MOE_ENOMEM, does_not_fit, a...); }
+        bytes = need;
+        return MOE_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }      // (the caller knows that nothing in flight reads it)
+};
 
 // =====================================================================================================
 // model
@@ -144,7 +163,7 @@ struct NetOptions {
 
 // the device resources one forward at a time runs on (the forward grows / creates them on demand): its workspace, and the second stream of small launch sets (option
 // branch_streams) -- the U branch forks behind the stem and joins in front of the branch sum
-struct StreamSet { char* ws = nullptr; size_t ws_bytes = 0; hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; };
+struct StreamSet { DevBuf ws; hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; };
 // ... with a stream of its own: one of the two sets consecutive small forwards alternate between when the caller declares them independent (option overlap_calls, moe_net_forward_ex)
 struct PipeSet : StreamSet { hipStream_t main = nullptr; hipEvent_t entry = nullptr, done = nullptr; };
 
@@ -203,8 +222,7 @@ struct moe_net {
     hipStream_t pipe_last_stream = nullptr;
     moe::NetRuntime rt;
     // moe_run_plan_ens: the padded transformed image and the canvas of one symmetry's doCrop (device, grow-only like the workspace)
-    void* ens_pad = nullptr; size_t ens_pad_bytes = 0;
-    void* ens_canvas = nullptr; size_t ens_canvas_bytes = 0;
+    moe::DevBuf ens_pad, ens_canvas;
 
     const moe::Param* get(const std::string& n) const
     {
@@ -391,8 +409,7 @@ int forward_dev(moe_net& n, const FwdIO& io, int B, int h, int w, hipStream_t s,
 void free_set(StreamSet& set);      // (synchronizes its side stream first)
 void pipe_destroy(moe_net& n);
 void free_records(NetRuntime& rt);
-// plan_run.cpp
-void free_ens_scratch(moe_net& n);
+inline void free_ens_scratch(moe_net& n) { n.ens_pad.release(); n.ens_canvas.release(); }
 // weights.cpp
 int build_device_weights(moe_net& n, int precision);
 void drop_lut(moe_net& n);

@@ -1,83 +1,230 @@
-// plan_run.cpp -- the device-resident doCrop (tile gather -> net -> stitch: python/imageProcess.py:157-172): the plans' device tables, stitch, the
-// moe_run_plan* runners, the planner's entry points, the inter-rank wire format and the image edges.
+// plan_run.cpp -- the device-resident doCrop (tile gather -> net -> stitch: python/imageProcess.py:157-172).  A plan handle owns the planner's result and, beside it,
+// its device state: TILE TABLES (which planes of which image go where: built by tile_table from an input layout and a (frame, tile) -> destination table, one bounded
+// cache), the stitch tables of a (device, C) and the internal tile pool.  Every moe_run_plan* runner is a destination table + run_sets, the one loop that cuts a
+// table's groups into launch sets; every stitch is stitch().  Also here: the planner's entry points, the inter-rank wire format, the self-ensemble and the image edges.
 #include "net.h"
 
 using namespace moe;
 
-// =====================================================================================================
-// plan device cache + stitch + run
-// =====================================================================================================
-static int plan_device_tables(const Plan& p, int device, int C, int64_t sC, int64_t sH, int64_t sW, int si, int scnt,
-                              PlanDeviceCache** outp)
+static int launched(const char* who)
 {
-    if (scnt < 1) { scnt = 1; si = 0; }
-    for (auto& up : p.dev) {
-        PlanDeviceCache& d = *up;
-        if (d.blob && d.device == device && d.C == C && d.sC == sC && d.sH == sH && d.sW == sW && d.shard_index == si && d.shard_count == scnt) {
-            *outp = &d;
-            return MOE_OK;
-        }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MOE_EHIP, "%s launch failed: %s", who, hipGetErrorString(e));
+    return MOE_OK;
+}
+
+// =====================================================================================================
+// the plan handle's device state
+// =====================================================================================================
+// Which planes go where, for one call's worth of work: per plan group the (frame, tile) pairs the destination table names, in (frame, raster) order, C planes each.
+struct TileTable {
+    int device = -1, n_frames = 0;                         // the key: the input layout and the destination table the device tables were built from
+    int64_t sC = 0, sH = 0, sW = 0, frame_stride = 0;
+    std::vector<int64_t> tile_dst;
+    bool y_mult8 = false;                                  // every y_off entry is a multiple of 8 elements (16-byte aligned output planes)
+    std::vector<int> group_first, group_count;             // per plan group: first slot / number of its pairs
+    void* dev = nullptr;                                   // one allocation: [slot][C] each, the plane's offset in the images / in the destination
+    const long long *x_off = nullptr, *y_off = nullptr;
+};
+
+struct StitchTables {      // what the stitch kernel reads of a plan besides the tiles: a function of (device, C) alone, uploaded once
+    int device = -1, C = 0;
+    void* dev = nullptr;
+    long long* tile_off = nullptr;     // the plan's own pool layout for C planes, raster order
+    int *row_first = nullptr, *row_cnt = nullptr, *col_first = nullptr, *col_cnt = nullptr, *row_tab = nullptr, *col_tab = nullptr;
+    float* ramp = nullptr;
+    std::vector<std::pair<int, int*>> strip_tabs;   // moe_stitch_band: row tables in which one tile row is present as the strip of its blend band
+};
+
+struct UploadedOffsets { int device; std::vector<int64_t> host; void* dev; };   // a caller's pool layout passed to moe_stitch from the host
+
+struct PlanDevice {
+    static constexpr size_t kCached = 16;      // tile tables / uploaded layouts kept; the oldest goes first
+    std::vector<TileTable> tables;
+    std::vector<StitchTables> stitch;          // (a handful: one per device and channel count the plan is stitched with)
+    std::vector<UploadedOffsets> uploaded;
+    DevBuf pool;                               // per-tile fp32 results when the caller passes no pool
+    ~PlanDevice()
+    {
+        for (auto& t : tables) (void)hipFree(t.dev);
+        for (auto& t : stitch) { (void)hipFree(t.dev); for (auto& e : t.strip_tabs) (void)hipFree(e.second); }
+        for (auto& u : uploaded) (void)hipFree(u.dev);
+        pool.release();
     }
-    if (p.dev.size() >= 16) {   // bounded: drop the oldest layout
-        if (p.dev.front()->blob) (void)hipFree(p.dev.front()->blob);
-        for (auto& e : p.dev.front()->strip_tabs) (void)hipFree(e.second);
-        p.dev.erase(p.dev.begin());
+    // Room for one more entry of `tables` or `uploaded`.  The dropped entry's block may still be read by kernels in flight: the runners and the stitch enqueue on the
+    // caller's stream, which is synchronised here, and hipFree itself waits for every other stream of the device -- nothing reads the block once it has returned.
+    template <typename V> static int make_room(V& v, hipStream_t s)
+    {
+        if (v.size() < kCached) return MOE_OK;
+        HIP_TRY(hipStreamSynchronize(s));
+        (void)hipFree(v.front().dev);
+        v.erase(v.begin());
+        return MOE_OK;
     }
-    p.dev.push_back(std::make_unique<PlanDeviceCache>());
-    PlanDeviceCache& d = *p.dev.back();
-    const size_t nt = p.tiles.size();
-    std::vector<long long> xo, yo;
+};
+
+static int upload(const void* host, size_t bytes, void** dev)
+{
+    HIP_TRY(hipMalloc(dev, bytes));
+    const hipError_t e = hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(*dev); *dev = nullptr; }
+    HIP_TRY(e);
+    return MOE_OK;
+}
+
+struct moe_plan { Plan p; mutable PlanDevice dev; };      // (the ABI's runners and stitches take the plan as const: the device state is a cache beside it)
+
+// the tile table of (input layout, destination table): tile_dst[f * n_tiles + k] is where frame f's tile k goes, -1 = not computed by this call
+static int tile_table(const moe_plan& pl, int device, int64_t frame_stride, int64_t sC, int64_t sH, int64_t sW, int n_frames, const int64_t* tile_dst,
+                      hipStream_t s, const TileTable** out)
+{
+    const Plan& p = pl.p;
+    const size_t n = p.tiles.size() * (size_t)n_frames;      // (entries of tile_dst; equal n_frames: equal sizes)
+    for (const TileTable& c : pl.dev.tables)
+        if (c.device == device && c.sC == sC && c.sH == sH && c.sW == sW && c.frame_stride == frame_stride && c.n_frames == n_frames &&
+            std::equal(c.tile_dst.begin(), c.tile_dst.end(), tile_dst)) { *out = &c; return MOE_OK; }
+    int rc = PlanDevice::make_room(pl.dev.tables, s);
+    if (rc) return rc;
+    TileTable d;
+    std::vector<long long> off, yo;      // x_off, then y_off behind it
     int slot = 0;
-    for (const auto& g : p.groups) {
+    for (const auto& g : p.groups) {     // same-shaped tiles of ALL frames share launches
         d.group_first.push_back(slot);
-        int cnt = 0;
-        for (int k : g.tiles) {
-            if (k % scnt != si) continue;
-            const TileRect& t = p.tiles[k];
-            const long long plane = (long long)(g.th * p.sc) * (g.tw * p.sc);
-            for (int c = 0; c < C; ++c) {
-                xo.push_back((long long)c * sC + (long long)t.top * sH + (long long)t.left * sW);
-                yo.push_back(p.tile_off[k] / p.C * C + (long long)c * plane);
+        const long long plane = (long long)(g.th * p.sc) * (g.tw * p.sc);
+        for (int f = 0; f < n_frames; ++f)
+            for (int k : g.tiles) {
+                const long long at = tile_dst[(size_t)f * p.tiles.size() + k];
+                if (at < 0) continue;                                  // not computed by this call
+                const TileRect& t = p.tiles[k];
+                for (int c = 0; c < p.C; ++c) {
+                    off.push_back((long long)f * frame_stride + (long long)c * sC + (long long)t.top * sH + (long long)t.left * sW);
+                    yo.push_back(at + (long long)c * plane);
+                }
+                ++slot;
             }
-            ++slot; ++cnt;
-        }
-        d.group_count.push_back(cnt);
+        d.group_count.push_back(slot - d.group_first.back());
     }
-    if (xo.empty()) { xo.push_back(0); yo.push_back(0); }
+    if (off.empty()) { off.push_back(0); yo.push_back(0); }
     d.y_mult8 = true;
     for (long long v : yo) d.y_mult8 = d.y_mult8 && (v % 8 == 0);
+    off.insert(off.end(), yo.begin(), yo.end());
+    rc = upload(off.data(), off.size() * 8, &d.dev);
+    if (rc) return rc;
+    d.x_off = (const long long*)d.dev; d.y_off = d.x_off + yo.size();
+    d.device = device; d.sC = sC; d.sH = sH; d.sW = sW; d.frame_stride = frame_stride; d.n_frames = n_frames;
+    d.tile_dst.assign(tile_dst, tile_dst + n);
+    pl.dev.tables.push_back(std::move(d));
+    *out = &pl.dev.tables.back();
+    return MOE_OK;
+}
+
+// The launch sets of one table: every group's planes through the net, `max_tiles` tiles' worth of 256^2 pixels at a time, from the image(s) into dst.
+static int run_sets(moe_net& n, const Plan& p, const TileTable& d, const void* img, int img_dtype, int64_t sH, int64_t sW, float* dst, int max_tiles, hipStream_t s)
+{
+    if (max_tiles <= 0) {
+        max_tiles = n.opt.tiles_per_batch > 0 ? n.opt.tiles_per_batch : 32;      // (tiles of 256^2 pixels per launch set: 28.97 / 28.59 / 28.42 / 28.28 / 28.33 ms per 1080p x4 frame with 4 / 8 / 12 / 16 / 24 in round 3: fewer pipeline
+                                                                                   // fills per pixel; round 4's kernels, 16 / 20 / 28: 24.32 / 24.20 / 24.09 -- the 28 full tiles of a 1080p frame as ONE launch set; a tile's bits do not depend on it)
+    }
+    for (size_t gi = 0; gi < p.groups.size(); ++gi) {
+        const auto& g = p.groups[gi];
+        const int nt = d.group_count[gi];
+        if (nt < 1) continue;
+        // bigger batches for small tiles: keep roughly max_tiles * 256^2 pixels per launch
+        const long long px = (long long)g.th * g.tw;
+        const int per = (int)std::max<long long>(1, std::min<long long>(nt, (long long)max_tiles * 65536 / std::max<long long>(px, 1)));
+        for (int t0 = 0; t0 < nt; t0 += per) {
+            const int cnt = std::min(per, nt - t0);
+            const long long slot = (long long)(d.group_first[gi] + t0) * p.C;
+            int rc = forward_dev(n, FwdIO{img, img_dtype, 0, sH, sW, d.x_off + slot, dst, MOE_F32, d.y_off + slot}, cnt * p.C, g.th, g.tw, s, d.y_mult8, own_ctx(n, &n.set));
+            if (rc) return rc;
+        }
+    }
+    return MOE_OK;
+}
+
+static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** out)
+{
+    for (StitchTables& c : pl.dev.stitch)
+        if (c.device == device && c.C == C) { *out = &c; return MOE_OK; }
+    const Plan& p = pl.p;
     // tile_off scaled to C planes (C may differ from the planning shape's channel count, e.g. alpha stripped)
-    std::vector<long long> toff(nt);
-    for (size_t k = 0; k < nt; ++k) toff[k] = p.tile_off[k] / p.C * C;
+    std::vector<long long> toff(p.tiles.size());
+    for (size_t k = 0; k < toff.size(); ++k) toff[k] = p.tile_off[k] / p.C * C;
     std::vector<char> host;
     auto put = [&](const void* src, size_t bytes) { const size_t a = (host.size() + 255) & ~(size_t)255; host.resize(a + bytes); memcpy(host.data() + a, src, bytes); return a; };
-    const size_t o_x = put(xo.data(), xo.size() * 8), o_y = put(yo.data(), yo.size() * 8), o_t = put(toff.data(), toff.size() * 8);
+    const size_t o_t = put(toff.data(), toff.size() * 8);
     const size_t o_rf = put(p.row_first.data(), p.row_first.size() * 4), o_rc = put(p.row_cnt.data(), p.row_cnt.size() * 4);
     const size_t o_cf = put(p.col_first.data(), p.col_first.size() * 4), o_cc = put(p.col_cnt.data(), p.col_cnt.size() * 4);
     const size_t o_rt = put(p.row_tab.data(), p.row_tab.size() * 4), o_ct = put(p.col_tab.data(), p.col_tab.size() * 4);
     const float zero = 0.f;
     const size_t o_rp = put(p.ramp.empty() ? &zero : p.ramp.data(), std::max<size_t>(4, p.ramp.size() * 4));
-    HIP_TRY(hipMalloc(&d.blob, host.size()));
-    HIP_TRY(hipMemcpy(d.blob, host.data(), host.size(), hipMemcpyHostToDevice));
-    char* b = (char*)d.blob;
-    d.x_off = (long long*)(b + o_x); d.y_off = (long long*)(b + o_y); d.tile_off = (long long*)(b + o_t);
+    StitchTables d;
+    int rc = upload(host.data(), host.size(), &d.dev);
+    if (rc) return rc;
+    char* b = (char*)d.dev;
+    d.device = device; d.C = C; d.tile_off = (long long*)(b + o_t);
     d.row_first = (int*)(b + o_rf); d.row_cnt = (int*)(b + o_rc); d.col_first = (int*)(b + o_cf); d.col_cnt = (int*)(b + o_cc);
     d.row_tab = (int*)(b + o_rt); d.col_tab = (int*)(b + o_ct); d.ramp = (float*)(b + o_rp);
-    d.device = device; d.C = C; d.sC = sC; d.sH = sH; d.sW = sW; d.shard_index = si; d.shard_count = scnt;
-    *outp = &d;
+    pl.dev.stitch.push_back(std::move(d));
+    *out = &pl.dev.stitch.back();
     return MOE_OK;
 }
 
-static void fill_stitch(const Plan& p, const PlanDeviceCache& d, StitchArgs& a, const float* tiles, const long long* tile_off, int C, void* out, int out_dtype)
+// The stitch of C planes from `tiles` into `out`.  tile_off: where each tile lies in `tiles` -- NULL = the plan's own pool layout, else a table on the device or
+// (off_on_host: uploaded once per distinct table, then kept on the plan -- e.g. a receive buffer's layout) on the host.  band: NULL = the whole canvas, else
+// {row0, row1, strip}: the rows of tile rows [row0, row1) only, strip != 0 with tile row row1 present as the strips of its blend band.
+static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s)
 {
-    a.tiles = tiles; a.tile_off = tile_off;
-    a.row_first = d.row_first; a.row_cnt = d.row_cnt; a.col_first = d.col_first; a.col_cnt = d.col_cnt;
-    a.row_tab = d.row_tab; a.col_tab = d.col_tab; a.ramp = d.ramp;
+    const Plan& p = pl.p;
+    HIP_TRY(hipSetDevice(device));
+    StitchTables* d = nullptr;
+    int rc = stitch_tables(pl, device, C, &d);
+    if (rc) return rc;
+    const long long* toff = tile_off ? (const long long*)tile_off : d->tile_off;
+    if (tile_off && off_on_host) {
+        const size_t nt = p.tiles.size();
+        toff = nullptr;
+        for (auto& c : pl.dev.uploaded)
+            if (c.device == device && std::equal(c.host.begin(), c.host.end(), tile_off)) { toff = (const long long*)c.dev; break; }
+        if (!toff) {
+            void* up = nullptr;
+            rc = PlanDevice::make_room(pl.dev.uploaded, s);
+            if (!rc) rc = upload(tile_off, nt * 8, &up);
+            if (rc) return rc;
+            pl.dev.uploaded.push_back(UploadedOffsets{device, std::vector<int64_t>(tile_off, tile_off + nt), up});
+            toff = (const long long*)up;
+        }
+    }
+    StitchArgs a{};
+    a.tiles = tiles; a.tile_off = toff;
+    a.row_first = d->row_first; a.row_cnt = d->row_cnt; a.col_first = d->col_first; a.col_cnt = d->col_cnt;
+    a.row_tab = d->row_tab; a.col_tab = d->col_tab; a.ramp = d->ramp;
     a.out = out; a.out_dtype = out_dtype; a.C = C; a.out_h = p.out_h; a.out_w = p.out_w; a.step_w = p.aw.step;
     a.y0 = 0; a.rows = p.out_h; a.row_lo = 0;
+    if (band) {
+        const int row0 = band[0], row1 = band[1], nrow = p.ah.step;
+        a.row_lo = row0;
+        a.y0 = p.row_tab[row0 * 4 + 1];                                  // S(row0): first un-blended row of the band's first tile row (0 for row 0)
+        a.rows = (row1 < nrow ? p.row_tab[row1 * 4 + 1] : p.out_h) - a.y0;
+        if (band[2] && row1 < nrow) {
+            // the band ends with the blend band of tile row row1, rows [first, solid): its tiles are present as STRIPS of exactly those pad_sc rows (C planes of
+            // pad_sc x width each): a row table in which that tile row starts at `first` and is pad_sc high addresses them
+            int* tab = nullptr;
+            for (auto& e : d->strip_tabs) if (e.first == row1) tab = e.second;
+            if (!tab) {
+                std::vector<int> rt(p.row_tab);
+                rt[row1 * 4 + 2] = rt[row1 * 4 + 0];
+                rt[row1 * 4 + 3] = rt[row1 * 4 + 1] - rt[row1 * 4 + 0];
+                rc = upload(rt.data(), rt.size() * 4, (void**)&tab);
+                if (rc) return rc;
+                d->strip_tabs.push_back({row1, tab});
+            }
+            a.row_tab = tab;
+        }
+    }
+    launch_stitch(a, s);
+    return launched("stitch");
 }
-
-struct moe_plan { Plan p; };
 
 extern "C" {
 
@@ -95,12 +242,7 @@ int moe_plan_create(const int64_t shape[3], double ram, double ram_coef, int pad
 
 void moe_plan_destroy(moe_plan* p)
 {
-    if (!p) return;
-    for (auto& d : p->p.dev) { if (d->blob) (void)hipFree(d->blob); for (auto& e : d->strip_tabs) (void)hipFree(e.second); }
-    for (auto& d : p->p.fdev) if (d->blob) (void)hipFree(d->blob);
-    for (auto& c : p->p.custom_off) if (c.dev) (void)hipFree(c.dev);
-    if (p->p.pool) (void)hipFree(p->p.pool);
-    delete p;
+    delete p;      // (~PlanDevice frees the device state)
 }
 
 int moe_plan_info(const moe_plan* p, int64_t info[12])
@@ -173,9 +315,7 @@ static int wire_call(bool pack, float* tiles, void* wire, const moe_wire_rec* re
 {
     if (n < 0 || (n > 0 && (!tiles || !wire || !recs_dev))) return fail(MOE_EINVAL, "moe_wire_%s: bad argument", pack ? "pack" : "unpack");
     launch_wire(pack, tiles, (unsigned*)wire, (const WireRec*)recs_dev, n, max_elems, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "wire kernel launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    return launched("wire kernel");
 }
 
 int moe_wire_pack(const float* tiles_dev, void* wire_dev, const moe_wire_rec* recs_dev, int n, int64_t max_elems, void* stream)
@@ -223,84 +363,23 @@ int moe_plan_tile_offsets(const moe_plan* p, int C, int64_t* off)
 int moe_stitch(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off, int C, void* out, int out_dtype, void* stream)
 {
     if (!p || !tiles_dev || !out || C < 1) return fail(MOE_EINVAL, "moe_stitch: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    PlanDeviceCache* d = nullptr;
-    int rc = plan_device_tables(p->p, device, C, 0, 0, 0, 0, 1, &d);
-    if (rc) return rc;
-    long long* toff = nullptr;
-    if (tile_off) {   // caller-defined pool layout (e.g. the receive buffer of dist.py): uploaded once per distinct table, then cached on the plan
-        const size_t nt = p->p.tiles.size();
-        for (auto& c : p->p.custom_off)
-            if (c.device == device && c.host.size() == nt && std::equal(c.host.begin(), c.host.end(), tile_off)) { toff = c.dev; break; }
-        if (!toff) {
-            if (p->p.custom_off.size() >= 16) {
-                HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-                (void)hipFree(p->p.custom_off.front().dev);
-                p->p.custom_off.erase(p->p.custom_off.begin());
-            }
-            HIP_TRY(hipMalloc((void**)&toff, nt * 8));
-            HIP_TRY(hipMemcpy(toff, tile_off, nt * 8, hipMemcpyHostToDevice));
-            p->p.custom_off.push_back(CustomOffsets{device, std::vector<long long>(tile_off, tile_off + nt), toff});
-        }
-    }
-    StitchArgs a{};
-    fill_stitch(p->p, *d, a, tiles_dev, toff ? toff : d->tile_off, C, out, out_dtype);
-    launch_stitch(a, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "stitch launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    return stitch(*p, device, tiles_dev, tile_off, true, C, out, out_dtype, nullptr, (hipStream_t)stream);
 }
 
 int moe_stitch_dev(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, void* out, int out_dtype, void* stream)
 {
     if (!p || !tiles_dev || !tile_off_dev || !out || C < 1) return fail(MOE_EINVAL, "moe_stitch_dev: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    PlanDeviceCache* d = nullptr;
-    int rc = plan_device_tables(p->p, device, C, 0, 0, 0, 0, 1, &d);
-    if (rc) return rc;
-    StitchArgs a{};
-    fill_stitch(p->p, *d, a, tiles_dev, (const long long*)tile_off_dev, C, out, out_dtype);
-    launch_stitch(a, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "stitch launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, C, out, out_dtype, nullptr, (hipStream_t)stream);
 }
 
 int moe_stitch_band(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, void* out, int out_dtype,
                     int row0, int row1, int strip, void* stream)
 {
     if (!p || !tiles_dev || !tile_off_dev || !out || C < 1) return fail(MOE_EINVAL, "moe_stitch_band: bad argument");
-    const Plan& q = p->p;
-    const int nrow = q.ah.step;
+    const int nrow = p->p.ah.step;
     if (row0 < 0 || row1 <= row0 || row1 > nrow) return fail(MOE_EINVAL, "moe_stitch_band: tile rows [%d, %d) of %d", row0, row1, nrow);
-    HIP_TRY(hipSetDevice(device));
-    PlanDeviceCache* d = nullptr;
-    int rc = plan_device_tables(q, device, C, 0, 0, 0, 0, 1, &d);
-    if (rc) return rc;
-    StitchArgs a{};
-    fill_stitch(q, *d, a, tiles_dev, (const long long*)tile_off_dev, C, out, out_dtype);
-    a.row_lo = row0;
-    a.y0 = q.row_tab[row0 * 4 + 1];                                  // S(row0): first un-blended row of the band's first tile row (0 for row 0)
-    a.rows = (row1 < nrow ? q.row_tab[row1 * 4 + 1] : q.out_h) - a.y0;
-    if (strip && row1 < nrow) {
-        // the band ends with the blend band of tile row row1, rows [first, solid): its tiles are present as STRIPS of exactly those pad_sc rows (C planes of
-        // pad_sc x width each): a row table in which that tile row starts at `first` and is pad_sc high addresses them
-        int* tab = nullptr;
-        for (auto& e : d->strip_tabs) if (e.first == row1) tab = e.second;
-        if (!tab) {
-            std::vector<int> rt(q.row_tab);
-            rt[row1 * 4 + 2] = rt[row1 * 4 + 0];
-            rt[row1 * 4 + 3] = rt[row1 * 4 + 1] - rt[row1 * 4 + 0];
-            HIP_TRY(hipMalloc((void**)&tab, rt.size() * 4));
-            HIP_TRY(hipMemcpy(tab, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));
-            d->strip_tabs.push_back({row1, tab});
-        }
-        a.row_tab = tab;
-    }
-    launch_stitch(a, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "stitch launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    const int band[3] = {row0, row1, strip};
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, C, out, out_dtype, band, (hipStream_t)stream);
 }
 
 int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int64_t c_sC, int64_t c_sH, int dtype, int C,
@@ -324,9 +403,7 @@ int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int6
     a.r = r; a.canvas = canvas; a.ramp = ramp; a.r_sC = r_sC; a.r_sH = r_sH; a.c_sC = c_sC; a.c_sH = c_sH;
     a.C = C; a.rh = rh; a.rw = rw; a.top_sc = top_sc; a.left_sc = left_sc;
     launch_blend_tile(a, dtype == MOE_F16, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "blend launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    return launched("blend");
 }
 
 int moe_run_plan_ex(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
@@ -340,45 +417,19 @@ int moe_run_plan_ex(moe_net* n, const moe_plan* pl, const void* img, int img_dty
     if (shard_index < 0 || shard_index >= shard_count) return fail(MOE_EINVAL, "moe_run_plan: shard %d of %d", shard_index, shard_count);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(n->device));
-    const int C = p.C;
-    PlanDeviceCache* d = nullptr;
-    int rc = plan_device_tables(p, n->device, C, sC, sH, sW, shard_index, shard_count, &d);
+    std::vector<int64_t> at(p.tile_off.begin(), p.tile_off.end());      // this shard's tiles into the plan's own pool layout
+    for (size_t k = 0; k < at.size(); ++k) if ((int)(k % shard_count) != shard_index) at[k] = -1;
+    const TileTable* d = nullptr;
+    int rc = tile_table(*pl, n->device, 0, sC, sH, sW, 1, at.data(), s, &d);
     if (rc) return rc;
     if (!pool) {
-        const size_t pool_need = p.pool_elems_per_plane_set;
-        if (pool_need > p.pool_elems) {
-            if (p.pool) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(p.pool)); p.pool = nullptr; p.pool_elems = 0; }
-            if (hipMalloc((void**)&p.pool, pool_need * 4) != hipSuccess) { (void)hipGetLastError(); return fail(MOE_ENOMEM, "tile pool of %zu bytes does not fit", pool_need * 4); }
-            p.pool_elems = pool_need;
-        }
-        pool = p.pool;
+        rc = pl->dev.pool.grow(p.pool_elems_per_plane_set * 4, s, "tile pool of %zu bytes does not fit", p.pool_elems_per_plane_set * 4);
+        if (rc) return rc;
+        pool = (float*)pl->dev.pool.p;
     }
-    if (max_tiles <= 0) {
-        max_tiles = n->opt.tiles_per_batch > 0 ? n->opt.tiles_per_batch : 32;     // (tiles of 256^2 pixels per launch set: 28.97 / 28.59 / 28.42 / 28.28 / 28.33 ms per 1080p x4 frame with 4 / 8 / 12 / 16 / 24 in round 3: fewer pipeline
-                                                                                   // fills per pixel; round 4's kernels, 16 / 20 / 28: 24.32 / 24.20 / 24.09 -- the 28 full tiles of a 1080p frame as ONE launch set; a tile's bits do not depend on it)
-    }
-    for (size_t gi = 0; gi < p.groups.size(); ++gi) {
-        const auto& g = p.groups[gi];
-        const int nt = d->group_count[gi];
-        if (nt < 1) continue;
-        // bigger batches for small tiles: keep roughly max_tiles * 256^2 pixels per launch
-        const long long px = (long long)g.th * g.tw;
-        const int per = (int)std::max<long long>(1, std::min<long long>(nt, (long long)max_tiles * 65536 / std::max<long long>(px, 1)));
-        for (int t0 = 0; t0 < nt; t0 += per) {
-            const int cnt = std::min(per, nt - t0);
-            const long long slot = (long long)(d->group_first[gi] + t0) * C;
-            rc = forward_dev(*n, FwdIO{img, img_dtype, 0, sH, sW, d->x_off + slot, pool, MOE_F32, d->y_off + slot}, cnt * C, g.th, g.tw, s, d->y_mult8, own_ctx(*n, &n->set));
-            if (rc) return rc;
-        }
-    }
-    if (do_stitch) {
-        StitchArgs a{};
-        fill_stitch(p, *d, a, pool, d->tile_off, C, out, out_dtype);
-        launch_stitch(a, s);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(MOE_EHIP, "stitch launch failed: %s", hipGetErrorString(e));
-    }
-    return MOE_OK;
+    rc = run_sets(*n, p, *d, img, img_dtype, sH, sW, pool, max_tiles, s);
+    if (rc || !do_stitch) return rc;
+    return stitch(*pl, n->device, pool, nullptr, false, p.C, out, out_dtype, nullptr, s);
 }
 
 int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,
@@ -391,69 +442,10 @@ int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img
     if (p.sc != n->scale) return fail(MOE_EINVAL, "moe_run_plan_tiles: plan scale %d != net scale %d", p.sc, n->scale);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(n->device));
-    const int C = p.C;
-    const long long nt = (long long)p.tiles.size();
-    FramesDeviceCache* d = nullptr;
-    for (auto& up : p.fdev) {
-        FramesDeviceCache& c = *up;
-        if (c.blob && c.device == n->device && c.C == C && c.sC == sC && c.sH == sH && c.sW == sW && c.frame_stride == frame_stride &&
-            c.n_frames == n_frames && c.tile_dst.size() == (size_t)(nt * n_frames) &&
-            std::equal(c.tile_dst.begin(), c.tile_dst.end(), tile_dst)) { d = &c; break; }
-    }
-    if (!d) {
-        if (p.fdev.size() >= 8) {
-            HIP_TRY(hipStreamSynchronize(s));
-            if (p.fdev.front()->blob) (void)hipFree(p.fdev.front()->blob);
-            p.fdev.erase(p.fdev.begin());
-        }
-        p.fdev.push_back(std::make_unique<FramesDeviceCache>());
-        d = p.fdev.back().get();
-        std::vector<long long> xo, yo;
-        int slot = 0;
-        for (const auto& g : p.groups) {      // same-shaped tiles of ALL frames share launches
-            d->group_first.push_back(slot);
-            int cnt = 0;
-            const long long plane = (long long)(g.th * p.sc) * (g.tw * p.sc);
-            for (int f = 0; f < n_frames; ++f)
-                for (int k : g.tiles) {
-                    const long long at = tile_dst[(long long)f * nt + k];
-                    if (at < 0) continue;                                  // not computed by this call
-                    const TileRect& t = p.tiles[k];
-                    for (int c = 0; c < C; ++c) {
-                        xo.push_back((long long)f * frame_stride + (long long)c * sC + (long long)t.top * sH + (long long)t.left * sW);
-                        yo.push_back(at + (long long)c * plane);
-                    }
-                    ++slot; ++cnt;
-                }
-            d->group_count.push_back(cnt);
-        }
-        if (xo.empty()) { xo.push_back(0); yo.push_back(0); }
-        d->y_mult8 = true;
-        for (long long v : yo) d->y_mult8 = d->y_mult8 && (v % 8 == 0);
-        HIP_TRY(hipMalloc(&d->blob, xo.size() * 16));
-        d->x_off = (long long*)d->blob; d->y_off = d->x_off + xo.size();
-        HIP_TRY(hipMemcpy(d->x_off, xo.data(), xo.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d->y_off, yo.data(), yo.size() * 8, hipMemcpyHostToDevice));
-        d->device = n->device; d->C = C; d->sC = sC; d->sH = sH; d->sW = sW; d->frame_stride = frame_stride;
-        d->n_frames = n_frames; d->tile_dst.assign(tile_dst, tile_dst + nt * n_frames);
-    }
-    if (max_tiles <= 0) {
-        max_tiles = n->opt.tiles_per_batch > 0 ? n->opt.tiles_per_batch : 32;     // (as moe_run_plan_ex)
-    }
-    for (size_t gi = 0; gi < p.groups.size(); ++gi) {
-        const auto& g = p.groups[gi];
-        const int ntl = d->group_count[gi];
-        if (ntl < 1) continue;
-        const long long px = (long long)g.th * g.tw;
-        const int per = (int)std::max<long long>(1, std::min<long long>(ntl, (long long)max_tiles * 65536 / std::max<long long>(px, 1)));
-        for (int t0 = 0; t0 < ntl; t0 += per) {
-            const int cnt = std::min(per, ntl - t0);
-            const long long slot = (long long)(d->group_first[gi] + t0) * C;
-            int rc = forward_dev(*n, FwdIO{imgs, img_dtype, 0, sH, sW, d->x_off + slot, dst, MOE_F32, d->y_off + slot}, cnt * C, g.th, g.tw, s, d->y_mult8, own_ctx(*n, &n->set));
-            if (rc) return rc;
-        }
-    }
-    return MOE_OK;
+    const TileTable* d = nullptr;
+    int rc = tile_table(*pl, n->device, frame_stride, sC, sH, sW, n_frames, tile_dst, s, &d);
+    if (rc) return rc;
+    return run_sets(*n, p, *d, imgs, img_dtype, sH, sW, dst, max_tiles, s);
 }
 
 int moe_run_plan_frames(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,
@@ -488,13 +480,6 @@ static Sym sym_of(int s)
     return s < 0 ? Sym{0, 0, 0} : tab[s];
 }
 
-static int sym_launched(const char* who)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "%s launch failed: %s", who, hipGetErrorString(e));
-    return MOE_OK;
-}
-
 // dst (C, Hp, Wp) = padImage(trans_s(src)); src = (C, H, W) with element strides
 static int sym_pad(const void* src, bool f16, int C, int H, int W, int64_t sC, int64_t sH, int64_t sW, int s, void* dst, int Hp, int Wp, hipStream_t st)
 {
@@ -503,7 +488,7 @@ static int sym_pad(const void* src, bool f16, int C, int H, int W, int64_t sC, i
     a.src = src; a.dst = dst; a.sC = sC; a.sH = sH; a.sW = sW; a.C = C; a.Hd = Hp; a.Wd = Wp;
     a.nR = y.t ? W : H; a.nC = y.t ? H : W; a.flipR = y.fv; a.flipC = y.fh;
     launch_sym(a, f16, false, y.t != 0, st);
-    return sym_launched("moe_sym_pad");
+    return launched("moe_sym_pad");
 }
 
 // acc (C, H, W) += transInv_s(t); t = (C, Ht, Wt) contiguous, the canvas of the transformed image
@@ -517,7 +502,7 @@ static int sym_fold(void* acc, const void* t, bool f16, int C, int H, int W, int
     a.flipR = y.t ? y.fh : y.fv; a.flipC = y.t ? y.fv : y.fh;       // (transposed, acc's rows run along t's columns: the flip of t's width reverses them)
     a.div = final_div > 1; a.inv = 1.0f / (float)(final_div > 1 ? final_div : 1);
     launch_sym(a, f16, true, y.t != 0, st);
-    return sym_launched("moe_sym_fold");
+    return launched("moe_sym_fold");
 }
 
 static bool sym_dtype(int dtype) { return dtype == MOE_F32 || dtype == MOE_F16; }
@@ -548,24 +533,6 @@ int moe_sym_fold(void* acc, const void* t, int dtype, int C, int H, int W, int s
 
 }  // extern "C"
 
-void moe::free_ens_scratch(moe_net& n)
-{
-    if (n.ens_pad) (void)hipFree(n.ens_pad);
-    if (n.ens_canvas) (void)hipFree(n.ens_canvas);
-    n.ens_pad = n.ens_canvas = nullptr;
-    n.ens_pad_bytes = n.ens_canvas_bytes = 0;
-}
-
-// grow-only, like the workspace: work enqueued on `s` may still read the old block
-static int ens_grow(void*& buf, size_t& have, size_t need, hipStream_t s, const char* what)
-{
-    if (need <= have) return MOE_OK;
-    if (buf) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(buf)); buf = nullptr; have = 0; }
-    if (hipMalloc(&buf, need) != hipSuccess) { (void)hipGetLastError(); buf = nullptr; return fail(MOE_ENOMEM, "moe_run_plan_ens: %s of %zu bytes does not fit", what, need); }
-    have = need;
-    return MOE_OK;
-}
-
 static int run_plan_ens(moe_net* n, const moe_plan* pl, const moe_plan* pl_t, int n_sym, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                         void* out, int out_dtype, int max_tiles, hipStream_t s)
 {
@@ -581,19 +548,20 @@ static int run_plan_ens(moe_net* n, const moe_plan* pl, const moe_plan* pl_t, in
         padded(pl_t->p, hpt, wpt);
         pad_need = std::max(pad_need, (size_t)p.C * hpt * wpt * es_in);
     }
-    int rc = ens_grow(n->ens_pad, n->ens_pad_bytes, pad_need, s, "the padded image");
-    if (!rc && canvas_need) rc = ens_grow(n->ens_canvas, n->ens_canvas_bytes, canvas_need, s, "a symmetry's canvas");
+    const char* fits = "moe_run_plan_ens: %s of %zu bytes does not fit";
+    int rc = n->ens_pad.grow(pad_need, s, fits, "the padded image", pad_need);
+    if (!rc && canvas_need) rc = n->ens_canvas.grow(canvas_need, s, fits, "a symmetry's canvas", canvas_need);
     if (rc) return rc;
     // v = doCrop(x)
-    rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, -1, n->ens_pad, hp, wp, s);
-    if (!rc) rc = moe_run_plan(n, pl, n->ens_pad, img_dtype, (int64_t)hp * wp, wp, 1, out, out_dtype, max_tiles, s);
+    rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, -1, n->ens_pad.p, hp, wp, s);
+    if (!rc) rc = moe_run_plan(n, pl, n->ens_pad.p, img_dtype, (int64_t)hp * wp, wp, 1, out, out_dtype, max_tiles, s);
     // v = v + transInv[i](doCrop(trans[i](x))), the closing / (n + 1) inside the last fold
     for (int i = 0; i < n_sym && !rc; ++i) {
         const bool t = sym_of(i).t != 0;
         const int h = t ? hpt : hp, w = t ? wpt : wp;
-        rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, i, n->ens_pad, h, w, s);
-        if (!rc) rc = moe_run_plan(n, t ? pl_t : pl, n->ens_pad, img_dtype, (int64_t)h * w, w, 1, n->ens_canvas, out_dtype, max_tiles, s);
-        if (!rc) rc = sym_fold(out, n->ens_canvas, f16_out, p.C, p.out_h, p.out_w, i, i == n_sym - 1 ? n_sym + 1 : 0, s);
+        rc = sym_pad(img, f16_in, p.C, p.H, p.W, sC, sH, sW, i, n->ens_pad.p, h, w, s);
+        if (!rc) rc = moe_run_plan(n, t ? pl_t : pl, n->ens_pad.p, img_dtype, (int64_t)h * w, w, 1, n->ens_canvas.p, out_dtype, max_tiles, s);
+        if (!rc) rc = sym_fold(out, n->ens_canvas.p, f16_out, p.C, p.out_h, p.out_w, i, i == n_sym - 1 ? n_sym + 1 : 0, s);
     }
     return rc;
 }
@@ -642,9 +610,7 @@ int moe_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h
     if (mode < MOE_RESIZE_NEAREST || mode > MOE_RESIZE_BICUBIC) return fail(MOE_EINVAL, "moe_resize: unknown mode %d", mode);
     HIP_TRY(hipSetDevice(device));
     launch_resize(src, dst, dtype, C, H, W, h, w, mode, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "resize launch failed: %s", hipGetErrorString(e));
-    return MOE_OK;
+    return launched("resize");
 }
 
 int moe_to_output(const void* src, int src_dtype, int H, int W, int C, int bits, void* dst, int dst_dtype, int device, void* stream)

@@ -514,6 +514,141 @@ def test_run_plan_frames_owner_sharding(dev):
                                          ctypes.c_void_p(p1.data_ptr()), pe - 8, 0, 1, 3, stream))      # pool stride too small
 
 
+_runner_case = {}
+
+
+def _plan_runner_case(dev):
+    """The shape of test_run_plan_frames_owner_sharding (a2, 3 x 150 x 200 fp32, cropsize 64: twelve tiles in four groups, ragged edge tiles included), computed
+    once for the runner tests below: the image, its plan, doCrop's canvas, the tile pool in the plan's own layout and the tiles' sizes in that pool."""
+    import ctypes
+    from moephoto_amd import _lib, imageProcess as ip
+    if not _runner_case:
+        opt = _opt_sr('a', 2, 64)
+        x = torch.from_numpy(gd.natural_image(70, (3, 150, 200))).to(dev)
+        plan = ip._plan_for(opt, x.shape)
+        assert plan.padImage(x).shape == x.shape and plan.n_tiles == 12
+        want = ip.doCrop(opt, x)
+        pool = torch.zeros(plan.pool_elems(3), dtype=torch.float32, device=dev)
+        sC, sH, sW = x.stride()
+        _lib.check(_lib.lib().moe_run_plan_ex(opt.modelCached._h, plan._h, x.data_ptr(), _lib.F32, sC, sH, sW, None, _lib.F32, 0,
+                                              ctypes.c_void_p(pool.data_ptr()), 0, 1, 0, torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        sizes = [3 * (t[1] - t[0]) * (t[3] - t[2]) * 4 for t in plan.tiles]
+        _runner_case.update(opt=opt, x=x, plan=plan, want=want, pool=pool, sizes=sizes)
+    c = _runner_case
+    return c['opt'], c['x'], c['plan'], c['want'], c['pool'], c['sizes']
+
+
+def _shuffled_layout(sizes, seed):
+    """Pool offsets of the tiles packed in a shuffled order: (offsets by tile, the order)"""
+    order = [int(k) for k in np.random.RandomState(seed).permutation(len(sizes))]
+    offs, at = [0] * len(sizes), 0
+    for k in order:
+        offs[k] = at
+        at += sizes[k]
+    return offs, tuple(order)
+
+
+def test_run_plan_ex_into_a_pool_equals_run_plan_tiles_with_one_frame(dev):
+    """moe_run_plan_ex into a caller's pool without the stitch is moe_run_plan_tiles with one frame and the plan's own offsets as the destination table; its
+    shard i of n is that table with the other tiles' entries at -1.  The pools are bit-equal."""
+    import ctypes
+    from moephoto_amd import _lib
+    opt, x, plan, _, pool_ref, sizes = _plan_runner_case(dev)
+    L, model = _lib.lib(), opt.modelCached
+    stream = torch.cuda.current_stream().cuda_stream
+    sC, sH, sW = x.stride()
+    off = plan.tile_offsets(3)
+    for si, scnt in ((0, 1), (1, 3)):
+        a = torch.zeros_like(pool_ref)
+        b = torch.zeros_like(pool_ref)
+        _lib.check(L.moe_run_plan_ex(model._h, plan._h, x.data_ptr(), _lib.F32, sC, sH, sW, None, _lib.F32, 0, ctypes.c_void_p(a.data_ptr()), si, scnt, 0, stream))
+        dst = (ctypes.c_int64 * plan.n_tiles)(*[o if k % scnt == si else -1 for k, o in enumerate(off)])
+        _lib.check(L.moe_run_plan_tiles(model._h, plan._h, x.data_ptr(), _lib.F32, 0, sC, sH, sW, 1, ctypes.c_void_p(b.data_ptr()), dst, 0, stream))
+        torch.cuda.synchronize()
+        assert torch.equal(a, b), (si, scnt)
+        mine = torch.zeros_like(pool_ref, dtype=torch.bool)
+        for k, o in enumerate(off):
+            if k % scnt == si:
+                mine[o:o + sizes[k]] = True
+        assert torch.equal(a[mine], pool_ref[mine]) and not a[~mine].any(), (si, scnt)
+
+
+def test_run_plan_with_more_input_layouts_than_the_plan_caches(dev):
+    """One plan, 18 distinct input layouts (row pitches: the image as a slice of wider tensors) -- more than the plan keeps device tables for -- with a
+    moe_stitch between the runs, then the first layout again: every canvas is bit-equal to doCrop of the contiguous image."""
+    from moephoto_amd import _lib
+    opt, x, plan, want, pool_ref, _ = _plan_runner_case(dev)
+    L, model = _lib.lib(), opt.modelCached
+    stream = torch.cuda.current_stream().cuda_stream
+    views = []
+    for i in range(18):
+        wide = torch.full((3, 150, 208 + 8 * i), float('nan'), dtype=torch.float32, device=dev)
+        wide[:, :, 3:203] = x
+        views.append(wide[:, :, 3:203])
+    assert len({v.stride() for v in views}) == 18
+    for v in views + [views[0]]:
+        y = torch.empty_like(want)
+        sC, sH, sW = v.stride()
+        _lib.check(L.moe_run_plan(model._h, plan._h, v.data_ptr(), _lib.F32, sC, sH, sW, y.data_ptr(), _lib.F32, 0, stream))
+        y2 = torch.empty_like(want)
+        _lib.check(L.moe_stitch(plan._h, 0, pool_ref.data_ptr(), None, 3, y2.data_ptr(), _lib.F32, stream))
+        torch.cuda.synchronize()
+        assert torch.equal(y, want) and torch.equal(y2, want), v.stride()
+
+
+def test_stitch_of_a_permuted_pool_host_table_device_table_and_default_layout(dev):
+    """The tiles at shuffled offsets in the pool: moe_stitch with the offsets passed from the host, moe_stitch_dev with the same table on the device and
+    moe_stitch of the plan's own layout give one canvas, bit for bit -- for 18 distinct permutations on one plan (more than the uploaded tables it keeps)."""
+    import ctypes
+    from moephoto_amd import _lib
+    opt, _, plan, want, pool_ref, sizes = _plan_runner_case(dev)
+    L = _lib.lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    off = plan.tile_offsets(3)
+    canvas0 = torch.empty_like(want)
+    _lib.check(L.moe_stitch(plan._h, 0, pool_ref.data_ptr(), None, 3, canvas0.data_ptr(), _lib.F32, stream))
+    seen = set()
+    for seed in range(18):
+        offs, order = _shuffled_layout(sizes, 100 + seed)
+        seen.add(order)
+        pool = torch.full_like(pool_ref, float('nan'))
+        for k in range(plan.n_tiles):
+            pool[offs[k]:offs[k] + sizes[k]] = pool_ref[off[k]:off[k] + sizes[k]]
+        host = (ctypes.c_int64 * plan.n_tiles)(*offs)
+        tab = torch.tensor(offs, dtype=torch.int64, device=dev)
+        ya, yb = torch.empty_like(want), torch.empty_like(want)
+        _lib.check(L.moe_stitch(plan._h, 0, pool.data_ptr(), ctypes.c_void_p(ctypes.addressof(host)), 3, ya.data_ptr(), _lib.F32, stream))
+        _lib.check(L.moe_stitch_dev(plan._h, 0, pool.data_ptr(), ctypes.c_void_p(tab.data_ptr()), 3, yb.data_ptr(), _lib.F32, stream))
+        torch.cuda.synchronize()
+        assert torch.equal(ya, canvas0) and torch.equal(yb, canvas0), seed
+    assert len(seen) == 18 and torch.equal(canvas0, want)
+
+
+def test_run_plan_tiles_with_more_destination_tables_than_the_plan_caches(dev):
+    """moe_run_plan_tiles with 10 distinct destination tables on one plan (each a shuffled packing of the pool), each stitched through moe_stitch_dev with its
+    table: every canvas is bit-equal to doCrop."""
+    import ctypes
+    from moephoto_amd import _lib
+    opt, x, plan, want, pool_ref, sizes = _plan_runner_case(dev)
+    L, model = _lib.lib(), opt.modelCached
+    stream = torch.cuda.current_stream().cuda_stream
+    sC, sH, sW = x.stride()
+    seen = set()
+    for seed in range(10):
+        offs, order = _shuffled_layout(sizes, 200 + seed)
+        seen.add(order)
+        pool = torch.full_like(pool_ref, float('nan'))
+        dst = (ctypes.c_int64 * plan.n_tiles)(*offs)
+        _lib.check(L.moe_run_plan_tiles(model._h, plan._h, x.data_ptr(), _lib.F32, 0, sC, sH, sW, 1, ctypes.c_void_p(pool.data_ptr()), dst, 0, stream))
+        tab = torch.tensor(offs, dtype=torch.int64, device=dev)
+        y = torch.empty_like(want)
+        _lib.check(L.moe_stitch_dev(plan._h, 0, pool.data_ptr(), ctypes.c_void_p(tab.data_ptr()), 3, y.data_ptr(), _lib.F32, stream))
+        torch.cuda.synchronize()
+        assert torch.equal(y, want), seed
+    assert len(seen) == 10
+
+
 def test_full_size_properties_config2(dev):
     """BASELINE config 2 at full size (1080p -> 7680x4320, a4-synth, 256-px tiles, 40 tiles), checked through
     properties that do not need a full CPU run:
