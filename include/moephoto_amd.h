@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MOE_ABI_VERSION 4      /* 4: moe_net_forward_ex / MOE_FWD_INPUT_SINCE_PREV (round 6); still 4 with moe_sym_pad / moe_sym_fold / moe_run_plan_ens: additions only, every earlier entry point is unchanged, so a caller built against the earlier 4 runs as before (a caller of the new ones looks the symbols up); 3: moe_net_calibrate / moe_net_exact_blocks, MOE_PREC_AUTO measures the checkpoint at finalize, moe_blend_tile (round 5); 2: MOE_PREC_AUTO, moe_net_resolved_precision, moe_plan_rows / moe_stitch_band, moe_plan_seams / moe_wire_* (round 4); 1 also lacked a bump for moe_net_set_option / moe_device_info / moe_stitch_dev */
+#define MOE_ABI_VERSION 4      /* 4: moe_net_forward_ex / MOE_FWD_INPUT_SINCE_PREV (round 6); still 4 with moe_sym_pad / moe_sym_fold / moe_run_plan_ens and with moe_stitch_out / moe_run_plan_out: additions only, every earlier entry point is unchanged, so a caller built against the earlier 4 runs as before (a caller of the new ones looks the symbols up); 3: moe_net_calibrate / moe_net_exact_blocks, MOE_PREC_AUTO measures the checkpoint at finalize, moe_blend_tile (round 5); 2: MOE_PREC_AUTO, moe_net_resolved_precision, moe_plan_rows / moe_stitch_band, moe_plan_seams / moe_wire_* (round 4); 1 also lacked a bump for moe_net_set_option / moe_device_info / moe_stitch_dev */
 
 /* error codes */
 #define MOE_OK 0
@@ -218,6 +218,12 @@ int moe_stitch_dev(const moe_plan* plan, int device, const float* tiles_dev, con
  * only those strips cross between neighbouring bands), bit-identical to the rows of moe_stitch's canvas. */
 int moe_stitch_band(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C,
                     void* out, int out_dtype, int row0, int row1, int strip, void* stream);
+/* The fold of moe_stitch_dev, the rounding of a canvas of `canvas_dtype` (MOE_F16 | MOE_F32) and the quantiser of moe_to_output in ONE pass over the pool: replaces
+ * python/imageProcess.py:120-131,167-170 (blend + slice-assign), :238-243 (toFloat) and :245-257 (toOutput) for a caller that only wants the encoder's samples.
+ * dst: out_h x out_w x C interleaved, MOE_U8 (bits = 8) or MOE_U16 (bits = 8 | 16), the bytes moe_stitch -> fp32 -> moe_to_output give; tile_off_dev: n_tiles int64
+ * on the DEVICE, NULL = the plan's own layout.  C = 1 .. 4, any out_w.  Asynchronous on `stream`; the canvas itself never exists. */
+int moe_stitch_out(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int bits,
+                   void* dst, int dst_dtype, void* stream);
 /* The body of the reference's tile loop behind the net call, for a caller that KEEPS that loop -- python/imageProcess.py:167-170:
  *     t = tmp_image[..., top*sc:bsc, left*sc:rsc];  q, _ = blend(*blend(unpad(r), t, topT, padSc, -2, bl.t()), leftT, padSc, -1, bl);  tmp_image[..., bsc-h:bsc, rsc-w:rsc] = q
  * as one kernel, in place on the canvas.  r: the tile result, C planes, element (c,i,j) at r + c*r_sC + i*r_sH + j (its first bsc-top_sc rows and rsc-left_sc
@@ -261,6 +267,11 @@ int moe_run_plan(moe_net* net, const moe_plan* plan, const void* img, int img_dt
 int moe_run_plan_ex(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                     void* out, int out_dtype, int max_tiles_per_batch, float* pool, int shard_index, int shard_count,
                     int do_stitch, void* stream);
+
+/* doCrop + toFloat + toOutput (python/imageProcess.py:157-172,238-257): moe_run_plan_ex without shard on the plan's internal pool, its final fold replaced by
+ * moe_stitch_out.  dst, canvas_dtype, bits, dst_dtype as there; asynchronous on `stream`. */
+int moe_run_plan_out(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
 
 /* Multi-frame, owner-sharded form of the tile loop (the multi-GPU step of moephoto_amd/dist.py; the reference runs frames one
  * after the other through doCrop, python/video.py:349-360 -> python/imageProcess.py:157-172).  `imgs` holds n_frames equally

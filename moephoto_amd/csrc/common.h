@@ -447,6 +447,7 @@ struct StitchArgs {
     int y0, rows;                                    // the canvas rows [y0, y0 + rows) are folded into `out` = (C, rows, out_w): the whole canvas (0, out_h) or a band (moe_stitch_band)
 };
 void launch_stitch(const StitchArgs& a, hipStream_t s);
+bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s);      // the fold + the canvas dtype's rounding + to_output's quantiser: a.out = interleaved u8 / u16
 
 // blend.hip: the two blend() calls + slice-assign of doCrop's loop body for ONE tile, in the canvas dtype (moe_blend_tile)
 struct BlendTileArgs {

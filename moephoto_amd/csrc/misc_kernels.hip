@@ -1313,6 +1313,113 @@ __global__ __launch_bounds__(256) void to_output3_kernel(const TS* __restrict__ 
     *(VecN<TD, 24>*)(dst + p0 * 3) = o;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Stitch straight into the encoder's bytes (moe_stitch_out): the fold above, the rounding of the canvas dtype and to_output_kernel's quantiser in one pass -- the pool is
+// read once and the interleaved u8 / u16 image written once; the fp16 / fp32 canvas and its fp32 copy (stitch -> toFloat -> toOutput: 17-18 bytes per pixel-plane) never
+// exist.  The shape of stitch8r_kernel with the planes inside the thread: one thread = R rows x 8 consecutive pixels x ALL C planes, so what it writes per row is one
+// contiguous run of 8 * C elements.  A thread whose eight columns lie in the solid part of ONE tile column folds the covering tile rows as vectors (one row outside a
+// blend band: the identity on that tile's values); threads on a column seam and the ragged end of a row (any out_w) enlist their group and the whole block folds those
+// pixels one per thread with stitch_pixel.  Per element the operations of the three passes in their order, so the bytes are theirs.  (Times of this form and of the
+// one-row-per-thread form before it, on the 8K frame beside the three passes: profiles/frame_stream/summary.md.)
+// ---------------------------------------------------------------------------------------------------
+template <typename TD, int C> struct alignas((sizeof(TD) * 8 * C) % 16 == 0 ? 16 : 8) StitchOutRun { TD e[8 * C]; };
+
+template <typename TD>
+__device__ __forceinline__ TD stitch_out_quant(float v, bool f16, float quant)
+{
+    if (f16) v = (float)(half_t)v;                       // what the fp16 canvas held
+    v = v * quant;                                       // to_output_kernel: image * quant, clamp_(0, quant - 1), truncate
+    v = fminf(fmaxf(v, 0.f), quant - 1.f);
+    if (!(v == v)) v = 0.f;
+    return (TD)(int)v;
+}
+
+template <typename TD, int C, int R>
+__global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float quant, int f16)
+{
+    __shared__ int s_seam[256];
+    __shared__ int s_nseam;
+    if (threadIdx.x == 0) s_nseam = 0;
+    __syncthreads();
+    const int Y0 = blockIdx.y * R;
+    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
+    TD* const dst = (TD*)a.out;
+    if (X0 < a.out_w) {
+        bool colfast = X0 + 8 <= a.out_w;
+        int j0 = 0, ox = 0, ew = 0;
+        if (colfast) {
+            j0 = a.col_first[X0];
+            colfast = a.col_cnt[X0] == 1 && a.col_cnt[X0 + 7] == 1 && a.col_first[X0 + 7] == j0;
+            const int sx = a.col_tab[j0 * 4 + 1];
+            ox = a.col_tab[j0 * 4 + 2]; ew = a.col_tab[j0 * 4 + 3];
+            colfast = colfast && X0 >= sx;
+        }
+        if (!colfast) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;      // a column seam or the row's ragged end: handed to the whole block below
+        else {
+            StitchOutRun<TD, C> o[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int Y = min(Y0 + r, a.out_h - 1);            // (rows past the canvas repeat the last one and are not stored)
+                const int i0 = a.row_first[Y], ni = a.row_cnt[Y];  // block-uniform
+                float cur[C][8];
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) cur[c][e] = 0.f;
+                for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {
+                    const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
+                    const long long o0 = a.tile_off[i * a.step_w + j0] + (long long)(Y - oy) * ew + (X0 - ox), plane = (long long)eh * ew;
+                    const bool band = Y < sy;
+                    const float wgt = band ? a.ramp[Y - fy] : 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const long long t = o0 + c * plane;
+                        float q[8];
+                        if ((t & 3) == 0) {
+                            const float4 q0 = *(const float4*)(a.tiles + t), q1 = *(const float4*)(a.tiles + t + 4);
+                            q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) q[e] = a.tiles[t + e];
+                        }
+                        if (band) {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) cur[c][e] = cur[c][e] + wgt * (q[e] - cur[c][e]);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) cur[c][e] = q[e];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[r].e[e * C + c] = stitch_out_quant<TD>(cur[c][e], f16 != 0, quant);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (Y0 + r >= a.out_h) break;
+                TD* p = dst + ((long long)(Y0 + r) * a.out_w + X0) * C;
+                if (((uintptr_t)p & (alignof(StitchOutRun<TD, C>) - 1)) == 0) *(StitchOutRun<TD, C>*)p = o[r];
+                else {
+#pragma unroll
+                    for (int k = 0; k < 8 * C; ++k) p[k] = o[r].e[k];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int total = s_nseam * (8 * R * C);
+    for (int t = threadIdx.x; t < total; t += 256) {
+        const int gidx = t / (8 * R * C), rem = t - gidx * (8 * R * C);
+        const int r = rem / (8 * C), ec = rem - r * (8 * C);
+        const int e = ec / C, c = ec - e * C;
+        const int X = (blockIdx.x * 256 + s_seam[gidx]) * 8 + e, Y = Y0 + r;
+        if (Y >= a.out_h || X >= a.out_w) continue;
+        dst[((long long)Y * a.out_w + X) * C + c] = stitch_out_quant<TD>(stitch_pixel(a, X, Y, c), f16 != 0, quant);
+    }
+}
+
 __global__ void nhwc_to_nchw_kernel(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1420,6 +1527,26 @@ void launch_stitch(const StitchArgs& a, hipStream_t s)
     if (a.out_w % 8 == 0 && a.step_w <= 64 && ((uintptr_t)a.out & 15) == 0) hipLaunchKernelGGL(stitch8r_kernel<4>, dim3((a.out_w / 8 + 255) / 256, (a.rows + 3) / 4, a.C), dim3(256), 0, s, a);
     else if (a.out_w % 4 == 0 && ((uintptr_t)a.out & 15) == 0) hipLaunchKernelGGL(stitch4_kernel, dim3((a.out_w / 4 + 255) / 256, a.rows, a.C), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(stitch_kernel, dim3((a.out_w + 255) / 256, a.rows, a.C), dim3(256), 0, s, a);
+}
+
+template <typename TD>
+static bool launch_stitch_out_t(const StitchArgs& a, float quant, int f16, hipStream_t s)
+{
+    constexpr int R = 4;          // rows per thread (stitch8r_kernel's)
+    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
+    if (a.C == 1) hipLaunchKernelGGL((stitch_out_kernel<TD, 1, R>), g, dim3(256), 0, s, a, quant, f16);
+    else if (a.C == 2) hipLaunchKernelGGL((stitch_out_kernel<TD, 2, R>), g, dim3(256), 0, s, a, quant, f16);
+    else if (a.C == 3) hipLaunchKernelGGL((stitch_out_kernel<TD, 3, R>), g, dim3(256), 0, s, a, quant, f16);
+    else if (a.C == 4) hipLaunchKernelGGL((stitch_out_kernel<TD, 4, R>), g, dim3(256), 0, s, a, quant, f16);
+    else return false;
+    return true;
+}
+
+// a.out: (out_h, out_w, C) interleaved, a.out_dtype MOE_U8 / MOE_U16; the whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
+bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s)
+{
+    const int f16 = canvas_dtype == MOE_F16;
+    return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s) : launch_stitch_out_t<uint16_t>(a, quant, f16, s);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -173,7 +173,11 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // The stitch of C planes from `tiles` into `out`.  tile_off: where each tile lies in `tiles` -- NULL = the plan's own pool layout, else a table on the device or
 // (off_on_host: uploaded once per distinct table, then kept on the plan -- e.g. a receive buffer's layout) on the host.  band: NULL = the whole canvas, else
 // {row0, row1, strip}: the rows of tile rows [row0, row1) only, strip != 0 with tile row row1 present as the strips of its blend band.
-static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s)
+// edge: NULL = `out` is the canvas (C, rows, out_w) of out_dtype; else `out` is the quantised interleaved image (out_h, out_w, C) of out_dtype MOE_U8 / MOE_U16
+// (moe_stitch_out: the whole canvas only).
+struct OutEdge { int canvas_dtype; float quant; };
+static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
+                  const OutEdge* edge = nullptr)
 {
     const Plan& p = pl.p;
     HIP_TRY(hipSetDevice(device));
@@ -222,8 +226,51 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
             a.row_tab = tab;
         }
     }
+    if (edge) {
+        if (!launch_stitch_out(a, edge->canvas_dtype, edge->quant, s)) return fail(MOE_EINVAL, "moe_stitch_out: %d planes (1 to 4 are supported)", C);
+        return launched("stitch_out");
+    }
     launch_stitch(a, s);
     return launched("stitch");
+}
+
+// What moe_stitch_out and moe_run_plan_out check of their output edge before any device call; planes: the C the kernel is asked for.
+static int out_edge_args(const char* who, int planes, int canvas_dtype, int bits, const void* dst, int dst_dtype)
+{
+    if (!dst) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "%s: %d planes (1 to 4 are supported)", who, planes);
+    if (canvas_dtype != MOE_F32 && canvas_dtype != MOE_F16) return fail(MOE_EINVAL, "%s: canvas dtype must be MOE_F32 or MOE_F16", who);
+    if (bits != 8 && bits != 16) return fail(MOE_EINVAL, "%s: %d bits (8 or 16)", who, bits);
+    if (dst_dtype != MOE_U8 && dst_dtype != MOE_U16) return fail(MOE_EINVAL, "%s: dst dtype must be MOE_U8 or MOE_U16", who);
+    if (dst_dtype == MOE_U8 && bits > 8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
+    return MOE_OK;
+}
+
+// moe_run_plan_ex, and moe_run_plan_out = the same with the final fold writing the quantised image (edge)
+static int run_plan(const char* who, moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                    void* out, int out_dtype, int max_tiles, float* pool, int shard_index, int shard_count, int do_stitch, void* stream, const OutEdge* edge)
+{
+    if (!n || !pl || !img || (do_stitch && !out)) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (!n->finalized) return fail(MOE_ESTATE, "%s: net is not finalized", who);
+    const Plan& p = pl->p;
+    if (p.sc != n->scale) return fail(MOE_EINVAL, "%s: plan scale %d != net scale %d", who, p.sc, n->scale);
+    if (shard_count < 1) { shard_count = 1; shard_index = 0; }
+    if (shard_index < 0 || shard_index >= shard_count) return fail(MOE_EINVAL, "%s: shard %d of %d", who, shard_index, shard_count);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(n->device));
+    std::vector<int64_t> at(p.tile_off.begin(), p.tile_off.end());      // this shard's tiles into the plan's own pool layout
+    for (size_t k = 0; k < at.size(); ++k) if ((int)(k % shard_count) != shard_index) at[k] = -1;
+    const TileTable* d = nullptr;
+    int rc = tile_table(*pl, n->device, 0, sC, sH, sW, 1, at.data(), s, &d);
+    if (rc) return rc;
+    if (!pool) {
+        rc = pl->dev.pool.grow(p.pool_elems_per_plane_set * 4, s, "tile pool of %zu bytes does not fit", p.pool_elems_per_plane_set * 4);
+        if (rc) return rc;
+        pool = (float*)pl->dev.pool.p;
+    }
+    rc = run_sets(*n, p, *d, img, img_dtype, sH, sW, pool, max_tiles, s);
+    if (rc || !do_stitch) return rc;
+    return stitch(*pl, n->device, pool, nullptr, false, p.C, out, out_dtype, nullptr, s, edge);
 }
 
 extern "C" {
@@ -382,6 +429,15 @@ int moe_stitch_band(const moe_plan* p, int device, const float* tiles_dev, const
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, out, out_dtype, band, (hipStream_t)stream);
 }
 
+int moe_stitch_out(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int bits, void* dst, int dst_dtype, void* stream)
+{
+    if (!p || !tiles_dev || C < 1) return fail(MOE_EINVAL, "moe_stitch_out: bad argument");
+    const int rc = out_edge_args("moe_stitch_out", C, canvas_dtype, bits, dst, dst_dtype);
+    if (rc) return rc;
+    const OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
+}
+
 int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int64_t c_sC, int64_t c_sH, int dtype, int C,
                    int top_sc, int left_sc, int bsc, int rsc, int topT, int leftT, int pad_sc, const void* ramp, void* stream)
 {
@@ -409,27 +465,17 @@ int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int6
 int moe_run_plan_ex(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                     void* out, int out_dtype, int max_tiles, float* pool, int shard_index, int shard_count, int do_stitch, void* stream)
 {
-    if (!n || !pl || !img || (do_stitch && !out)) return fail(MOE_EINVAL, "moe_run_plan: NULL argument");
-    if (!n->finalized) return fail(MOE_ESTATE, "moe_run_plan: net is not finalized");
-    const Plan& p = pl->p;
-    if (p.sc != n->scale) return fail(MOE_EINVAL, "moe_run_plan: plan scale %d != net scale %d", p.sc, n->scale);
-    if (shard_count < 1) { shard_count = 1; shard_index = 0; }
-    if (shard_index < 0 || shard_index >= shard_count) return fail(MOE_EINVAL, "moe_run_plan: shard %d of %d", shard_index, shard_count);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(n->device));
-    std::vector<int64_t> at(p.tile_off.begin(), p.tile_off.end());      // this shard's tiles into the plan's own pool layout
-    for (size_t k = 0; k < at.size(); ++k) if ((int)(k % shard_count) != shard_index) at[k] = -1;
-    const TileTable* d = nullptr;
-    int rc = tile_table(*pl, n->device, 0, sC, sH, sW, 1, at.data(), s, &d);
+    return run_plan("moe_run_plan", n, pl, img, img_dtype, sC, sH, sW, out, out_dtype, max_tiles, pool, shard_index, shard_count, do_stitch, stream, nullptr);
+}
+
+int moe_run_plan_out(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_out: NULL argument");
+    const int rc = out_edge_args("moe_run_plan_out", pl->p.C, canvas_dtype, bits, dst, dst_dtype);
     if (rc) return rc;
-    if (!pool) {
-        rc = pl->dev.pool.grow(p.pool_elems_per_plane_set * 4, s, "tile pool of %zu bytes does not fit", p.pool_elems_per_plane_set * 4);
-        if (rc) return rc;
-        pool = (float*)pl->dev.pool.p;
-    }
-    rc = run_sets(*n, p, *d, img, img_dtype, sH, sW, pool, max_tiles, s);
-    if (rc || !do_stitch) return rc;
-    return stitch(*pl, n->device, pool, nullptr, false, p.C, out, out_dtype, nullptr, s);
+    const OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    return run_plan("moe_run_plan_out", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
 int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,

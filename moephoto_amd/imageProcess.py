@@ -250,30 +250,46 @@ def prepareOpt(opt, shape):
     return opt.scale, int(opt.padding * opt.scale)
 
 
-def doCrop(opt, x, *args, **_):
-    """python/imageProcess.py:157-172, entirely on the device: the planes of x (C,H,W) become the batch
-    (runSR.py:37-40), tiles are gathered straight from x by the stem kernel, same-shaped tiles are batched
-    through the net, and the gather-stitch kernel folds them with the reference's sequential blend."""
+def _outStorage(bitDepth):
+    """(torch dtype, numpy dtype, library dtype) of the quantised image: uint8, or uint16 samples in int16 storage (toOutput's convention)."""
+    if bitDepth not in (8, 16):
+        raise ValueError('bitDepth must be 8 or 16, got {}'.format(bitDepth))
+    return (torch.uint8, np.uint8, _lib.U8) if bitDepth == 8 else (torch.int16, np.uint16, _lib.U16)
+
+
+def _runPlan(who, opt, x, bitDepth=None, out=None):
+    """doCrop and doCropOut: the checks, the plan, the pad, the call (moe_run_plan, or with bitDepth moe_run_plan_out) and its one retry after a MemoryError."""
     model = opt.modelCached
     if not isinstance(model, EngineModule):
-        raise TypeError('doCrop needs an engine-backed model (moephoto_amd.models.*), got {}'.format(type(model).__name__))
+        raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
     if x.device.type != 'cuda':
-        raise _lib.EngineError('doCrop: input must live on a HIP device (moephoto_amd has no CPU path)')
+        raise _lib.EngineError('{}: input must live on a HIP device (moephoto_amd has no CPU path)'.format(who))
     if x.dim() != 3:
-        raise ValueError('doCrop expects a (C,H,W) image')
+        raise ValueError('{} expects a (C,H,W) image'.format(who))
+    if bitDepth is not None:
+        out_dt, _, lib_dt = _outStorage(bitDepth)
     plan = _plan_for(opt, x.shape)
     xp = plan.padImage(x)
     if xp.dtype not in _DT:
         xp = xp.to(config.dtype())
     model.to(device=x.device)
     C = xp.shape[0]
-    out = xp.new_empty((C, plan.outH, plan.outW))
+    if bitDepth is None:
+        out = xp.new_empty((C, plan.outH, plan.outW))
+    elif out is None:
+        out = torch.empty((plan.outH, plan.outW, C), dtype=out_dt, device=x.device)
+    elif tuple(out.shape) != (plan.outH, plan.outW, C) or out.dtype != out_dt or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('{}: out must be a contiguous {} tensor of shape {} on {}'.format(who, out_dt, (plan.outH, plan.outW, C), x.device))
     sC, sH, sW = xp.stride()
     stream = torch.cuda.current_stream(x.device).cuda_stream
+    L = _lib.lib()
 
     def run():
-        _lib.check(_lib.lib().moe_run_plan(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW,
-                                           out.data_ptr(), _DT[out.dtype], int(config.tilesPerBatch), stream))
+        if bitDepth is None:
+            _lib.check(L.moe_run_plan(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, out.data_ptr(), _DT[out.dtype], int(config.tilesPerBatch), stream))
+        else:          # the canvas doCrop would have returned has xp's dtype: its rounding is applied before the quantiser
+            _lib.check(L.moe_run_plan_out(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(bitDepth),
+                                          out.data_ptr(), lib_dt, int(config.tilesPerBatch), stream))
     try:
         run()
     except MemoryError:              # the engine's workspace / tile pool is hipMalloc'ed beside torch's caching allocator: release the
@@ -282,6 +298,20 @@ def doCrop(opt, x, *args, **_):
     # the engine reads xp asynchronously: keep it alive until the stream has consumed it
     xp.record_stream(torch.cuda.current_stream(x.device))
     return out
+
+
+def doCrop(opt, x, *args, **_):
+    """python/imageProcess.py:157-172, entirely on the device: the planes of x (C,H,W) become the batch
+    (runSR.py:37-40), tiles are gathered straight from x by the stem kernel, same-shaped tiles are batched
+    through the net, and the gather-stitch kernel folds them with the reference's sequential blend."""
+    return _runPlan('doCrop', opt, x)
+
+
+def doCropOut(opt, x, bitDepth, out=None):
+    """toOutput(bitDepth)(toFloat(doCrop(opt, x))) without the download, as ONE call (moe_run_plan_out): doCrop up to the final fold, which rounds each pixel as the
+    canvas of x's dtype would have and writes the quantised (H, W, C) image (uint8, or uint16 samples in int16 storage) -- the canvas and its fp32 copy never exist
+    (python/imageProcess.py:157-172,238-257).  out: a contiguous device tensor of that shape and dtype to write into (the frame stream's slot buffers), else a new one."""
+    return _runPlan('doCropOut', opt, x, bitDepth, out)
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------

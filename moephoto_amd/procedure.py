@@ -10,12 +10,16 @@ everything between the upload (toTorch) and the download (toOutput) resident on 
 (python/procedure.py:52-55), SR through runSR.sr (:63-73), resize through moe_resize (:104-107), output = toFloat -> toOutput (:128-136).  The progress/ETA
 nodes of the reference are observability only and are not reproduced; `nodes` lists the resolved
 steps.  Ops other than file / buffer / DN / SR / resize / output belong to other model families and raise.
+
+`genFrameStream(steps, width, height, depth)` builds the same chain for a video source as a ring of `depth` frames in flight -- upload, compute and download on
+three queues, the last fold writing the encoder's samples itself (imageProcess.doCropOut) -- and `runFramesStreamed` is `runFrames` over it.
 """
+import time
 from functools import reduce
 
-from . import runDN, runSR
+from . import _lib, runDN, runSR
 from .config import config
-from .imageProcess import RGBFilter, apply, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toTorch, writeFile
+from .imageProcess import RGBFilter, apply, doCropOut, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toTorch, writeFile, _DT, _outStorage
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -96,4 +100,262 @@ def runFrames(process, read, write, width, height, bitDepth=16, start=0, stop=-1
                     write(buf)
                     n += 1
         i += 1
+    return n
+
+
+# ---- streamed frames: a ring of `depth` frames in flight ---------------------------------------------------------------------------------
+# runFrames above is serial per frame: a blocking pageable upload, the chain, stitch -> fp32 copy -> quantise, a blocking pageable download.  The stream keeps `depth`
+# slots (pinned input, device raw frame, device output, pinned output, three events -- all allocated once) and three queues: frame k's upload, compute and download are
+# enqueued in push(k), each waiting on the DEVICE for the events of what it depends on; the host then waits for the download of frame k - depth + 1 only.
+#
+# FrameStream is the ordering logic alone (which slot, which event is waited on before which stage, what push / flush return); it drives a backend object
+#     event() -> e          upload(slot, raw, wait, record)          compute(slot, wait, record)          download(slot, wait, record)
+#     wait(slot, e) -> bytes of the slot's finished frame            abort()   close()
+# where a stage first makes its queue wait for every event of `wait`, enqueues its work, then records `record` behind it.  _DeviceBackend is the one on the GPU.
+def _checkRing(depth, bitDepth):
+    if not isinstance(depth, int) or isinstance(depth, bool) or not 1 <= depth <= 4:
+        raise ValueError('frame stream: depth must be 1..4, got {!r}'.format(depth))
+    if bitDepth not in (8, 16):
+        raise ValueError('frame stream: bitDepth must be 8 or 16, got {!r}'.format(bitDepth))
+
+
+class FrameStream(object):
+    def __init__(self, backend, width, height, bitDepth, depth=2, nodes=()):
+        _checkRing(depth, bitDepth)
+        self.backend, self.depth, self.nodes = backend, depth, list(nodes)
+        self.width, self.height, self.bitDepth = int(width), int(height), bitDepth
+        self.frameBytes = self.width * self.height * 3 * (1 if bitDepth <= 8 else 2)
+        self.events = [dict(uploaded=backend.event(), computed=backend.event(), downloaded=backend.event()) for _ in range(depth)]
+        self.pushed = self.returned = 0       # frames enqueued / handed back; frame k lives in slot k % depth
+        self.closed = self._released = False
+
+    def _guard(self, f):
+        if self.closed:
+            raise RuntimeError('frame stream is closed')
+        try:
+            return f()
+        except BaseException:          # nothing is retried: one device synchronise, the stream is dead, the caller sees the error
+            self.closed = True
+            self.backend.abort()
+            raise
+
+    def _collect(self):
+        """The oldest frame in flight.  Its download event was recorded by an earlier push on this thread, so the host wait cannot hang; once it has passed, every stage
+        of that frame and of the frames before it is over -- the next push may overwrite the slot's pinned input and the caller owns a copy of its pinned output."""
+        slot = self.returned % self.depth
+        buf = self.backend.wait(slot, self.events[slot]['downloaded'])
+        self.returned += 1
+        return buf
+
+    def push(self, raw):
+        """Enqueue one raw frame; returns the frames that are finished, in input order: none while fewer than `depth` are in flight, then one per push."""
+        if self.closed:
+            raise RuntimeError('frame stream is closed')
+        if not raw:
+            return []
+        if len(raw) != self.frameBytes:
+            raise ValueError('short frame: {} of {} bytes'.format(len(raw), self.frameBytes))
+
+        def f():
+            slot = self.pushed % self.depth
+            ev, again = self.events[slot], self.pushed >= self.depth
+            b = self.backend
+            # upload: the slot's raw frame was read by the compute of frame k - depth
+            b.upload(slot, raw, [ev['computed']] if again else [], ev['uploaded'])
+            # compute: needs this frame's upload, and overwrites the output buffer the download of frame k - depth read
+            b.compute(slot, [ev['uploaded']] + ([ev['downloaded']] if again else []), ev['computed'])
+            b.download(slot, [ev['computed']], ev['downloaded'])
+            self.pushed += 1
+            return [self._collect()] if self.pushed - self.returned >= self.depth else []
+        return self._guard(f)
+
+    def flush(self):
+        """Every frame still in flight, in input order."""
+        return self._guard(lambda: [self._collect() for _ in range(self.pushed - self.returned)])
+
+    def close(self):
+        """Frames still in flight are dropped.  Also after a failed stage: the backend lets go of its slots exactly once."""
+        self.closed = True
+        if not self._released:
+            self._released = True
+            self.backend.close()
+
+
+class _DeviceBackend(object):
+    """The stages on the GPU: upload = host memcpy into the slot's pinned buffer + async H2D on its own stream; compute = moe_to_float, the chain's steps and the output
+    edge on torch's current stream; download = async D2H into the slot's pinned buffer on a third stream.  timing: the events take timestamps and `stats` sums the
+    milliseconds per stage over the collected frames (tools/frame_stream_bench.py)."""
+
+    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False):
+        import torch
+        self.torch, self.funcs, self.edge, self.bitDepth, self.timing = torch, funcs, edge, bitDepth, timing
+        self.dev = torch.device(config.device())
+        if self.dev.type != 'cuda':
+            raise _lib.EngineError('frame stream: needs a HIP device (moephoto_amd has no CPU path)')
+        self.H, self.W = int(height), int(width)
+        out_dt, _, _ = _outStorage(bitDepth)
+        self.src_dt = _lib.U8 if bitDepth <= 8 else _lib.U16
+        self.up, self.down = torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev)
+        self.slots = []
+        for _ in range(depth):
+            s = dict(pin_in=torch.empty((self.H, self.W, 3), dtype=out_dt, pin_memory=True), raw=torch.empty((self.H, self.W, 3), dtype=out_dt, device=self.dev),
+                     x=torch.empty((3, self.H, self.W), dtype=config.dtype(), device=self.dev),
+                     out=torch.empty((outHW[0], outHW[1], 3), dtype=out_dt, device=self.dev), pin_out=torch.empty((outHW[0], outHW[1], 3), dtype=out_dt, pin_memory=True))
+            s['in_bytes'] = s['pin_in'].numpy().view('uint8').reshape(-1)
+            s['out_np'] = s['pin_out'].numpy()
+            if timing:
+                s.update(t_up=self.event(), t_comp=self.event(), t_down=self.event())
+            self.slots.append(s)
+        self.stats = dict(frames=0, memcpy_ms=0.0, h2d_ms=0.0, compute_ms=0.0, d2h_ms=0.0, tobytes_ms=0.0)
+
+    def event(self):
+        return self.torch.cuda.Event(enable_timing=self.timing)
+
+    def _stage(self, stream, s, name, wait, record, work):
+        for e in wait:
+            stream.wait_event(e)
+        if self.timing:
+            s['t_' + name].record(stream)
+            s['e_' + name] = record
+        work(stream)
+        record.record(stream)
+
+    def upload(self, slot, raw, wait, record):
+        import numpy as np
+        s = self.slots[slot]
+        t0 = time.perf_counter()
+        s['in_bytes'][:] = np.frombuffer(raw, np.uint8)
+        self.stats['memcpy_ms'] += (time.perf_counter() - t0) * 1e3
+
+        def work(stream):
+            with self.torch.cuda.stream(stream):
+                s['raw'].copy_(s['pin_in'], non_blocking=True)
+        self._stage(self.up, s, 'up', wait, record, work)
+
+    def compute(self, slot, wait, record):
+        s = self.slots[slot]
+
+        def work(stream):
+            _lib.check(_lib.lib().moe_to_float(s['raw'].data_ptr(), self.src_dt, self.bitDepth, self.H, self.W, 3, s['x'].data_ptr(), _DT[s['x'].dtype],
+                                               self.dev.index or 0, stream.cuda_stream))
+            self.edge(reduce(apply, self.funcs, s['x']), s['out'])
+        self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
+
+    def download(self, slot, wait, record):
+        s = self.slots[slot]
+
+        def work(stream):
+            with self.torch.cuda.stream(stream):
+                s['pin_out'].copy_(s['out'], non_blocking=True)
+        self._stage(self.down, s, 'down', wait, record, work)
+
+    def wait(self, slot, event):
+        s = self.slots[slot]
+        event.synchronize()
+        if self.timing:
+            for name, key in (('up', 'h2d_ms'), ('comp', 'compute_ms'), ('down', 'd2h_ms')):      # (the download is over, so is everything before it)
+                self.stats[key] += s['t_' + name].elapsed_time(s['e_' + name])
+        t0 = time.perf_counter()
+        buf = s['out_np'].tobytes()
+        self.stats['tobytes_ms'] += (time.perf_counter() - t0) * 1e3
+        self.stats['frames'] += 1
+        return buf
+
+    def abort(self):
+        self.torch.cuda.synchronize(self.dev)
+
+    def close(self):
+        self.torch.cuda.synchronize(self.dev)
+        self.slots = []
+
+
+def _quantiseInto(bitDepth):
+    """The unfused output edge: moe_to_output straight on a step's (C, H, W) result.  toFloat's fp32 copy of an fp16 result is skipped: fp16 -> fp32 is exact and the
+    kernel widens each value itself, so the samples are toOutput(toFloat(y))'s."""
+    lib_dt = _outStorage(bitDepth)[2]
+
+    def f(y, out):
+        import torch
+        if y.dtype not in _DT:
+            y = y.float()
+        y = y.contiguous()
+        C, H, W = y.shape
+        if tuple(out.shape) != (H, W, C):
+            raise ValueError('frame stream: the chain gave {} where {} was planned'.format((H, W, C), tuple(out.shape)))
+        cur = torch.cuda.current_stream(y.device)
+        _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], H, W, C, int(bitDepth), out.data_ptr(), lib_dt, y.device.index or 0, cur.cuda_stream))
+        y.record_stream(cur)
+    return f
+
+
+def genFrameStream(steps, width, height, depth=2, timing=False):
+    """genProcess for a video source as a stream: `steps` as genProcess takes them, steps[0] = {'op': 'buffer', 'bitDepth': 8 | 16}; frames are width x height x 3.
+    Returns a FrameStream: push(raw) -> list of finished frames' bytes (input order; [] for an empty buffer), flush(), close(), nodes.  The last compute step decides
+    the output edge: an SR without ensemble or a DN of strength 1 folds its tiles straight into the encoder's samples (doCropOut: the canvas never exists); after a
+    resize, a DN blended with its input or an ensemble the step's result is quantised in place.  Same bytes as genProcess + runFrames either way."""
+    steps = [dict(s) for s in steps]
+    if not steps or steps[0].get('op') != 'buffer':
+        raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
+    bitDepth = int(steps[0].get('bitDepth', 16))
+    _checkRing(depth, bitDepth)          # (before any model is loaded)
+    work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
+    for opt in work:
+        if opt['op'] not in stepOpts:
+            raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(opt['op']))
+    funcs, nodes, edge = [], [], None
+    h, w = int(height), int(width)
+    for k, opt in enumerate(work):
+        op, last = opt['op'], k == len(work) - 1
+        so = stepOpts[op]
+        convertValues(int, opt, so.get('toInt', []))
+        convertValues(float, opt, so.get('toFloat', []))
+        if op == 'resize':
+            funcs.append(resize(opt, dict(source=True)))
+            h = round(h * opt['scaleH']) if 'scaleH' in opt else opt['height']
+            w = round(w * opt['scaleW']) if 'scaleW' in opt else opt['width']
+            nodes.append(dict(op='resize', mode=opt['method']))
+            continue
+        o = so['getOpt'].getOpt(opt)
+        if o is None:
+            raise ValueError('unknown model for step {}'.format(opt))
+        opt['opt'] = o
+        if op == 'SR':
+            if not opt['scale'] > 1:
+                raise TypeError('Invalid scale setting for SR.')
+            if last and o.ensemble == 0:
+                edge = lambda x, out, o=o: doCropOut(o, x, bitDepth, out)
+            else:
+                funcs.append(runSR.sr(o))
+            h, w = h * opt['scale'], w * opt['scale']
+        elif last and o.strength == 1:         # RGBFilter on three planes with nothing to blend: prepare, doCrop
+            edge = lambda x, out, o=o: doCropOut(o, o.prepare(x), bitDepth, out)
+        else:
+            funcs.append(RGBFilter(o))
+        nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
+    backend = _DeviceBackend(funcs, edge or _quantiseInto(bitDepth), bitDepth, width, height, (h, w), depth, timing)
+    return FrameStream(backend, width, height, bitDepth, depth, nodes)
+
+
+def runFramesStreamed(stream, read, write, start=0, stop=-1):
+    """runFrames over a FrameStream: the same frames reach `write` in the same order and the same count is returned; they arrive up to depth - 1 reads later.  A short
+    frame raises the same ValueError after every frame already pushed has been written."""
+    i = n = 0
+
+    def hand(bufs):
+        nonlocal n
+        for buf in bufs:
+            if buf:
+                write(buf)
+                n += 1
+    while stop < 0 or i <= stop:
+        raw = read(stream.frameBytes)
+        if len(raw) == 0:
+            break
+        if len(raw) != stream.frameBytes:
+            hand(stream.flush())
+            raise ValueError('short frame: {} of {} bytes'.format(len(raw), stream.frameBytes))
+        if i >= start:
+            hand(stream.push(raw))
+        i += 1
+    hand(stream.flush())
     return n
