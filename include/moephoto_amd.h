@@ -224,6 +224,19 @@ int moe_stitch_band(const moe_plan* plan, int device, const float* tiles_dev, co
  * on the DEVICE, NULL = the plan's own layout.  C = 1 .. 4, any out_w.  Asynchronous on `stream`; the canvas itself never exists. */
 int moe_stitch_out(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int bits,
                    void* dst, int dst_dtype, void* stream);
+/* The DN step's edge inside that fold, for plans of scale 1: replaces RGBFilter's passes behind doCrop -- strengthOp's `s * x + (1 - s) * inp` (python/imageProcess.py:562,
+ * three elementwise passes) and mergeAlpha's concatenation (:359-366, within RGBFilter :368-377) -- and, with bits != 0, toFloat / toOutput as moe_stitch_out does (:238-257).  Per pixel-plane
+ * c = the fold rounded to the canvas dtype T = inp_dtype (MOE_F16 | MOE_F32), then y = T(T(sf * c) + T(tf * inp)) with sf = (float)strength, tf = (float)(1.0 - strength)
+ * and every product and the sum formed in fp32 -- the bits torch gives for the expression on device tensors; strength == 1: y = c.  (Where torch's own kernels
+ * round an fp16 product once instead of fp32-then-fp16 -- the last partial block of 2048 elements of a dense tensor, every element of a strided view -- so does this
+ * one: an inp with unit column stride on a 16-byte aligned base counts as the dense image or its padded copy, any other inp as a strided view.)  inp: the image the net saw, element
+ * (c,i,j) at inp + c*sC + i*sH + j*sW (elements; may be a view), read at the output's coordinates; alpha (NULL: none): one more plane of dtype T, element (i,j) at
+ * alpha + i*aH + j*aW, copied unchanged behind the C planes.  bits = 0: dst = the canvas (C [+ 1], out_h, out_w) contiguous, dst_dtype = inp_dtype; bits = 8 | 16:
+ * dst = out_h x out_w x (C [+ 1]) interleaved samples, MOE_U8 (8) or MOE_U16, as moe_stitch_out writes them; no canvas exists.  C + alpha = 1 .. 4; strength finite;
+ * tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+int moe_stitch_mix(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C,
+                   const void* inp, int inp_dtype, int64_t sC, int64_t sH, int64_t sW, const void* alpha, int64_t aH, int64_t aW,
+                   double strength, int bits, void* dst, int dst_dtype, void* stream);
 /* The body of the reference's tile loop behind the net call, for a caller that KEEPS that loop -- python/imageProcess.py:167-170:
  *     t = tmp_image[..., top*sc:bsc, left*sc:rsc];  q, _ = blend(*blend(unpad(r), t, topT, padSc, -2, bl.t()), leftT, padSc, -1, bl);  tmp_image[..., bsc-h:bsc, rsc-w:rsc] = q
  * as one kernel, in place on the canvas.  r: the tile result, C planes, element (c,i,j) at r + c*r_sC + i*r_sH + j (its first bsc-top_sc rows and rsc-left_sc
@@ -272,6 +285,13 @@ int moe_run_plan_ex(moe_net* net, const moe_plan* plan, const void* img, int img
  * moe_stitch_out.  dst, canvas_dtype, bits, dst_dtype as there; asynchronous on `stream`. */
 int moe_run_plan_out(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                      int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
+
+/* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
+ * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
+ * alpha, strength, bits, dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */
+int moe_run_plan_filter(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                        const void* alpha, int64_t aH, int64_t aW, double strength, int bits, void* dst, int dst_dtype,
+                        int max_tiles_per_batch, void* stream);
 
 /* Multi-frame, owner-sharded form of the tile loop (the multi-GPU step of moephoto_amd/dist.py; the reference runs frames one
  * after the other through doCrop, python/video.py:349-360 -> python/imageProcess.py:157-172).  `imgs` holds n_frames equally

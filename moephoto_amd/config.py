@@ -19,6 +19,7 @@ class Config(object):
         self.maxGraphicMemoryUsage = 0
         self.modelRoot = '.'        # directory that holds ./model/<name>/model_new.pth
         self.tilesPerBatch = 0      # 0: engine default
+        self.filterOnDevice = True     # DN step: strength blend and alpha plane inside the final fold (moe_run_plan_filter); False: the torch expressions (same bits)
         self.ensembleOnDevice = True   # SR self-ensemble: symmetries, sums and average as engine passes (moe_run_plan_ens); False: the torch expressions (same bits)
 
     def getConfig(self):

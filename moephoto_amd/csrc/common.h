@@ -448,6 +448,16 @@ struct StitchArgs {
 };
 void launch_stitch(const StitchArgs& a, hipStream_t s);
 bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s);      // the fold + the canvas dtype's rounding + to_output's quantiser: a.out = interleaved u8 / u16
+// The DN step's edge inside the stitch (stitch_mix_kernel, plans of scale 1): what RGBFilter does behind doCrop.  T = the canvas dtype.
+struct StitchMix {
+    const void* inp; long long sC, sH, sW;           // the image the net saw, dtype T: element (c, y, x) at inp + c sC + y sH + x sW (elements); its top-left out_h x out_w is read
+    const void* alpha; long long aH, aW;             // optional plane of dtype T copied behind the net's planes (nullptr: none)
+    float sf, tf; int blend;                         // y = T(T(sf c) + T(tf inp)); blend == 0 (strength 1): y = c
+    float quant;                                     // 0: the canvas form; else 2^bits: the sample form
+    int inp_vec, alpha_vec;                          // set by launch_stitch_mix: rows may be read as 16-byte vectors
+    long long once_from; int q_once;                 // set by launch_stitch_mix, fp16: from this element of the (C, H, W) result on / for inp everywhere a product is rounded once, as torch's kernels do
+};
+bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s);
 
 // blend.hip: the two blend() calls + slice-assign of doCrop's loop body for ONE tile, in the canvas dtype (moe_blend_tile)
 struct BlendTileArgs {

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "../../include/moephoto_amd.h"
 
 namespace {
@@ -1420,6 +1421,202 @@ __global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float qua
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The DN step's edge in the stitch (moe_stitch_mix; plans of scale 1): RGBFilter's passes behind doCrop -- strengthOp's s * x + (1 - s) * inp and the alpha plane that
+// rides around the net (python/imageProcess.py:350-377,562) -- inside the fold above, and, in the sample form, toFloat / toOutput (:238-257) behind them.  Per
+// pixel-plane, in T = the canvas dtype, as torch evaluates the expression on device tensors (scalars as fp32, every intermediate tensor in T):
+//     c = T(fold);   y = T( T(sf * c) + T(tf * inp) );   strength 1: y = c (strengthOp returns x itself)
+// The two products and the sum are three separately rounded fp32 operations: the empty asm statements keep each product in its register, so neither is fused into
+// the sum (an FMA rounds once) nor, for fp16, into its own conversion (v_fma_mixlo_f16 rounds the exact product once; sym.hip's closing average met the same).  The
+// fp32 sum of two fp16 values followed by its rounding to fp16 is the correctly rounded sum either way (24 >= 2 * 11 + 2 bits).
+// Where torch itself rounds an fp16 product ONCE, so does this kernel (measured on torch 2.10, profiles/filter/summary.md): its vectorised elementwise kernel
+// takes a dense tensor in blocks of 2048 elements and the last, partial block runs through other code, in which the compiler did pick v_fma_mixlo_f16 -- as it did in
+// the kernel that serves strided views.  So element i of the (C, H, W) result has its products rounded once when i >= once_from = the start of that last block, and
+// the input's product everywhere when the input is a view torch would not vectorise (m.q_once).  0.2 - 3 % of such elements differ by one fp16 ulp between the forms.
+// Shape: stitch_out_kernel's -- one thread = R rows (4, or 1 on small canvases: launch_stitch_mix_t) x 8 pixels x all CT output planes, seam and ragged-row threads hand their pixels to the block.  Planes [0, a.C) are
+// the net's; plane a.C (when CT > a.C) is alpha, copied.  TD == T: the canvas form, dst = (CT, out_h, out_w) planes; else the sample form, dst = (out_h, out_w, CT)
+// interleaved through to_output_kernel's quantiser.  inp / alpha are read through element strides, as 16-byte vectors where m.inp_vec / m.alpha_vec say they may be.
+// ---------------------------------------------------------------------------------------------------
+// T(h * f): the product rounded to fp32, then to T
+template <typename T>
+__device__ __forceinline__ T stitch_mix_mul(T h, float f)
+{
+#pragma clang fp contract(off)
+    float p = __fmul_rn(f, (float)h);
+    asm("" : "+v"(p));
+    return (T)p;
+}
+
+// fp16(h * f) with ONE rounding of the exact product: v_fma_mixlo_f16 with h read as fp16 from the low half of its register, f and the addend -0 as fp32
+__device__ __forceinline__ half_t stitch_mix_mul_once(half_t h, float f)
+{
+    unsigned r;
+    const unsigned hb = __builtin_bit_cast(unsigned short, h);
+    const float nz = -0.0f;
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hb), "v"(f), "v"(nz));
+    return __builtin_bit_cast(half_t, (unsigned short)(r & 0xffffu));
+}
+__device__ __forceinline__ float stitch_mix_mul_once(float h, float f) { return stitch_mix_mul<float>(h, f); }      // (fp32: a product has one rounding anyway)
+
+template <typename T>
+__device__ __forceinline__ T stitch_mix_value(float cur, T inp, float sf, float tf, bool p_once, bool q_once)
+{
+#pragma clang fp contract(off)
+    const T c = (T)cur;
+    const T hp = p_once ? stitch_mix_mul_once(c, sf) : stitch_mix_mul<T>(c, sf);
+    const T hq = q_once ? stitch_mix_mul_once(inp, tf) : stitch_mix_mul<T>(inp, tf);
+    return (T)__fadd_rn((float)hp, (float)hq);
+}
+
+template <typename T>
+__device__ __forceinline__ void stitch_mix_load8(const T* p, long long sW, bool vec, T (&v)[8])
+{
+    if (vec) {
+        typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
+        constexpr int N = 16 / sizeof(T);
+#pragma unroll
+        for (int k = 0; k < 8 / N; ++k) {
+            const vec_t q = *(const vec_t*)(p + k * N);
+#pragma unroll
+            for (int e = 0; e < N; ++e) v[k * N + e] = q[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = p[e * sW];
+    }
+}
+
+template <typename T, typename TD, int CT, int R>
+__global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix m)
+{
+    constexpr bool SAMPLE = !std::is_same<T, TD>::value;
+    __shared__ int s_seam[256];
+    __shared__ int s_nseam;
+    if (threadIdx.x == 0) s_nseam = 0;
+    __syncthreads();
+    const int Y0 = blockIdx.y * R;
+    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
+    const int nC = a.C;
+    const T* const inp = (const T*)m.inp;
+    const T* const alpha = (const T*)m.alpha;
+    TD* const dst = (TD*)a.out;
+    const long long out_plane = (long long)a.out_h * a.out_w;
+    if (X0 < a.out_w) {
+        bool colfast = X0 + 8 <= a.out_w;
+        int j0 = 0, ox = 0, ew = 0;
+        if (colfast) {
+            j0 = a.col_first[X0];
+            colfast = a.col_cnt[X0] == 1 && a.col_cnt[X0 + 7] == 1 && a.col_first[X0 + 7] == j0;
+            const int sx = a.col_tab[j0 * 4 + 1];
+            ox = a.col_tab[j0 * 4 + 2]; ew = a.col_tab[j0 * 4 + 3];
+            colfast = colfast && X0 >= sx;
+        }
+        if (!colfast) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;      // a column seam or the row's ragged end: handed to the whole block below
+        else {
+            typename std::conditional<SAMPLE, StitchOutRun<TD, CT>, VecN<T, 8 * CT>>::type o[R];      // sample form: e[pixel * CT + plane]; canvas form: e[plane * 8 + pixel]
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int Y = min(Y0 + r, a.out_h - 1);            // (rows past the canvas repeat the last one and are not stored)
+                const int i0 = a.row_first[Y], ni = a.row_cnt[Y];  // block-uniform
+                float cur[CT][8];
+#pragma unroll
+                for (int c = 0; c < CT; ++c)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) cur[c][e] = 0.f;
+                for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {
+                    const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
+                    const long long o0 = a.tile_off[i * a.step_w + j0] + (long long)(Y - oy) * ew + (X0 - ox), plane = (long long)eh * ew;
+                    const bool band = Y < sy;
+                    const float wgt = band ? a.ramp[Y - fy] : 0.f;
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) {
+                        if (c >= nC) break;
+                        const long long t = o0 + c * plane;
+                        float q[8];
+                        if ((t & 3) == 0) {
+                            const float4 q0 = *(const float4*)(a.tiles + t), q1 = *(const float4*)(a.tiles + t + 4);
+                            q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) q[e] = a.tiles[t + e];
+                        }
+                        if (band) {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) cur[c][e] = cur[c][e] + wgt * (q[e] - cur[c][e]);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) cur[c][e] = q[e];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    T y[8];
+                    if (c >= nC) stitch_mix_load8(alpha + Y * m.aH + X0 * m.aW, m.aW, m.alpha_vec != 0, y);
+                    else if (m.blend) {
+                        const long long left = sizeof(T) == 2 ? m.once_from - (((long long)c * a.out_h + Y) * a.out_w + X0) : 8;      // elements of the run in front of once_from
+                        stitch_mix_load8(inp + c * m.sC + Y * m.sH + X0 * m.sW, m.sW, m.inp_vec != 0, y);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) y[e] = stitch_mix_value<T>(cur[c][e], y[e], m.sf, m.tf, e >= left, e >= left || m.q_once);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) y[e] = (T)cur[c][e];
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        if constexpr (SAMPLE) o[r].e[e * CT + c] = stitch_out_quant<TD>((float)y[e], false, m.quant);
+                        else o[r].e[c * 8 + e] = y[e];
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (Y0 + r >= a.out_h) break;
+                if constexpr (SAMPLE) {
+                    TD* p = dst + ((long long)(Y0 + r) * a.out_w + X0) * CT;
+                    if (((uintptr_t)p & (alignof(StitchOutRun<TD, CT>) - 1)) == 0) *(StitchOutRun<TD, CT>*)p = o[r];
+                    else {
+#pragma unroll
+                        for (int k = 0; k < 8 * CT; ++k) p[k] = o[r].e[k];
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) {
+                        T* p = dst + c * out_plane + (long long)(Y0 + r) * a.out_w + X0;
+                        if (((uintptr_t)p & 15) == 0) {
+                            VecN<T, 8> v;
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) v.e[e] = o[r].e[c * 8 + e];
+                            *(VecN<T, 8>*)p = v;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) p[e] = o[r].e[c * 8 + e];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int total = s_nseam * (8 * R * CT);
+    for (int t = threadIdx.x; t < total; t += 256) {
+        const int gidx = t / (8 * R * CT), rem = t - gidx * (8 * R * CT);
+        const int r = rem / (8 * CT), ec = rem - r * (8 * CT);
+        const int e = ec / CT, c = ec - e * CT;
+        const int X = (blockIdx.x * 256 + s_seam[gidx]) * 8 + e, Y = Y0 + r;
+        if (Y >= a.out_h || X >= a.out_w) continue;
+        T y;
+        if (c >= nC) y = alpha[Y * m.aH + X * m.aW];
+        else {
+            const float cur = stitch_pixel(a, X, Y, c);
+            const bool p_once = sizeof(T) == 2 && ((long long)c * a.out_h + Y) * a.out_w + X >= m.once_from;
+            y = m.blend ? stitch_mix_value<T>(cur, inp[c * m.sC + Y * m.sH + X * m.sW], m.sf, m.tf, p_once, p_once || m.q_once) : (T)cur;
+        }
+        if constexpr (SAMPLE) dst[((long long)Y * a.out_w + X) * CT + c] = stitch_out_quant<TD>((float)y, false, m.quant);
+        else dst[c * out_plane + (long long)Y * a.out_w + X] = y;
+    }
+}
+
 __global__ void nhwc_to_nchw_kernel(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1547,6 +1744,45 @@ bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipSt
 {
     const int f16 = canvas_dtype == MOE_F16;
     return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s) : launch_stitch_out_t<uint16_t>(a, quant, f16, s);
+}
+
+template <typename T, typename TD, int R>
+static bool launch_stitch_mix_r(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
+{
+    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
+    if (planes == 1) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 1, R>), g, dim3(256), 0, s, a, m);
+    else if (planes == 2) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 2, R>), g, dim3(256), 0, s, a, m);
+    else if (planes == 3) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m);
+    else if (planes == 4) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m);
+    else return false;
+    return true;
+}
+
+// Rows per thread: stitch_out_kernel's four where that still gives the device a few waves per SIMD (a 4K canvas and larger); one row on smaller canvases -- a DN
+// step's 1080p frame is 270 workgroups of four rows on 256 CUs, one wave per SIMD waiting out its own loads (times of both: profiles/filter/summary.md).
+template <typename T, typename TD>
+static bool launch_stitch_mix_t(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
+{
+    const long long blocks4 = (long long)(((a.out_w + 7) / 8 + 255) / 256) * ((a.out_h + 3) / 4);
+    return blocks4 >= 1024 ? launch_stitch_mix_r<T, TD, 4>(a, m, planes, s) : launch_stitch_mix_r<T, TD, 1>(a, m, planes, s);
+}
+
+// a.C: the net's planes; with m.alpha one more plane is written.  m.quant == 0: a.out = the canvas (planes, out_h, out_w) of canvas_dtype; else a.out = interleaved
+// (out_h, out_w, planes) of a.out_dtype MOE_U8 / MOE_U16.  The whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
+bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s)
+{
+    const int planes = a.C + (m.alpha ? 1 : 0);
+    const bool f16 = canvas_dtype == MOE_F16;
+    const long long V = f16 ? 8 : 4;          // elements of a 16-byte vector: base, plane and row pitch must be multiples of it
+    m.inp_vec = m.sW == 1 && (uintptr_t)m.inp % 16 == 0 && m.sC % V == 0 && m.sH % V == 0;
+    m.alpha_vec = m.alpha && m.aW == 1 && (uintptr_t)m.alpha % 16 == 0 && m.aH % V == 0;
+    // where torch rounds an fp16 product once (stitch_mix_kernel's comment): from the last, partial block of 2048 elements of the dense (C, H, W) result on; the input's
+    // product everywhere unless the input has a unit column stride and a 16-byte aligned base -- the image itself or its padded copy, which torch sees as a dense tensor
+    m.once_from = (long long)a.C * a.out_h * a.out_w / 2048 * 2048;
+    m.q_once = f16 && !(m.sW == 1 && (uintptr_t)m.inp % 16 == 0);
+    if (m.quant == 0.f) return f16 ? launch_stitch_mix_t<half_t, half_t>(a, m, planes, s) : launch_stitch_mix_t<float, float>(a, m, planes, s);
+    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s);
+    return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -174,8 +174,8 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // (off_on_host: uploaded once per distinct table, then kept on the plan -- e.g. a receive buffer's layout) on the host.  band: NULL = the whole canvas, else
 // {row0, row1, strip}: the rows of tile rows [row0, row1) only, strip != 0 with tile row row1 present as the strips of its blend band.
 // edge: NULL = `out` is the canvas (C, rows, out_w) of out_dtype; else `out` is the quantised interleaved image (out_h, out_w, C) of out_dtype MOE_U8 / MOE_U16
-// (moe_stitch_out: the whole canvas only).
-struct OutEdge { int canvas_dtype; float quant; };
+// (moe_stitch_out: the whole canvas only); with mix the DN step's blend and alpha ride in the fold too (moe_stitch_mix: canvas or samples, mix->quant says which).
+struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; };
 static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
                   const OutEdge* edge = nullptr)
 {
@@ -226,6 +226,10 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
             a.row_tab = tab;
         }
     }
+    if (edge && edge->mix) {
+        if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
+        return launched("stitch_mix");
+    }
     if (edge) {
         if (!launch_stitch_out(a, edge->canvas_dtype, edge->quant, s)) return fail(MOE_EINVAL, "moe_stitch_out: %d planes (1 to 4 are supported)", C);
         return launched("stitch_out");
@@ -246,7 +250,25 @@ static int out_edge_args(const char* who, int planes, int canvas_dtype, int bits
     return MOE_OK;
 }
 
-// moe_run_plan_ex, and moe_run_plan_out = the same with the final fold writing the quantised image (edge)
+// What moe_stitch_mix and moe_run_plan_filter check of their edge before any device call, and the edge itself.  planes: the net's; inp: the image the blend reads.
+static int mix_edge_args(const char* who, const Plan& p, int planes, const void* inp, int inp_dtype, int64_t sC, int64_t sH, int64_t sW, const void* alpha, int64_t aH, int64_t aW,
+                         double strength, int bits, const void* dst, int dst_dtype, StitchMix* m)
+{
+    if (!inp || !dst) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (p.sc != 1) return fail(MOE_EINVAL, "%s: plan scale %d (the blend with the input needs a plan of scale 1)", who, p.sc);
+    if (bits != 0 && bits != 8 && bits != 16) return fail(MOE_EINVAL, "%s: %d bits (0 = the canvas, 8 or 16)", who, bits);
+    if (inp_dtype != MOE_F32 && inp_dtype != MOE_F16) return fail(MOE_EINVAL, "%s: canvas dtype (the input's) must be MOE_F32 or MOE_F16", who);
+    if (bits == 0 && dst_dtype != inp_dtype) return fail(MOE_EINVAL, "%s: dst dtype must be the input's for the canvas form (bits = 0)", who);
+    if (bits != 0 && dst_dtype != MOE_U8 && dst_dtype != MOE_U16) return fail(MOE_EINVAL, "%s: dst dtype must be MOE_U8 or MOE_U16 for %d bits", who, bits);
+    if (bits > 8 && dst_dtype == MOE_U8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
+    if (planes < 1 || planes + (alpha ? 1 : 0) > 4) return fail(MOE_EINVAL, "%s: %d planes%s (1 to 4 in all are supported)", who, planes, alpha ? " + alpha" : "");
+    if (!std::isfinite(strength)) return fail(MOE_EINVAL, "%s: strength must be finite", who);
+    // strengthOp (python/imageProcess.py:562): x itself for s == 1, else s * x + (1 - s) * inp with the two Python floats handed to the device as fp32
+    *m = StitchMix{inp, sC, sH, sW, alpha, aH, aW, (float)strength, (float)(1.0 - strength), strength != 1.0, bits ? (float)(1 << bits) : 0.f, 0, 0, 0, 0};
+    return MOE_OK;
+}
+
+// moe_run_plan_ex, and moe_run_plan_out / moe_run_plan_filter = the same with the final fold writing the quantised image / the DN step's result (edge)
 static int run_plan(const char* who, moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                     void* out, int out_dtype, int max_tiles, float* pool, int shard_index, int shard_count, int do_stitch, void* stream, const OutEdge* edge)
 {
@@ -438,6 +460,17 @@ int moe_stitch_out(const moe_plan* p, int device, const float* tiles_dev, const 
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
+int moe_stitch_mix(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, const void* inp, int inp_dtype, int64_t sC, int64_t sH, int64_t sW,
+                   const void* alpha, int64_t aH, int64_t aW, double strength, int bits, void* dst, int dst_dtype, void* stream)
+{
+    if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_mix: NULL argument");
+    StitchMix m{};
+    const int rc = mix_edge_args("moe_stitch_mix", p->p, C, inp, inp_dtype, sC, sH, sW, alpha, aH, aW, strength, bits, dst, dst_dtype, &m);
+    if (rc) return rc;
+    const OutEdge edge{inp_dtype, m.quant, &m};
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
+}
+
 int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int64_t c_sC, int64_t c_sH, int dtype, int C,
                    int top_sc, int left_sc, int bsc, int rsc, int topT, int leftT, int pad_sc, const void* ramp, void* stream)
 {
@@ -476,6 +509,17 @@ int moe_run_plan_out(moe_net* n, const moe_plan* pl, const void* img, int img_dt
     if (rc) return rc;
     const OutEdge edge{canvas_dtype, (float)(1 << bits)};
     return run_plan("moe_run_plan_out", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
+}
+
+int moe_run_plan_filter(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW, const void* alpha, int64_t aH, int64_t aW,
+                        double strength, int bits, void* dst, int dst_dtype, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_filter: NULL argument");
+    StitchMix m{};
+    const int rc = mix_edge_args("moe_run_plan_filter", pl->p, pl->p.C, img, img_dtype, sC, sH, sW, alpha, aH, aW, strength, bits, dst, dst_dtype, &m);
+    if (rc) return rc;
+    const OutEdge edge{img_dtype, m.quant, &m};
+    return run_plan("moe_run_plan_filter", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
 int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,

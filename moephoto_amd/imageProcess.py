@@ -7,7 +7,7 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   prepare / getAnchors / TilePlan      :19-35, 73-118   -> C planner (moe_plan_create)
   prepareOpt, doCrop                   :133-172         -> moe_run_plan (tile gather, net, stitch on device)
   ensemble, trans/transInv             :563-572         -> moe_run_plan_ens (symmetry + pad, doCrop, fold + average on device)
-  RGBFilter, strengthOp, alpha helpers :350-377, 562
+  RGBFilter, strengthOp, alpha helpers :350-377, 562   -> moe_run_plan_filter (blend with the input and alpha inside the final fold)
   toTorch / toFloat / toOutput         :238-263         -> moe_to_float / moe_to_output kernels
   readFile / writeFile                 :265-302         (PIL, host)
 
@@ -15,6 +15,7 @@ There is no CPU path: models must be moephoto_amd.models.EngineModule instances 
 """
 import ctypes
 import logging
+import math
 import time
 from functools import reduce
 
@@ -257,8 +258,9 @@ def _outStorage(bitDepth):
     return (torch.uint8, np.uint8, _lib.U8) if bitDepth == 8 else (torch.int16, np.uint16, _lib.U16)
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None):
-    """doCrop and doCropOut: the checks, the plan, the pad, the call (moe_run_plan, or with bitDepth moe_run_plan_out) and its one retry after a MemoryError."""
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None):
+    """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
+    alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold) and its one retry after a MemoryError."""
     model = opt.modelCached
     if not isinstance(model, EngineModule):
         raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
@@ -274,6 +276,14 @@ def _runPlan(who, opt, x, bitDepth=None, out=None):
         xp = xp.to(config.dtype())
     model.to(device=x.device)
     C = xp.shape[0]
+    if mix is not None:
+        strength, alpha = float(mix[0]), mix[1]
+        if alpha is not None:
+            if alpha.dim() != 2 or alpha.shape[0] < plan.outH or alpha.shape[1] < plan.outW or alpha.device != x.device:
+                raise ValueError('{}: the alpha plane must be (H, W) on {}'.format(who, x.device))
+            alpha = alpha.to(xp.dtype)
+            C += 1
+        aH, aW = alpha.stride() if alpha is not None else (0, 0)
     if bitDepth is None:
         out = xp.new_empty((C, plan.outH, plan.outW))
     elif out is None:
@@ -285,7 +295,10 @@ def _runPlan(who, opt, x, bitDepth=None, out=None):
     L = _lib.lib()
 
     def run():
-        if bitDepth is None:
+        if mix is not None:        # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
+            _lib.check(L.moe_run_plan_filter(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
+                                             strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
+        elif bitDepth is None:
             _lib.check(L.moe_run_plan(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, out.data_ptr(), _DT[out.dtype], int(config.tilesPerBatch), stream))
         else:          # the canvas doCrop would have returned has xp's dtype: its rounding is applied before the quantiser
             _lib.check(L.moe_run_plan_out(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(bitDepth),
@@ -297,6 +310,8 @@ def _runPlan(who, opt, x, bitDepth=None, out=None):
         run()
     # the engine reads xp asynchronously: keep it alive until the stream has consumed it
     xp.record_stream(torch.cuda.current_stream(x.device))
+    if mix is not None and alpha is not None:
+        alpha.record_stream(torch.cuda.current_stream(x.device))
     return out
 
 
@@ -505,12 +520,32 @@ def mergeAlpha(t):
     return f
 
 
+def _finite(s):
+    return isinstance(s, (int, float)) and math.isfinite(s)
+
+
 def _RGBFilter(opt, img):
     """The DN wrapper (python/imageProcess.py:350-377): the denoiser sees the colour planes only, `strength` blends its result
-    with the input, alpha rides around it."""
+    with the input, alpha rides around it.  With config.filterOnDevice the blend and the alpha plane are the final fold's own work (moe_run_plan_filter: one call, no
+    temporaries, no concatenation) whenever there is something to blend or to carry; the torch expressions below are the other form of the same bits.  The image
+    must be dense and 16-byte aligned, as every image of the pipeline is: torch rounds the fp16 products of a strided view differently (stitch_mix_kernel's comment)."""
     alpha = {}
     rgb = opt.prepare(extractAlpha(alpha)(img))
+    if (config.filterOnDevice and isinstance(opt.modelCached, EngineModule) and rgb.device.type == 'cuda' and rgb.dtype in _DT and rgb.dim() == 3
+            and rgb.is_contiguous() and rgb.data_ptr() % 16 == 0 and _finite(opt.strength) and (opt.strength != 1 or 'im' in alpha)):
+        return _runPlan('RGBFilter', opt, rgb, mix=(opt.strength, alpha.get('im')))
     return mergeAlpha(alpha)(strengthOp(doCrop(opt, rgb), rgb, opt.strength))
+
+
+def filterOut(opt, img, bitDepth, out=None):
+    """toOutput(bitDepth)(toFloat(_RGBFilter(opt, img))) without the download, as ONE call (moe_run_plan_filter), as doCropOut is to doCrop: the final fold blends each
+    pixel with the input, rounds as the canvas of img's dtype would have and writes the quantised (H, W, C) image, alpha included; neither the canvas nor its fp32
+    copy exists.  strength must be finite.  out: as doCropOut's."""
+    if not _finite(opt.strength):
+        raise ValueError('filterOut: strength must be finite, got {!r}'.format(opt.strength))
+    alpha = {}
+    rgb = opt.prepare(extractAlpha(alpha)(img))
+    return _runPlan('filterOut', opt, rgb, bitDepth, out, mix=(opt.strength, alpha.get('im')))
 
 
 RGBFilter = lambda opt: lambda img: _RGBFilter(opt, img)

@@ -14,12 +14,13 @@ steps.  Ops other than file / buffer / DN / SR / resize / output belong to other
 `genFrameStream(steps, width, height, depth)` builds the same chain for a video source as a ring of `depth` frames in flight -- upload, compute and download on
 three queues, the last fold writing the encoder's samples itself (imageProcess.doCropOut) -- and `runFramesStreamed` is `runFrames` over it.
 """
+import math
 import time
 from functools import reduce
 
 from . import _lib, runDN, runSR
 from .config import config
-from .imageProcess import RGBFilter, apply, doCropOut, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toTorch, writeFile, _DT, _outStorage
+from .imageProcess import RGBFilter, apply, doCropOut, filterOut, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toTorch, writeFile, _DT, _outStorage
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -291,8 +292,9 @@ def _quantiseInto(bitDepth):
 def genFrameStream(steps, width, height, depth=2, timing=False):
     """genProcess for a video source as a stream: `steps` as genProcess takes them, steps[0] = {'op': 'buffer', 'bitDepth': 8 | 16}; frames are width x height x 3.
     Returns a FrameStream: push(raw) -> list of finished frames' bytes (input order; [] for an empty buffer), flush(), close(), nodes.  The last compute step decides
-    the output edge: an SR without ensemble or a DN of strength 1 folds its tiles straight into the encoder's samples (doCropOut: the canvas never exists); after a
-    resize, a DN blended with its input or an ensemble the step's result is quantised in place.  Same bytes as genProcess + runFrames either way."""
+    the output edge, named by the stream's `edge`: 'crop' -- an SR without ensemble or a DN of strength 1 folds its tiles straight into the encoder's samples
+    (doCropOut: the canvas never exists); 'filter' -- a DN of any other finite strength does the same with the blend inside the fold (filterOut, under
+    config.filterOnDevice); 'quantise' -- after a resize, an ensemble or otherwise the step's result is quantised in place.  Same bytes as genProcess + runFrames."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
@@ -302,7 +304,7 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
     for opt in work:
         if opt['op'] not in stepOpts:
             raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(opt['op']))
-    funcs, nodes, edge = [], [], None
+    funcs, nodes, edge, edgeName = [], [], None, 'quantise'
     h, w = int(height), int(width)
     for k, opt in enumerate(work):
         op, last = opt['op'], k == len(work) - 1
@@ -323,17 +325,21 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
             if not opt['scale'] > 1:
                 raise TypeError('Invalid scale setting for SR.')
             if last and o.ensemble == 0:
-                edge = lambda x, out, o=o: doCropOut(o, x, bitDepth, out)
+                edge, edgeName = (lambda x, out, o=o: doCropOut(o, x, bitDepth, out)), 'crop'
             else:
                 funcs.append(runSR.sr(o))
             h, w = h * opt['scale'], w * opt['scale']
         elif last and o.strength == 1:         # RGBFilter on three planes with nothing to blend: prepare, doCrop
-            edge = lambda x, out, o=o: doCropOut(o, o.prepare(x), bitDepth, out)
+            edge, edgeName = (lambda x, out, o=o: doCropOut(o, o.prepare(x), bitDepth, out)), 'crop'
+        elif last and config.filterOnDevice and isinstance(o.strength, (int, float)) and math.isfinite(o.strength):      # the blend with the frame inside the fold
+            edge, edgeName = (lambda x, out, o=o: filterOut(o, x, bitDepth, out)), 'filter'
         else:
             funcs.append(RGBFilter(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
     backend = _DeviceBackend(funcs, edge or _quantiseInto(bitDepth), bitDepth, width, height, (h, w), depth, timing)
-    return FrameStream(backend, width, height, bitDepth, depth, nodes)
+    stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
+    stream.edge = edgeName
+    return stream
 
 
 def runFramesStreamed(stream, read, write, start=0, stop=-1):
