@@ -1,5 +1,5 @@
 // misc_kernels.hip -- the HBM-bound kernels around the MFMA convolution: 1->C stem, C->1 tail (+branch sum),
-// squeeze-excite pooling / gates, tile stitch, and the uint8/uint16 <-> float image edges.
+// squeeze-excite pooling / gates, and the uint8/uint16 <-> float image edges.
 // All of them stream NHWC fp16 activations with 16-byte accesses (8 lanes = one 128-B pixel line).
 #include "common.h"
 #include <algorithm>
@@ -1076,171 +1076,6 @@ __global__ __launch_bounds__(256) void frm_apply_kernel(FrmArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Stitch: per-pixel fold of doCrop's sequential blend (imageProcess.py:120-131,167-170).  Every HR pixel visits,
-// in raster tile order, the tiles whose written region covers it and applies
-//     v1 = ex + wH*(r-ex)  (row inside the tile's blend band, else r);   v = ex + wW*(v1-ex)  (column likewise)
-// with the same fp32 operation order as the reference, so the result is bit-identical to the sequential loop.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float stitch_pixel(const StitchArgs& a, int X, int Y, int c)
-{
-    const int i0 = a.row_first[Y], ni = a.row_cnt[Y];
-    const int j0 = a.col_first[X], nj = a.col_cnt[X];
-    float cur = 0.f;
-    for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {      // (row_lo: a band starts at the solid part of its first tile row, which overwrites whatever the rows above wrote)
-        const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
-        for (int j = j0; j < j0 + nj; ++j) {
-            const int fx = a.col_tab[j * 4 + 0], sx = a.col_tab[j * 4 + 1], ox = a.col_tab[j * 4 + 2], ew = a.col_tab[j * 4 + 3];
-            const float r = a.tiles[a.tile_off[i * a.step_w + j] + ((long long)c * eh + (Y - oy)) * ew + (X - ox)];
-            float v1 = r;
-            if (Y < sy) v1 = cur + a.ramp[Y - fy] * (r - cur);
-            float v = v1;
-            if (X < sx) v = cur + a.ramp[X - fx] * (v1 - cur);
-            cur = v;
-        }
-    }
-    return cur;
-}
-
-__global__ __launch_bounds__(256) void stitch_kernel(StitchArgs a)
-{
-    const int X = blockIdx.x * 256 + threadIdx.x;
-    const int Y = blockIdx.y + a.y0, c = blockIdx.z;
-    if (X >= a.out_w) return;
-    const float cur = stitch_pixel(a, X, Y, c);
-    const long long o = ((long long)c * a.rows + (Y - a.y0)) * a.out_w + X;
-    if (a.out_dtype == MOE_F16) ((half_t*)a.out)[o] = (half_t)cur;
-    else ((float*)a.out)[o] = cur;
-}
-
-// Four consecutive pixels per thread (out_w % 4 == 0).  Almost every quad lies inside one tile's solid region: then the fold is
-// the identity on that tile's value and the quad is one 16-byte load and one 8/16-byte store; the others take the exact
-// per-pixel fold above.  (One pixel per thread: 465 us per 8K frame; this: 350; eight rows per thread was slower again.)
-__global__ __launch_bounds__(256) void stitch4_kernel(StitchArgs a)
-{
-    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    const int Y = blockIdx.y + a.y0, c = blockIdx.z;
-    if (X0 >= a.out_w) return;
-    float v[4];
-    const int i0 = a.row_first[Y], j0 = a.col_first[X0];
-    bool fast = a.row_cnt[Y] == 1 && a.col_cnt[X0] == 1 && a.col_cnt[X0 + 3] == 1 && a.col_first[X0 + 3] == j0;
-    if (fast) {
-        const int sy = a.row_tab[i0 * 4 + 1], oy = a.row_tab[i0 * 4 + 2], eh = a.row_tab[i0 * 4 + 3];
-        const int sx = a.col_tab[j0 * 4 + 1], ox = a.col_tab[j0 * 4 + 2], ew = a.col_tab[j0 * 4 + 3];
-        const long long o = a.tile_off[i0 * a.step_w + j0] + ((long long)c * eh + (Y - oy)) * ew + (X0 - ox);
-        fast = Y >= sy && X0 >= sx && (o & 3) == 0;
-        if (fast) {
-            const float4 q = *(const float4*)(a.tiles + o);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        }
-    }
-    if (!fast) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = stitch_pixel(a, X0 + e, Y, c);
-    }
-    const long long o = ((long long)c * a.rows + (Y - a.y0)) * a.out_w + X0;
-    if (a.out_dtype == MOE_F16) {
-        half4_t h;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) h[e] = (half_t)v[e];
-        *(half4_t*)((half_t*)a.out + o) = h;
-    } else {
-        *(float4*)((float*)a.out + o) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-// R rows x eight consecutive pixels per thread (out_w % 8 == 0, at most 64 tile columns).  History of this kernel on the 8K / 32K canvas:
-// one pixel per thread 465 us; four pixels (stitch4 above) 350 us -- a chain of four dependent table loads per thread (col_first -> col_tab
-// -> tile_off -> tile data) for 16 bytes of payload; eight pixels with the column table staged in LDS and a block-uniform row side
-// 388 us / 4.46 ms = 1.6 / 2.1 TB/s; this form 1.88 ms on the 32K canvas = 5.1 TB/s.  What the last step removed: (1) a block lived for one
-// chain of dependent loads and moved 12 KB with it -- now a block takes R rows, so one chain carries R x 2 independent 16-byte loads per
-// thread; (2) seam ROWS (two covering tile rows: 4 % of the rows) sent every thread through the per-pixel fold -- now a thread whose eight
-// columns lie in the solid part of ONE tile column folds the covering tile rows as vectors (the reference's order per pixel: cur = r, or
-// cur + ramp (r - cur) inside the tile's blend band, python/imageProcess.py:120-131, so the result stays bit-identical to the sequential
-// loop); (3) a thread on a COLUMN seam walked its 8 pixels one after the other, ~5 dependent loads each, and held its wave meanwhile --
-// every fourth wave of a 2048-px tile column; now such threads only enlist their group and the whole block folds the seam pixels one
-// pixel per thread.
-template <int R>
-__global__ __launch_bounds__(256) void stitch8r_kernel(StitchArgs a)
-{
-    __shared__ int s_col[64 * 4];
-    __shared__ int s_seam[256];
-    __shared__ int s_nseam;
-    const int Y0 = blockIdx.y * R + a.y0, c = blockIdx.z;
-    const int yend = a.y0 + a.rows;                       // (a band of the canvas: moe_stitch_band; the whole canvas: y0 = 0, rows = out_h)
-    const int nsw = a.step_w;
-    for (int t = threadIdx.x; t < nsw * 4; t += 256) s_col[t] = a.col_tab[t];
-    if (threadIdx.x == 0) s_nseam = 0;
-    __syncthreads();
-    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
-    if (X0 < a.out_w) {
-        const int j0 = a.col_first[X0], j7 = a.col_first[X0 + 7];
-        bool colfast = a.col_cnt[X0] == 1 && a.col_cnt[X0 + 7] == 1 && j0 == j7;
-        const int sx = s_col[j0 * 4 + 1], ox = s_col[j0 * 4 + 2], ew = s_col[j0 * 4 + 3];
-        colfast = colfast && X0 >= sx;
-        if (!colfast) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;      // eight columns on a seam: handed to the whole block below
-        else {
-            float v[R][8];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int Y = min(Y0 + r, yend - 1);               // (rows past the band repeat the last one and are not stored)
-                const int i0 = a.row_first[Y], ni = a.row_cnt[Y];  // block-uniform
-                float cur[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {
-                    const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
-                    const long long o = a.tile_off[i * nsw + j0] + ((long long)c * eh + (Y - oy)) * ew + (X0 - ox);
-                    float q[8];
-                    if ((o & 3) == 0) {
-                        const float4 q0 = *(const float4*)(a.tiles + o), q1 = *(const float4*)(a.tiles + o + 4);
-                        q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) q[e] = a.tiles[o + e];
-                    }
-                    if (Y < sy) {
-                        const float wgt = a.ramp[Y - fy];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) cur[e] = cur[e] + wgt * (q[e] - cur[e]);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) cur[e] = q[e];
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[r][e] = cur[e];
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (Y0 + r >= yend) break;
-                const long long o = ((long long)c * a.rows + (Y0 + r - a.y0)) * a.out_w + X0;
-                if (a.out_dtype == MOE_F16) {
-                    half8_t h;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) h[e] = (half_t)v[r][e];
-                    *(half8_t*)((half_t*)a.out + o) = h;
-                } else {
-                    *(float4*)((float*)a.out + o) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
-                    *(float4*)((float*)a.out + o + 4) = make_float4(v[r][4], v[r][5], v[r][6], v[r][7]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // column seams: one pixel per thread and pass, the exact per-pixel fold (a thread walking its own 8 x R seam pixels one after the other
-    // held its wave for 32 chains of dependent loads: every fourth wave of a 2048-px tile column)
-    const int total = s_nseam * 8 * R;
-    for (int t = threadIdx.x; t < total; t += 256) {
-        const int gidx = t / (8 * R), rem = t - gidx * 8 * R;
-        const int r = rem >> 3, e = rem & 7;
-        const int X = (blockIdx.x * 256 + s_seam[gidx]) * 8 + e, Y = Y0 + r;
-        if (Y >= yend) continue;
-        const float cur = stitch_pixel(a, X, Y, c);
-        const long long o = ((long long)c * a.rows + (Y - a.y0)) * a.out_w + X;
-        if (a.out_dtype == MOE_F16) ((half_t*)a.out)[o] = (half_t)cur;
-        else ((float*)a.out)[o] = cur;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // Image edges: toTorch (imageProcess.py:259-263) and toOutput (:245-257)
 // ---------------------------------------------------------------------------------------------------
 template <typename TS, typename TD>
@@ -1312,309 +1147,6 @@ __global__ __launch_bounds__(256) void to_output3_kernel(const TS* __restrict__ 
         }
     }
     *(VecN<TD, 24>*)(dst + p0 * 3) = o;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Stitch straight into the encoder's bytes (moe_stitch_out): the fold above, the rounding of the canvas dtype and to_output_kernel's quantiser in one pass -- the pool is
-// read once and the interleaved u8 / u16 image written once; the fp16 / fp32 canvas and its fp32 copy (stitch -> toFloat -> toOutput: 17-18 bytes per pixel-plane) never
-// exist.  The shape of stitch8r_kernel with the planes inside the thread: one thread = R rows x 8 consecutive pixels x ALL C planes, so what it writes per row is one
-// contiguous run of 8 * C elements.  A thread whose eight columns lie in the solid part of ONE tile column folds the covering tile rows as vectors (one row outside a
-// blend band: the identity on that tile's values); threads on a column seam and the ragged end of a row (any out_w) enlist their group and the whole block folds those
-// pixels one per thread with stitch_pixel.  Per element the operations of the three passes in their order, so the bytes are theirs.  (Times of this form and of the
-// one-row-per-thread form before it, on the 8K frame beside the three passes: profiles/frame_stream/summary.md.)
-// ---------------------------------------------------------------------------------------------------
-template <typename TD, int C> struct alignas((sizeof(TD) * 8 * C) % 16 == 0 ? 16 : 8) StitchOutRun { TD e[8 * C]; };
-
-template <typename TD>
-__device__ __forceinline__ TD stitch_out_quant(float v, bool f16, float quant)
-{
-    if (f16) v = (float)(half_t)v;                       // what the fp16 canvas held
-    v = v * quant;                                       // to_output_kernel: image * quant, clamp_(0, quant - 1), truncate
-    v = fminf(fmaxf(v, 0.f), quant - 1.f);
-    if (!(v == v)) v = 0.f;
-    return (TD)(int)v;
-}
-
-template <typename TD, int C, int R>
-__global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float quant, int f16)
-{
-    __shared__ int s_seam[256];
-    __shared__ int s_nseam;
-    if (threadIdx.x == 0) s_nseam = 0;
-    __syncthreads();
-    const int Y0 = blockIdx.y * R;
-    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
-    TD* const dst = (TD*)a.out;
-    if (X0 < a.out_w) {
-        bool colfast = X0 + 8 <= a.out_w;
-        int j0 = 0, ox = 0, ew = 0;
-        if (colfast) {
-            j0 = a.col_first[X0];
-            colfast = a.col_cnt[X0] == 1 && a.col_cnt[X0 + 7] == 1 && a.col_first[X0 + 7] == j0;
-            const int sx = a.col_tab[j0 * 4 + 1];
-            ox = a.col_tab[j0 * 4 + 2]; ew = a.col_tab[j0 * 4 + 3];
-            colfast = colfast && X0 >= sx;
-        }
-        if (!colfast) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;      // a column seam or the row's ragged end: handed to the whole block below
-        else {
-            StitchOutRun<TD, C> o[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int Y = min(Y0 + r, a.out_h - 1);            // (rows past the canvas repeat the last one and are not stored)
-                const int i0 = a.row_first[Y], ni = a.row_cnt[Y];  // block-uniform
-                float cur[C][8];
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) cur[c][e] = 0.f;
-                for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {
-                    const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
-                    const long long o0 = a.tile_off[i * a.step_w + j0] + (long long)(Y - oy) * ew + (X0 - ox), plane = (long long)eh * ew;
-                    const bool band = Y < sy;
-                    const float wgt = band ? a.ramp[Y - fy] : 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const long long t = o0 + c * plane;
-                        float q[8];
-                        if ((t & 3) == 0) {
-                            const float4 q0 = *(const float4*)(a.tiles + t), q1 = *(const float4*)(a.tiles + t + 4);
-                            q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) q[e] = a.tiles[t + e];
-                        }
-                        if (band) {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) cur[c][e] = cur[c][e] + wgt * (q[e] - cur[c][e]);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) cur[c][e] = q[e];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[r].e[e * C + c] = stitch_out_quant<TD>(cur[c][e], f16 != 0, quant);
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (Y0 + r >= a.out_h) break;
-                TD* p = dst + ((long long)(Y0 + r) * a.out_w + X0) * C;
-                if (((uintptr_t)p & (alignof(StitchOutRun<TD, C>) - 1)) == 0) *(StitchOutRun<TD, C>*)p = o[r];
-                else {
-#pragma unroll
-                    for (int k = 0; k < 8 * C; ++k) p[k] = o[r].e[k];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int total = s_nseam * (8 * R * C);
-    for (int t = threadIdx.x; t < total; t += 256) {
-        const int gidx = t / (8 * R * C), rem = t - gidx * (8 * R * C);
-        const int r = rem / (8 * C), ec = rem - r * (8 * C);
-        const int e = ec / C, c = ec - e * C;
-        const int X = (blockIdx.x * 256 + s_seam[gidx]) * 8 + e, Y = Y0 + r;
-        if (Y >= a.out_h || X >= a.out_w) continue;
-        dst[((long long)Y * a.out_w + X) * C + c] = stitch_out_quant<TD>(stitch_pixel(a, X, Y, c), f16 != 0, quant);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The DN step's edge in the stitch (moe_stitch_mix; plans of scale 1): RGBFilter's passes behind doCrop -- strengthOp's s * x + (1 - s) * inp and the alpha plane that
-// rides around the net (python/imageProcess.py:350-377,562) -- inside the fold above, and, in the sample form, toFloat / toOutput (:238-257) behind them.  Per
-// pixel-plane, in T = the canvas dtype, as torch evaluates the expression on device tensors (scalars as fp32, every intermediate tensor in T):
-//     c = T(fold);   y = T( T(sf * c) + T(tf * inp) );   strength 1: y = c (strengthOp returns x itself)
-// The two products and the sum are three separately rounded fp32 operations: the empty asm statements keep each product in its register, so neither is fused into
-// the sum (an FMA rounds once) nor, for fp16, into its own conversion (v_fma_mixlo_f16 rounds the exact product once; sym.hip's closing average met the same).  The
-// fp32 sum of two fp16 values followed by its rounding to fp16 is the correctly rounded sum either way (24 >= 2 * 11 + 2 bits).
-// Where torch itself rounds an fp16 product ONCE, so does this kernel (measured on torch 2.10, profiles/filter/summary.md): its vectorised elementwise kernel
-// takes a dense tensor in blocks of 2048 elements and the last, partial block runs through other code, in which the compiler did pick v_fma_mixlo_f16 -- as it did in
-// the kernel that serves strided views.  So element i of the (C, H, W) result has its products rounded once when i >= once_from = the start of that last block, and
-// the input's product everywhere when the input is a view torch would not vectorise (m.q_once).  0.2 - 3 % of such elements differ by one fp16 ulp between the forms.
-// Shape: stitch_out_kernel's -- one thread = R rows (4, or 1 on small canvases: launch_stitch_mix_t) x 8 pixels x all CT output planes, seam and ragged-row threads hand their pixels to the block.  Planes [0, a.C) are
-// the net's; plane a.C (when CT > a.C) is alpha, copied.  TD == T: the canvas form, dst = (CT, out_h, out_w) planes; else the sample form, dst = (out_h, out_w, CT)
-// interleaved through to_output_kernel's quantiser.  inp / alpha are read through element strides, as 16-byte vectors where m.inp_vec / m.alpha_vec say they may be.
-// ---------------------------------------------------------------------------------------------------
-// T(h * f): the product rounded to fp32, then to T
-template <typename T>
-__device__ __forceinline__ T stitch_mix_mul(T h, float f)
-{
-#pragma clang fp contract(off)
-    float p = __fmul_rn(f, (float)h);
-    asm("" : "+v"(p));
-    return (T)p;
-}
-
-// fp16(h * f) with ONE rounding of the exact product: v_fma_mixlo_f16 with h read as fp16 from the low half of its register, f and the addend -0 as fp32
-__device__ __forceinline__ half_t stitch_mix_mul_once(half_t h, float f)
-{
-    unsigned r;
-    const unsigned hb = __builtin_bit_cast(unsigned short, h);
-    const float nz = -0.0f;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hb), "v"(f), "v"(nz));
-    return __builtin_bit_cast(half_t, (unsigned short)(r & 0xffffu));
-}
-__device__ __forceinline__ float stitch_mix_mul_once(float h, float f) { return stitch_mix_mul<float>(h, f); }      // (fp32: a product has one rounding anyway)
-
-template <typename T>
-__device__ __forceinline__ T stitch_mix_value(float cur, T inp, float sf, float tf, bool p_once, bool q_once)
-{
-#pragma clang fp contract(off)
-    const T c = (T)cur;
-    const T hp = p_once ? stitch_mix_mul_once(c, sf) : stitch_mix_mul<T>(c, sf);
-    const T hq = q_once ? stitch_mix_mul_once(inp, tf) : stitch_mix_mul<T>(inp, tf);
-    return (T)__fadd_rn((float)hp, (float)hq);
-}
-
-template <typename T>
-__device__ __forceinline__ void stitch_mix_load8(const T* p, long long sW, bool vec, T (&v)[8])
-{
-    if (vec) {
-        typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
-        constexpr int N = 16 / sizeof(T);
-#pragma unroll
-        for (int k = 0; k < 8 / N; ++k) {
-            const vec_t q = *(const vec_t*)(p + k * N);
-#pragma unroll
-            for (int e = 0; e < N; ++e) v[k * N + e] = q[e];
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = p[e * sW];
-    }
-}
-
-template <typename T, typename TD, int CT, int R>
-__global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix m)
-{
-    constexpr bool SAMPLE = !std::is_same<T, TD>::value;
-    __shared__ int s_seam[256];
-    __shared__ int s_nseam;
-    if (threadIdx.x == 0) s_nseam = 0;
-    __syncthreads();
-    const int Y0 = blockIdx.y * R;
-    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
-    const int nC = a.C;
-    const T* const inp = (const T*)m.inp;
-    const T* const alpha = (const T*)m.alpha;
-    TD* const dst = (TD*)a.out;
-    const long long out_plane = (long long)a.out_h * a.out_w;
-    if (X0 < a.out_w) {
-        bool colfast = X0 + 8 <= a.out_w;
-        int j0 = 0, ox = 0, ew = 0;
-        if (colfast) {
-            j0 = a.col_first[X0];
-            colfast = a.col_cnt[X0] == 1 && a.col_cnt[X0 + 7] == 1 && a.col_first[X0 + 7] == j0;
-            const int sx = a.col_tab[j0 * 4 + 1];
-            ox = a.col_tab[j0 * 4 + 2]; ew = a.col_tab[j0 * 4 + 3];
-            colfast = colfast && X0 >= sx;
-        }
-        if (!colfast) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;      // a column seam or the row's ragged end: handed to the whole block below
-        else {
-            typename std::conditional<SAMPLE, StitchOutRun<TD, CT>, VecN<T, 8 * CT>>::type o[R];      // sample form: e[pixel * CT + plane]; canvas form: e[plane * 8 + pixel]
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int Y = min(Y0 + r, a.out_h - 1);            // (rows past the canvas repeat the last one and are not stored)
-                const int i0 = a.row_first[Y], ni = a.row_cnt[Y];  // block-uniform
-                float cur[CT][8];
-#pragma unroll
-                for (int c = 0; c < CT; ++c)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) cur[c][e] = 0.f;
-                for (int i = max(i0, a.row_lo); i < i0 + ni; ++i) {
-                    const int fy = a.row_tab[i * 4 + 0], sy = a.row_tab[i * 4 + 1], oy = a.row_tab[i * 4 + 2], eh = a.row_tab[i * 4 + 3];
-                    const long long o0 = a.tile_off[i * a.step_w + j0] + (long long)(Y - oy) * ew + (X0 - ox), plane = (long long)eh * ew;
-                    const bool band = Y < sy;
-                    const float wgt = band ? a.ramp[Y - fy] : 0.f;
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        if (c >= nC) break;
-                        const long long t = o0 + c * plane;
-                        float q[8];
-                        if ((t & 3) == 0) {
-                            const float4 q0 = *(const float4*)(a.tiles + t), q1 = *(const float4*)(a.tiles + t + 4);
-                            q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) q[e] = a.tiles[t + e];
-                        }
-                        if (band) {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) cur[c][e] = cur[c][e] + wgt * (q[e] - cur[c][e]);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) cur[c][e] = q[e];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    T y[8];
-                    if (c >= nC) stitch_mix_load8(alpha + Y * m.aH + X0 * m.aW, m.aW, m.alpha_vec != 0, y);
-                    else if (m.blend) {
-                        const long long left = sizeof(T) == 2 ? m.once_from - (((long long)c * a.out_h + Y) * a.out_w + X0) : 8;      // elements of the run in front of once_from
-                        stitch_mix_load8(inp + c * m.sC + Y * m.sH + X0 * m.sW, m.sW, m.inp_vec != 0, y);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) y[e] = stitch_mix_value<T>(cur[c][e], y[e], m.sf, m.tf, e >= left, e >= left || m.q_once);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) y[e] = (T)cur[c][e];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        if constexpr (SAMPLE) o[r].e[e * CT + c] = stitch_out_quant<TD>((float)y[e], false, m.quant);
-                        else o[r].e[c * 8 + e] = y[e];
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (Y0 + r >= a.out_h) break;
-                if constexpr (SAMPLE) {
-                    TD* p = dst + ((long long)(Y0 + r) * a.out_w + X0) * CT;
-                    if (((uintptr_t)p & (alignof(StitchOutRun<TD, CT>) - 1)) == 0) *(StitchOutRun<TD, CT>*)p = o[r];
-                    else {
-#pragma unroll
-                        for (int k = 0; k < 8 * CT; ++k) p[k] = o[r].e[k];
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        T* p = dst + c * out_plane + (long long)(Y0 + r) * a.out_w + X0;
-                        if (((uintptr_t)p & 15) == 0) {
-                            VecN<T, 8> v;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v.e[e] = o[r].e[c * 8 + e];
-                            *(VecN<T, 8>*)p = v;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) p[e] = o[r].e[c * 8 + e];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int total = s_nseam * (8 * R * CT);
-    for (int t = threadIdx.x; t < total; t += 256) {
-        const int gidx = t / (8 * R * CT), rem = t - gidx * (8 * R * CT);
-        const int r = rem / (8 * CT), ec = rem - r * (8 * CT);
-        const int e = ec / CT, c = ec - e * CT;
-        const int X = (blockIdx.x * 256 + s_seam[gidx]) * 8 + e, Y = Y0 + r;
-        if (Y >= a.out_h || X >= a.out_w) continue;
-        T y;
-        if (c >= nC) y = alpha[Y * m.aH + X * m.aW];
-        else {
-            const float cur = stitch_pixel(a, X, Y, c);
-            const bool p_once = sizeof(T) == 2 && ((long long)c * a.out_h + Y) * a.out_w + X >= m.once_from;
-            y = m.blend ? stitch_mix_value<T>(cur, inp[c * m.sC + Y * m.sH + X * m.sW], m.sf, m.tf, p_once, p_once || m.q_once) : (T)cur;
-        }
-        if constexpr (SAMPLE) dst[((long long)Y * a.out_w + X) * CT + c] = stitch_out_quant<TD>((float)y, false, m.quant);
-        else dst[c * out_plane + (long long)Y * a.out_w + X] = y;
-    }
 }
 
 __global__ void nhwc_to_nchw_kernel(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C)
@@ -1718,75 +1250,8 @@ void launch_frm_pre(const FrmPreArgs& a, hipStream_t s)
     hipLaunchKernelGGL(frm_pre_kernel, dim3(a.B), dim3(256), 0, s, a);
 }
 
-void launch_stitch(const StitchArgs& a, hipStream_t s)
-{
-    if (a.rows <= 0) return;
-    if (a.out_w % 8 == 0 && a.step_w <= 64 && ((uintptr_t)a.out & 15) == 0) hipLaunchKernelGGL(stitch8r_kernel<4>, dim3((a.out_w / 8 + 255) / 256, (a.rows + 3) / 4, a.C), dim3(256), 0, s, a);
-    else if (a.out_w % 4 == 0 && ((uintptr_t)a.out & 15) == 0) hipLaunchKernelGGL(stitch4_kernel, dim3((a.out_w / 4 + 255) / 256, a.rows, a.C), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(stitch_kernel, dim3((a.out_w + 255) / 256, a.rows, a.C), dim3(256), 0, s, a);
-}
-
-template <typename TD>
-static bool launch_stitch_out_t(const StitchArgs& a, float quant, int f16, hipStream_t s)
-{
-    constexpr int R = 4;          // rows per thread (stitch8r_kernel's)
-    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
-    if (a.C == 1) hipLaunchKernelGGL((stitch_out_kernel<TD, 1, R>), g, dim3(256), 0, s, a, quant, f16);
-    else if (a.C == 2) hipLaunchKernelGGL((stitch_out_kernel<TD, 2, R>), g, dim3(256), 0, s, a, quant, f16);
-    else if (a.C == 3) hipLaunchKernelGGL((stitch_out_kernel<TD, 3, R>), g, dim3(256), 0, s, a, quant, f16);
-    else if (a.C == 4) hipLaunchKernelGGL((stitch_out_kernel<TD, 4, R>), g, dim3(256), 0, s, a, quant, f16);
-    else return false;
-    return true;
-}
-
-// a.out: (out_h, out_w, C) interleaved, a.out_dtype MOE_U8 / MOE_U16; the whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
-bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s)
-{
-    const int f16 = canvas_dtype == MOE_F16;
-    return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s) : launch_stitch_out_t<uint16_t>(a, quant, f16, s);
-}
-
-template <typename T, typename TD, int R>
-static bool launch_stitch_mix_r(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
-{
-    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
-    if (planes == 1) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 1, R>), g, dim3(256), 0, s, a, m);
-    else if (planes == 2) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 2, R>), g, dim3(256), 0, s, a, m);
-    else if (planes == 3) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m);
-    else if (planes == 4) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m);
-    else return false;
-    return true;
-}
-
-// Rows per thread: stitch_out_kernel's four where that still gives the device a few waves per SIMD (a 4K canvas and larger); one row on smaller canvases -- a DN
-// step's 1080p frame is 270 workgroups of four rows on 256 CUs, one wave per SIMD waiting out its own loads (times of both: profiles/filter/summary.md).
-template <typename T, typename TD>
-static bool launch_stitch_mix_t(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
-{
-    const long long blocks4 = (long long)(((a.out_w + 7) / 8 + 255) / 256) * ((a.out_h + 3) / 4);
-    return blocks4 >= 1024 ? launch_stitch_mix_r<T, TD, 4>(a, m, planes, s) : launch_stitch_mix_r<T, TD, 1>(a, m, planes, s);
-}
-
-// a.C: the net's planes; with m.alpha one more plane is written.  m.quant == 0: a.out = the canvas (planes, out_h, out_w) of canvas_dtype; else a.out = interleaved
-// (out_h, out_w, planes) of a.out_dtype MOE_U8 / MOE_U16.  The whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
-bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s)
-{
-    const int planes = a.C + (m.alpha ? 1 : 0);
-    const bool f16 = canvas_dtype == MOE_F16;
-    const long long V = f16 ? 8 : 4;          // elements of a 16-byte vector: base, plane and row pitch must be multiples of it
-    m.inp_vec = m.sW == 1 && (uintptr_t)m.inp % 16 == 0 && m.sC % V == 0 && m.sH % V == 0;
-    m.alpha_vec = m.alpha && m.aW == 1 && (uintptr_t)m.alpha % 16 == 0 && m.aH % V == 0;
-    // where torch rounds an fp16 product once (stitch_mix_kernel's comment): from the last, partial block of 2048 elements of the dense (C, H, W) result on; the input's
-    // product everywhere unless the input has a unit column stride and a 16-byte aligned base -- the image itself or its padded copy, which torch sees as a dense tensor
-    m.once_from = (long long)a.C * a.out_h * a.out_w / 2048 * 2048;
-    m.q_once = f16 && !(m.sW == 1 && (uintptr_t)m.inp % 16 == 0);
-    if (m.quant == 0.f) return f16 ? launch_stitch_mix_t<half_t, half_t>(a, m, planes, s) : launch_stitch_mix_t<float, float>(a, m, planes, s);
-    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s);
-    return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s);
-}
-
 // ---------------------------------------------------------------------------------------------------
-// Wire format of tile results between ranks (moephoto_amd/dist.py, wire = 'f16s').  The stitch reads a tile's value at full precision only where
+// Wire format of tile results between ranks (moephoto_amd/dist.py, wire = 'f16s').  The fold of the tiles into the canvas reads a tile's value at full precision only where
 // a blend happens (the tile's own blend band, and the rows / columns a LATER tile blends over: python/imageProcess.py:120-131); everywhere else the
 // value either is the canvas pixel (then it is rounded to the canvas dtype) or is overwritten.  So a tile travels as the fp16 image of all its
 // values plus the fp32 values of its seam rows and seam columns, and unpacking gives back fp32 tiles whose seams are exact and whose interior is

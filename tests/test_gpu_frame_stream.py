@@ -112,6 +112,55 @@ def test_stitch_out_with_a_permuted_pool_layout(dev):
     assert torch.equal(got, want) and torch.equal(got, plain)
 
 
+def _stitch(pl, C, pool_d, dt, dev, out=None):
+    from moephoto_amd import _lib
+    if out is None:
+        out = torch.empty((C, pl.outH, pl.outW), dtype=dt, device=dev)
+    _lib.check(_lib.lib().moe_stitch(pl._h, 0, pool_d.data_ptr(), None, C, out.data_ptr(), _lib.F16 if dt == torch.float16 else _lib.F32, torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+@pytest.mark.parametrize('width', [1100, 1104])
+def test_stitch_of_more_than_64_tile_columns(width, dev):
+    """92 tile columns x 2 tile rows (the column table of a block no longer has a size): the canvas against the oracle's fold, the fp16 canvas and the samples against
+    the fp32 canvas.  Width 1100 ends every row on a ragged run of four pixels, 1104 on a whole run of eight."""
+    from oracle import planner as oplanner, stitch as ostitch
+    params = ((2, 24, width), 1, 2, 8, 16)
+    pl, C, pool_d, off = _plan_and_pool(params, dev)
+    opl = oplanner.prepare(params[0], 1 << 40, 1e-3, 2, 1, 8, 16)
+    assert pl.stepW > 64 and (pl.stepW, pl.stepH, pl.n_tiles) == (92, 2, 184) and (opl.step_w, opl.step_h) == (92, 2) and pl.outW % 8 == width % 8
+    f32 = _stitch(pl, C, pool_d, torch.float32, dev)
+    f16 = _stitch(pl, C, pool_d, torch.float16, dev)
+    want = _three_passes(pl, C, pool_d, None, torch.float16, 16, dev)
+    got = _stitch_out(pl, C, pool_d, None, torch.float16, 16, dev)
+    torch.cuda.synchronize()
+    hp = pool_d.cpu().numpy()
+    tiles = [hp[off[k]:off[k] + C * (t[1] - t[0]) * (t[3] - t[2])].reshape(C, t[1] - t[0], t[3] - t[2]) for k, t in enumerate(pl.tiles)]
+    err = float(np.abs(f32.cpu().numpy() - ostitch.fold_stitch(tiles, opl, 1)).max())
+    print('width {}: max abs error against the oracle fold {:.3e}'.format(width, err))
+    assert err <= 1e-6
+    assert torch.equal(f16, f32.half())
+    assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize('name', sorted(PLANS))
+def test_stitch_fp16_canvas_is_the_rounded_fp32_canvas_dense_and_unaligned(name, dev):
+    """The canvas edge on every width and base: the fp16 canvas is the fp32 canvas rounded, written into a dense tensor and into one that starts one element past a
+    16-byte boundary (no row of it can take a vector store); the elements in front of and behind the canvas stay as they were."""
+    pl, C, pool_d, _ = _plan_and_pool(PLANS[name], dev)
+    want = _stitch(pl, C, pool_d, torch.float32, dev).half()
+    dense = _stitch(pl, C, pool_d, torch.float16, dev)
+    n = C * pl.outH * pl.outW
+    flat = torch.full((n + 2,), 7.0, dtype=torch.float16, device=dev)
+    assert flat.data_ptr() % 16 == 0
+    shifted = _stitch(pl, C, pool_d, torch.float16, dev, out=flat[1:n + 1].view(C, pl.outH, pl.outW))
+    torch.cuda.synchronize()
+    assert shifted.data_ptr() % 16 == 2
+    assert torch.equal(dense, want)
+    assert torch.equal(shifted, want)
+    assert flat[0].item() == 7.0 and flat[n + 1].item() == 7.0
+
+
 # ---- 2. doCropOut -------------------------------------------------------------------------------------------------------------------------
 def _configure(fp16, crop):
     from moephoto_amd.config import config

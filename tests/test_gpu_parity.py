@@ -1429,7 +1429,7 @@ def test_stitch_band_equals_rows_of_the_canvas(dev):
     dist.TileExchange.cut_strips does), must equal the same rows of moe_stitch's canvas bit for bit -- including the re-anchored last tile row."""
     import ctypes
     from moephoto_amd import _lib, imageProcess as ip
-    for (H, W, crop, scale, model) in ((150, 200, 64, 4, 'a'), (293, 120, 96, 2, 'a')):
+    for (H, W, crop, scale, model) in ((150, 200, 64, 4, 'a'), (293, 120, 96, 2, 'a'), (150, 101, 64, 2, 'a')):      # (the last: a canvas width of 202, no multiple of 8)
         opt = _opt_sr(model, scale, crop, fp16_io=True)
         xd = torch.from_numpy(gd.natural_image(3, (3, H, W))).to(dev).half()
         plan = ip._plan_for(opt, xd.shape)
