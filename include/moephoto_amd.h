@@ -286,6 +286,25 @@ int moe_run_plan_ex(moe_net* net, const moe_plan* plan, const void* img, int img
 int moe_run_plan_out(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                      int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
 
+/* ---- the encoder's planar Y'CbCr 4:2:0 frame ------------------------------------------------------------
+ * The reference fixes the pixel format of its output pipe to bgr24 / bgr48le (python/video.py:24,219,230) and the encoder converts every frame on the CPU.  These
+ * entry points write the encoder's own planes instead: limited-range Y'CbCr at `depth` 8 (uint8 planes), 10, 12 or 16 bits (little-endian uint16 planes), 4:2:0 with
+ * centre siting, the Y plane (out_h x out_w), then Cb, then Cr (ceil(out_h / 2) x ceil(out_w / 2) each), contiguous -- ffmpeg's rawvideo yuv420p, yuv420p10le,
+ * yuv420p12le, yuv420p16le.  Per pixel the three samples are first taken at 16 bits exactly as moe_stitch_out / moe_to_output give them with bits = 16 (the canvas
+ * dtype's rounding, * 65536, clamp, truncate, NaN = 0); the integer conversion behind them is defined in moephoto_amd/pixfmt.py (14-bit coefficients, a chroma sample
+ * from the sums of its 2 x 2 block, the edge pixel repeated on odd sizes).  Three planes only.  dst: any 2-byte aligned address (any address for depth 8). */
+#define MOE_YUV_BT709 0
+#define MOE_YUV_BT601 1
+#define MOE_YUV_BT2020NC 2
+#define MOE_ORDER_BGR 0        /* plane 0 is blue: the video path's frames */
+#define MOE_ORDER_RGB 1
+/* moe_stitch_out's fold with that frame behind it, for a plan of three planes; tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+int moe_stitch_yuv(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int canvas_dtype, int depth, int matrix, int order,
+                   void* dst, void* stream);
+/* moe_run_plan_out with its final fold replaced by moe_stitch_yuv. */
+int moe_run_plan_yuv(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     int canvas_dtype, int depth, int matrix, int order, void* dst, int max_tiles_per_batch, void* stream);
+
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
  * alpha, strength, bits, dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */
@@ -345,6 +364,8 @@ int moe_run_plan_ens(moe_net* net, const moe_plan* plan, const moe_plan* plan_t,
 int moe_to_float(const void* src, int src_dtype, int bits, int H, int W, int C, void* dst, int dst_dtype, int device, void* stream);
 /* src: C planes H x W (MOE_F32/MOE_F16); dst: H x W x C interleaved, v*2^bits clamped to [0, 2^bits-1], truncated */
 int moe_to_output(const void* src, int src_dtype, int H, int W, int C, int bits, void* dst, int dst_dtype, int device, void* stream);
+/* src: three planes H x W (MOE_F32/MOE_F16); dst: the Y'CbCr 4:2:0 frame of moe_stitch_yuv, from the samples moe_to_output gives with bits = 16 */
+int moe_to_yuv(const void* src, int src_dtype, int H, int W, int depth, int matrix, int order, void* dst, int device, void* stream);
 
 /* the pipeline's `resize` step: resizeByTorch = F.interpolate(x[None], size=(h, w), mode, align_corners=False)
  * (python/imageProcess.py:174-195, 555-556; python/procedure.py:104-107).  src: C planes H x W, dst: C planes h x w, same dtype

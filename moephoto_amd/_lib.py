@@ -88,6 +88,9 @@ def lib():
         'moe_stitch': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_vp]),
         'moe_stitch_out': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp]),
         'moe_run_plan_out': (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp]),
+        'moe_stitch_yuv': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+        'moe_run_plan_yuv': (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+        'moe_to_yuv': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
         'moe_stitch_mix': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_dbl, c_int, c_vp, c_int, c_vp]),
         'moe_run_plan_filter': (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp]),
         'moe_run_plan': (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp]),
@@ -114,7 +117,8 @@ EXPORTS = ['moe_last_error', 'moe_abi_version', 'moe_device_count', 'moe_net_cre
            'moe_net_num_params', 'moe_net_param_info', 'moe_net_set_param', 'moe_net_finalize', 'moe_net_resolved_precision', 'moe_net_calibrate', 'moe_net_exact_blocks', 'moe_net_workspace_bytes',
            'moe_net_max_tile_pixels', 'moe_net_forward', 'moe_net_forward_ex', 'moe_net_set_profile', 'moe_net_get_profile', 'moe_net_get_profile_at', 'moe_net_set_exact_blocks', 'moe_net_set_debug', 'moe_net_set_option', 'moe_device_info', 'moe_blend_tile', 'moe_stitch_dev', 'moe_stitch_band', 'moe_net_debug_tap', 'moe_plan_create', 'moe_plan_destroy', 'moe_plan_info',
            'moe_plan_tiles', 'moe_plan_ramp', 'moe_plan_rows', 'moe_plan_seams', 'moe_wire_words', 'moe_wire_pack', 'moe_wire_unpack', 'moe_plan_pool_elems', 'moe_plan_tile_offsets', 'moe_stitch', 'moe_run_plan',
-           'moe_run_plan_ex', 'moe_run_plan_frames', 'moe_run_plan_tiles', 'moe_sym_pad', 'moe_sym_fold', 'moe_run_plan_ens', 'moe_stitch_out', 'moe_run_plan_out', 'moe_stitch_mix', 'moe_run_plan_filter', 'moe_to_float', 'moe_to_output', 'moe_resize']
+           'moe_run_plan_ex', 'moe_run_plan_frames', 'moe_run_plan_tiles', 'moe_sym_pad', 'moe_sym_fold', 'moe_run_plan_ens', 'moe_stitch_out', 'moe_run_plan_out', 'moe_stitch_mix', 'moe_run_plan_filter', 'moe_to_float', 'moe_to_output', 'moe_resize',
+           'moe_stitch_yuv', 'moe_run_plan_yuv', 'moe_to_yuv']
 
 
 def check(rc):

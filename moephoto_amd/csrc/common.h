@@ -458,6 +458,16 @@ struct StitchMix {
     long long once_from; int q_once;                 // set by launch_stitch_mix, fp16: from this element of the (C, H, W) result on / for inp everywhere a product is rounded once, as torch's kernels do
 };
 bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s);
+// The encoder's planar Y'CbCr 4:2:0 frame behind the fold (stitch_yuv_kernel) or behind three dense planes (to_output_yuv_kernel); the definition: moephoto_amd/pixfmt.py.
+// dst = the Y plane H x W, then Cb, then Cr of ceil(H / 2) x ceil(W / 2), uint8 (depth 8) or uint16.  The shifts of the definition are folded into the multipliers:
+// (L 219 + 2^(37 - D)) >> (38 - D) = (L (219 << (D - 6)) + 2^31) >> 32, the high word of one 32 x 32 + 64 bit multiply-add; chroma likewise with 224 << (D - 8).
+struct YuvEdge {
+    int ky[3], ku[3], kv[3];                         // the 14-bit coefficients of the Y, Cb and Cr rows per PLANE (order bgr: plane 0 is blue)
+    unsigned mul_y, base_y; int mul_c, base_c;       // 219 << (D - 6), 16 << (D - 8);  224 << (D - 8), 128 << (D - 8)
+    int depth, f16;                                  // D;  the samples are taken from the value rounded to fp16 (what an fp16 canvas held)
+};
+void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s);      // C = 3, the whole canvas; a.out = the frame
+void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s);
 
 // blend.hip: the two blend() calls + slice-assign of doCrop's loop body for ONE tile, in the canvas dtype (moe_blend_tile)
 struct BlendTileArgs {

@@ -174,8 +174,9 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // (off_on_host: uploaded once per distinct table, then kept on the plan -- e.g. a receive buffer's layout) on the host.  band: NULL = the whole canvas, else
 // {row0, row1, strip}: the rows of tile rows [row0, row1) only, strip != 0 with tile row row1 present as the strips of its blend band.
 // edge: NULL = `out` is the canvas (C, rows, out_w) of out_dtype; else `out` is the quantised interleaved image (out_h, out_w, C) of out_dtype MOE_U8 / MOE_U16
-// (moe_stitch_out: the whole canvas only); with mix the DN step's blend and alpha ride in the fold too (moe_stitch_mix: canvas or samples, mix->quant says which).
-struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; };
+// (moe_stitch_out: the whole canvas only); with mix the DN step's blend and alpha ride in the fold too (moe_stitch_mix: canvas or samples, mix->quant says which);
+// with yuv `out` is the planar Y'CbCr 4:2:0 frame (moe_stitch_yuv: three planes, the whole canvas).
+struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; };
 static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
                   const OutEdge* edge = nullptr)
 {
@@ -226,6 +227,10 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
             a.row_tab = tab;
         }
     }
+    if (edge && edge->yuv) {
+        launch_stitch_yuv(a, *edge->yuv, s);
+        return launched("stitch_yuv");
+    }
     if (edge && edge->mix) {
         if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
         return launched("stitch_mix");
@@ -247,6 +252,29 @@ static int out_edge_args(const char* who, int planes, int canvas_dtype, int bits
     if (bits != 8 && bits != 16) return fail(MOE_EINVAL, "%s: %d bits (8 or 16)", who, bits);
     if (dst_dtype != MOE_U8 && dst_dtype != MOE_U16) return fail(MOE_EINVAL, "%s: dst dtype must be MOE_U8 or MOE_U16", who);
     if (dst_dtype == MOE_U8 && bits > 8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
+    return MOE_OK;
+}
+
+// What moe_stitch_yuv, moe_run_plan_yuv and moe_to_yuv check of their edge before any device call, and the edge itself.  planes: the plan's C (moe_to_yuv: 3).
+// The coefficient tables are moephoto_amd/pixfmt.py's, per matrix the Y, Cb and Cr rows over (R, G, B).
+static int yuv_edge_args(const char* who, int planes, int dtype, int depth, int matrix, int order, const void* dst, YuvEdge* y)
+{
+    static const int tab[3][3][3] = {{{3483, 11718, 1183}, {-1877, -6315, 8192}, {8192, -7441, -751}},        // MOE_YUV_BT709
+                                     {{4899, 9617, 1868}, {-2765, -5427, 8192}, {8192, -6860, -1332}},        // MOE_YUV_BT601
+                                     {{4304, 11108, 972}, {-2288, -5904, 8192}, {8192, -7533, -659}}};        // MOE_YUV_BT2020NC
+    if (!dst) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (planes != 3) return fail(MOE_EINVAL, "%s: the plan has %d planes (C must be 3)", who, planes);
+    if (dtype != MOE_F32 && dtype != MOE_F16) return fail(MOE_EINVAL, "%s: canvas dtype must be MOE_F32 or MOE_F16", who);
+    if (depth != 8 && depth != 10 && depth != 12 && depth != 16) return fail(MOE_EINVAL, "%s: depth %d (8, 10, 12 or 16)", who, depth);
+    if (matrix < MOE_YUV_BT709 || matrix > MOE_YUV_BT2020NC) return fail(MOE_EINVAL, "%s: unknown matrix %d", who, matrix);
+    if (order != MOE_ORDER_BGR && order != MOE_ORDER_RGB) return fail(MOE_EINVAL, "%s: unknown order %d", who, order);
+    for (int p = 0; p < 3; ++p) {
+        const int colour = order == MOE_ORDER_BGR ? 2 - p : p;
+        y->ky[p] = tab[matrix][0][colour]; y->ku[p] = tab[matrix][1][colour]; y->kv[p] = tab[matrix][2][colour];
+    }
+    y->mul_y = 219u << (depth - 6); y->base_y = 16u << (depth - 8);
+    y->mul_c = 224 << (depth - 8); y->base_c = 128 << (depth - 8);
+    y->depth = depth; y->f16 = dtype == MOE_F16;
     return MOE_OK;
 }
 
@@ -471,6 +499,17 @@ int moe_stitch_mix(const moe_plan* p, int device, const float* tiles_dev, const 
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
+int moe_stitch_yuv(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int canvas_dtype, int depth, int matrix, int order, void* dst, void* stream)
+{
+    if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_yuv: NULL argument");
+    YuvEdge y{};
+    const int rc = yuv_edge_args("moe_stitch_yuv", p->p.C, canvas_dtype, depth, matrix, order, dst, &y);
+    if (rc) return rc;
+    OutEdge edge{canvas_dtype, 0.f};
+    edge.yuv = &y;
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, 3, dst, depth == 8 ? MOE_U8 : MOE_U16, nullptr, (hipStream_t)stream, &edge);
+}
+
 int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int64_t c_sC, int64_t c_sH, int dtype, int C,
                    int top_sc, int left_sc, int bsc, int rsc, int topT, int leftT, int pad_sc, const void* ramp, void* stream)
 {
@@ -509,6 +548,18 @@ int moe_run_plan_out(moe_net* n, const moe_plan* pl, const void* img, int img_dt
     if (rc) return rc;
     const OutEdge edge{canvas_dtype, (float)(1 << bits)};
     return run_plan("moe_run_plan_out", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
+}
+
+int moe_run_plan_yuv(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                     int canvas_dtype, int depth, int matrix, int order, void* dst, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_yuv: NULL argument");
+    YuvEdge y{};
+    const int rc = yuv_edge_args("moe_run_plan_yuv", pl->p.C, canvas_dtype, depth, matrix, order, dst, &y);
+    if (rc) return rc;
+    OutEdge edge{canvas_dtype, 0.f};
+    edge.yuv = &y;
+    return run_plan("moe_run_plan_yuv", n, pl, img, img_dtype, sC, sH, sW, dst, depth == 8 ? MOE_U8 : MOE_U16, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
 int moe_run_plan_filter(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW, const void* alpha, int64_t aH, int64_t aW,
@@ -711,6 +762,19 @@ int moe_to_output(const void* src, int src_dtype, int H, int W, int C, int bits,
     HIP_TRY(hipSetDevice(device));
     launch_to_output(src, src_dtype, H, W, C, (float)(1 << bits), dst, dst_dtype, (hipStream_t)stream);
     return MOE_OK;
+}
+
+int moe_to_yuv(const void* src, int src_dtype, int H, int W, int depth, int matrix, int order, void* dst, int device, void* stream)
+{
+    if (!src) return fail(MOE_EINVAL, "moe_to_yuv: NULL argument");
+    if (H < 1 || W < 1) return fail(MOE_EINVAL, "moe_to_yuv: size %d x %d must be positive", H, W);
+    YuvEdge y{};
+    const int rc = yuv_edge_args("moe_to_yuv", 3, src_dtype, depth, matrix, order, dst, &y);
+    if (rc) return rc;
+    y.f16 = 0;      // (the planes are the canvas: their values are converted as they are)
+    HIP_TRY(hipSetDevice(device));
+    launch_to_output_yuv(src, src_dtype, H, W, y, dst, (hipStream_t)stream);
+    return launched("to_output_yuv");
 }
 
 }  // extern "C"

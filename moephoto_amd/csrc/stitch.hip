@@ -1,4 +1,5 @@
-// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_mix): one skeleton, three edges.
+// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv): one skeleton, three edges on
+// it and the Y'CbCr 4:2:0 edge over the same fold with a body of its own (chroma needs row pairs).
 //
 // Stitch: per-pixel fold of doCrop's sequential blend (imageProcess.py:120-131,167-170).  Every HR pixel visits,
 // in raster tile order, the tiles whose written region covers it and applies
@@ -9,6 +10,7 @@
 //     CanvasEdge     the (C, rows, out_w) planes of the fp16 / fp32 canvas, or a band of its rows                                       stitch8r_kernel
 //     SamplesEdge    the encoder's interleaved u8 / u16 samples: the canvas dtype's rounding and to_output_kernel's quantiser            stitch_out_kernel
 //     MixEdge        the DN step: strengthOp's blend with the image the net saw and the alpha plane, in canvas or sample form            stitch_mix_kernel
+//     (YuvEdge)      the encoder's planar Y'CbCr 4:2:0 frame from SamplesEdge's 16-bit samples: half the bytes of the interleaved image      stitch_yuv_kernel
 // The fold itself (stitch_classify, stitch_fold_row, stitch_pixel) exists once, so the bit equalities the tests demand between the edges (moe_stitch_out == moe_stitch ->
 // float -> quantise, moe_stitch_mix == stitch + torch) hold by construction.  This file is compiled without extra flags: the fold's cur + w (q - cur) contracts to one FMA.
 #include "common.h"
@@ -98,7 +100,8 @@ __device__ __forceinline__ StitchFold<NP> stitch_fold_row(const StitchArgs& a, c
 // A run of N elements a thread writes at once: aligned vector stores where the address allows it, element by element elsewhere (a canvas whose width is not a
 // multiple of 8, a base in the middle of a buffer).  The vector path stores words, not the struct: a struct copy is taken apart into element stores, the ones that
 // equal the fallback's are then sunk behind the branch, and the "vector" path keeps 16-byte stores for part of the run only (samples of the 8K canvas: 257 us for 211).
-template <typename T, int N> struct alignas((sizeof(T) * N) % 16 == 0 ? 16 : 8) StitchRun { T e[N]; };
+// (a run of four bytes -- four u8 chroma samples -- is one word)
+template <typename T, int N> struct alignas((sizeof(T) * N) % 16 == 0 ? 16 : (sizeof(T) * N) % 8 == 0 ? 8 : 4) StitchRun { T e[N]; };
 
 template <typename T, int N>
 __device__ __forceinline__ void stitch_store(T* p, const StitchRun<T, N>& v)
@@ -379,6 +382,192 @@ __global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix
     stitch_fold<R>(a, MixEdge<T, TD, CT>{m});
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The encoder's planar Y'CbCr 4:2:0 frame (moe_stitch_yuv, moe_to_yuv; the definition: moephoto_amd/pixfmt.py).  Per pixel the three planes are taken at 16 bits by
+// SamplesEdge's quantiser -- the samples moe_stitch_out / moe_to_output write with bits = 16 -- and the conversion behind them is integer: Y per pixel, Cb and Cr from
+// the sums of a 2 x 2 block.  The frame is 1.5 samples per pixel instead of 3: half the writes, half the download.
+// stitch_yuv_kernel is the fold's fourth edge with a body of its own: the skeleton's hooks are per row and a chroma sample needs a row pair.  A vector-path thread
+// owns 8 columns x R rows x 3 planes with X0 a multiple of 8 and Y0 a multiple of R (even), so no 2 x 2 block straddles two threads: it writes R runs of eight Y, R / 2
+// runs of four Cb and of four Cr.  min(Y0 + r, out_h - 1) is the replication of the last row of an odd canvas.  Seam groups and the ragged row end go through the
+// per-pixel fold one sample per thread, then one 2 x 2 block per thread; the odd last column is replicated there.  The Cb / Cr bases are aligned only by luck: every
+// run goes through stitch_store.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned yuv_luma(const YuvEdge& y, unsigned p0, unsigned p1, unsigned p2)
+{
+    // < 2^30: the coefficients are positive and sum to 2^14.  24-bit multiplies (samples of 16 bits, coefficients of 14): v_mad_u32_u24 runs at the full rate, a
+    // 32-bit v_mul_lo_u32 at a quarter of it -- with 32-bit products this edge was 216.9 us on the 8K canvas beside the sample edge's 203.1 (profiles/yuv/summary.md)
+    const unsigned L = __umul24(y.ky[0], p0) + __umul24(y.ky[1], p1) + __umul24(y.ky[2], p2);
+    return y.base_y + (unsigned)(((unsigned long long)L * y.mul_y + 0x80000000ull) >> 32);             // one v_mad_u64_u32, its high word
+}
+
+// s0..s2: the planes' sums over the block, four samples each.  |M| <= 2^13 * 4 * 65535 < 2^31 whatever the order of the terms (the positive and the negative
+// coefficients of a chroma row each sum to 2^13 in magnitude).
+__device__ __forceinline__ unsigned yuv_chroma(const int (&k)[3], const YuvEdge& y, int s0, int s1, int s2)
+{
+    const int M = __mul24(k[0], s0) + __mul24(k[1], s1) + __mul24(k[2], s2);                             // (|k| <= 2^13, sums < 2^18: signed 24-bit factors)
+    return (unsigned)(y.base_c + (int)(((long long)M * y.mul_c + 0x80000000ll) >> 32));                 // (>> 32 of the signed sum: the floor shift of the definition)
+}
+
+__device__ __forceinline__ int yuv_sample16(float v, bool f16) { return stitch_out_quant<uint16_t>(v, f16, 65536.f); }
+
+template <typename TD, int R>
+__global__ __launch_bounds__(256) void stitch_yuv_kernel(StitchArgs a, YuvEdge y)
+{
+    static_assert(R % 2 == 0, "a thread owns whole row pairs");
+    __shared__ int s_seam[256];
+    __shared__ int s_nseam;
+    if (threadIdx.x == 0) s_nseam = 0;
+    __syncthreads();
+    const int Y0 = blockIdx.y * R, X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
+    const int cw = (a.out_w + 1) / 2, ch = (a.out_h + 1) / 2;
+    TD* const py = (TD*)a.out;
+    TD* const pu = py + (long long)a.out_h * a.out_w;
+    TD* const pv = pu + (long long)ch * cw;
+    const bool f16 = y.f16 != 0;
+    if (X0 < a.out_w) {
+        StitchCols k;
+        if (!stitch_classify(a, X0, k)) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;
+        else {
+            StitchRun<TD, 8> oy[R];
+            StitchRun<TD, 4> ou[R / 2], ov[R / 2];
+            int sum[3][4];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const StitchFold<3> f = stitch_fold_row<3>(a, k, X0, min(Y0 + r, a.out_h - 1), 0, 3);
+                int s[3][8];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[c][e] = yuv_sample16(f.v[c][e], f16);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) oy[r].e[e] = (TD)yuv_luma(y, s[0][e], s[1][e], s[2][e]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sum[c][e] = (r & 1 ? sum[c][e] : 0) + s[c][2 * e] + s[c][2 * e + 1];
+                if (r & 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        ou[r / 2].e[e] = (TD)yuv_chroma(y.ku, y, sum[0][e], sum[1][e], sum[2][e]);
+                        ov[r / 2].e[e] = (TD)yuv_chroma(y.kv, y, sum[0][e], sum[1][e], sum[2][e]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (Y0 + r >= a.out_h) break;
+                stitch_store(py + (long long)(Y0 + r) * a.out_w + X0, oy[r]);
+                if (!(r & 1)) {      // (the pair's second row may be the replicated one: the chroma row exists with the first)
+                    const long long at = (long long)((Y0 + r) / 2) * cw + X0 / 2;
+                    stitch_store(pu + at, ou[r / 2]);
+                    stitch_store(pv + at, ov[r / 2]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // The enlisted groups: 4 * (R / 2) blocks of 2 x 2 pixels each, 12 samples a block.  One thread folds ONE sample (as the other edges' seam pass does: a thread that
+    // walked its block's twelve folds one after the other held the whole workgroup for twelve chains of dependent loads -- 216 us on the 8K canvas for the sample
+    // edge's 203); the samples of 21 blocks meet in LDS and one thread per block converts and writes them.
+    constexpr int PER = 4 * (R / 2), NB = 21;      // blocks of one group: (row pair, block), the block innermost;  blocks per pass: 21 * 12 = 252 threads
+    __shared__ int s_smp[NB * 12];
+    const int nblk = s_nseam * PER, t = threadIdx.x;
+    auto origin = [&](int b, int& xa, int& ya) {
+        const int gidx = b / PER, rem = b - gidx * PER;
+        xa = (blockIdx.x * 256 + s_seam[gidx]) * 8 + (rem % 4) * 2; ya = Y0 + (rem / 4) * 2;
+        return b < nblk && xa < a.out_w && ya < a.out_h;
+    };
+    for (int b0 = 0; b0 < nblk; b0 += NB) {          // (block-uniform)
+        int xa, ya;
+        if (t < NB * 12 && origin(b0 + t / 12, xa, ya)) {
+            const int item = t % 12, c = item % 3, i = item / 6, j = (item / 3) & 1;          // sample (i, j, c) of the block: (row, column, plane), the plane innermost
+            const int X = j ? min(xa + 1, a.out_w - 1) : xa, Y = i ? min(ya + 1, a.out_h - 1) : ya;      // (the odd last column / row: the edge pixel again)
+            s_smp[t] = yuv_sample16(stitch_pixel(a, X, Y, c), f16);
+        }
+        __syncthreads();
+        if (t < NB && origin(b0 + t, xa, ya)) {
+            const int* q = s_smp + t * 12;
+            int sum[3] = {0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int* e = q + (i * 2 + j) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sum[c] += e[c];
+                    if ((i && ya + 1 >= a.out_h) || (j && xa + 1 >= a.out_w)) continue;
+                    py[(long long)(ya + i) * a.out_w + xa + j] = (TD)yuv_luma(y, e[0], e[1], e[2]);
+                }
+            const long long at = (long long)(ya / 2) * cw + xa / 2;
+            pu[at] = (TD)yuv_chroma(y.ku, y, sum[0], sum[1], sum[2]);
+            pv[at] = (TD)yuv_chroma(y.kv, y, sum[0], sum[1], sum[2]);
+        }
+        __syncthreads();
+    }
+}
+
+// The unfused form (moe_to_yuv): three dense planes of H x W -> the same frame, for chains whose last step is a resize, an ensemble or a blended DN.  One thread = one
+// row pair x 8 columns; the samples are to_output_kernel's with bits = 16 (no canvas rounding: the planes are the canvas).
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void to_output_yuv_kernel(const TS* __restrict__ src, TD* __restrict__ dst, int H, int W, YuvEdge y)
+{
+    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8, ya = blockIdx.y * 2;
+    if (X0 >= W) return;
+    const int cw = (W + 1) / 2, ch = (H + 1) / 2;
+    const long long HW = (long long)H * W;
+    TD* const pu = dst + HW;
+    TD* const pv = pu + (long long)ch * cw;
+    const bool whole = X0 + 8 <= W;
+    StitchRun<TD, 8> oy[2];
+    int sum[3][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int Y = min(ya + i, H - 1);
+        int s[3][8];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const TS* p = src + c * HW + (long long)Y * W;
+            TS v[8];
+            if (whole) stitch_mix_load8(p + X0, 1, ((uintptr_t)(p + X0) & 15) == 0, v);
+            else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = p[min(X0 + e, W - 1)];
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[c][e] = yuv_sample16((float)v[e], false);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum[c][e] = (i ? sum[c][e] : 0) + s[c][2 * e] + s[c][2 * e + 1];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) oy[i].e[e] = (TD)yuv_luma(y, s[0][e], s[1][e], s[2][e]);
+    }
+    StitchRun<TD, 4> ou, ov;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        ou.e[e] = (TD)yuv_chroma(y.ku, y, sum[0][e], sum[1][e], sum[2][e]);
+        ov.e[e] = (TD)yuv_chroma(y.kv, y, sum[0][e], sum[1][e], sum[2][e]);
+    }
+    const long long at = (long long)blockIdx.y * cw + X0 / 2;
+    if (whole) {
+        stitch_store(dst + (long long)ya * W + X0, oy[0]);
+        if (ya + 1 < H) stitch_store(dst + (long long)(ya + 1) * W + X0, oy[1]);
+        stitch_store(pu + at, ou);
+        stitch_store(pv + at, ov);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {      // (constant indices: a run indexed by a loop variable is moved to LDS)
+            if (X0 + e >= W) break;
+            dst[(long long)ya * W + X0 + e] = oy[0].e[e];
+            if (ya + 1 < H) dst[(long long)(ya + 1) * W + X0 + e] = oy[1].e[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (X0 + 2 * e >= W) break;
+            pu[at + e] = ou.e[e]; pv[at + e] = ov.e[e];
+        }
+    }
+}
+
 }  // namespace
 
 // One thread takes eight columns: any out_w, any base alignment, any number of tile columns.
@@ -445,4 +634,25 @@ bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipSt
     if (m.quant == 0.f) return f16 ? launch_stitch_mix_t<half_t, half_t>(a, m, planes, s) : launch_stitch_mix_t<float, float>(a, m, planes, s);
     if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s);
     return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s);
+}
+
+// a.out: the Y'CbCr 4:2:0 frame of a.out_h x a.out_w (uint8 for depth 8, else uint16); three planes, the whole canvas (y0 = 0, rows = out_h, row_lo = 0)
+void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s)
+{
+    constexpr int R = 4;          // rows per thread (the sample edge's): two chroma rows
+    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
+    if (y.depth == 8) hipLaunchKernelGGL((stitch_yuv_kernel<uint8_t, R>), g, dim3(256), 0, s, a, y);
+    else hipLaunchKernelGGL((stitch_yuv_kernel<uint16_t, R>), g, dim3(256), 0, s, a, y);
+}
+
+void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s)
+{
+    const dim3 g(((W + 7) / 8 + 255) / 256, (H + 1) / 2);
+    if (src_dtype == MOE_F16) {
+        if (y.depth == 8) hipLaunchKernelGGL((to_output_yuv_kernel<half_t, uint8_t>), g, dim3(256), 0, s, (const half_t*)src, (uint8_t*)dst, H, W, y);
+        else hipLaunchKernelGGL((to_output_yuv_kernel<half_t, uint16_t>), g, dim3(256), 0, s, (const half_t*)src, (uint16_t*)dst, H, W, y);
+    } else {
+        if (y.depth == 8) hipLaunchKernelGGL((to_output_yuv_kernel<float, uint8_t>), g, dim3(256), 0, s, (const float*)src, (uint8_t*)dst, H, W, y);
+        else hipLaunchKernelGGL((to_output_yuv_kernel<float, uint16_t>), g, dim3(256), 0, s, (const float*)src, (uint16_t*)dst, H, W, y);
+    }
 }

@@ -9,6 +9,7 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   ensemble, trans/transInv             :563-572         -> moe_run_plan_ens (symmetry + pad, doCrop, fold + average on device)
   RGBFilter, strengthOp, alpha helpers :350-377, 562   -> moe_run_plan_filter (blend with the input and alpha inside the final fold)
   toTorch / toFloat / toOutput         :238-263         -> moe_to_float / moe_to_output kernels
+  doCropYuv, toYuv                     (python/video.py:24,219,230 fix the pipe to bgr24 / bgr48le) -> moe_run_plan_yuv / moe_to_yuv: the encoder's 4:2:0 planes
   readFile / writeFile                 :265-302         (PIL, host)
 
 There is no CPU path: models must be moephoto_amd.models.EngineModule instances on a HIP device.
@@ -23,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, pixfmt
 from .config import config
 from .models import EngineModule
 from .weights import load_state_dict_file
@@ -258,9 +259,20 @@ def _outStorage(bitDepth):
     return (torch.uint8, np.uint8, _lib.U8) if bitDepth == 8 else (torch.int16, np.uint16, _lib.U16)
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None):
+def _yuvOut(who, fmt, w, h, out, device):
+    """The flat uint8 device tensor a Y'CbCr frame of w x h is written into: `out` checked, or a new one."""
+    n = pixfmt.frameBytes(fmt, w, h)
+    if out is None:
+        return torch.empty((n,), dtype=torch.uint8, device=device)
+    if tuple(out.shape) != (n,) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+        raise ValueError('{}: out must be a flat contiguous uint8 tensor of {} bytes ({} at {} x {}) on {}'.format(who, n, fmt, w, h, device))
+    return out
+
+
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None):
     """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
-    alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold) and its one retry after a MemoryError."""
+    alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold, with yuv = (pixFmt, matrix, order) moe_run_plan_yuv: the
+    encoder's planar frame from the final fold) and its one retry after a MemoryError."""
     model = opt.modelCached
     if not isinstance(model, EngineModule):
         raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
@@ -284,7 +296,12 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None):
             alpha = alpha.to(xp.dtype)
             C += 1
         aH, aW = alpha.stride() if alpha is not None else (0, 0)
-    if bitDepth is None:
+    if yuv is not None:
+        depth, matrix, order = pixfmt.check(*yuv)
+        if C != 3:
+            raise ValueError('{}: a three-plane image expected, got {} planes'.format(who, C))
+        out = _yuvOut(who, yuv[0], plan.outW, plan.outH, out, x.device)
+    elif bitDepth is None:
         out = xp.new_empty((C, plan.outH, plan.outW))
     elif out is None:
         out = torch.empty((plan.outH, plan.outW, C), dtype=out_dt, device=x.device)
@@ -295,7 +312,10 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None):
     L = _lib.lib()
 
     def run():
-        if mix is not None:        # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
+        if yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
+            _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth, matrix, order,
+                                          out.data_ptr(), int(config.tilesPerBatch), stream))
+        elif mix is not None:      # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
             _lib.check(L.moe_run_plan_filter(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
                                              strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
         elif bitDepth is None:
@@ -327,6 +347,14 @@ def doCropOut(opt, x, bitDepth, out=None):
     canvas of x's dtype would have and writes the quantised (H, W, C) image (uint8, or uint16 samples in int16 storage) -- the canvas and its fp32 copy never exist
     (python/imageProcess.py:157-172,238-257).  out: a contiguous device tensor of that shape and dtype to write into (the frame stream's slot buffers), else a new one."""
     return _runPlan('doCropOut', opt, x, bitDepth, out)
+
+
+def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr'):
+    """doCropOut(opt, x, 16) followed by pixfmt.fromSamples16, as ONE call (moe_run_plan_yuv): the final fold writes the encoder's planar Y'CbCr 4:2:0 frame -- fmt one of
+    pixfmt.FORMATS (yuv420p, yuv420p10le, yuv420p12le, yuv420p16le), limited range, matrix bt709 / bt601 / bt2020nc; order says whether plane 0 of x is blue ('bgr', the
+    video path's frames) or red.  Half the bytes of the interleaved image.  Returns a flat uint8 device tensor of pixfmt.frameBytes(fmt, outW, outH); out: one to write into."""
+    pixfmt.check(fmt, matrix, order)
+    return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order))
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------
@@ -608,6 +636,28 @@ def toOutput(bitDepth):
 
 
 toOutput8 = toOutput(8)
+
+
+def toYuv(fmt, matrix='bt709', order='bgr'):
+    """The unfused form of doCropYuv (moe_to_yuv): a (3, H, W) fp16 / fp32 device image -> the flat uint8 device tensor of its Y'CbCr 4:2:0 frame, from the samples
+    toOutput(16)(toFloat(y)) would give.  f(y, out=None); out as doCropYuv's."""
+    depth, mat, ordr = pixfmt.check(fmt, matrix, order)
+
+    def f(y, out=None):
+        if y.device.type != 'cuda':
+            raise _lib.EngineError('toYuv: input must live on a HIP device (moephoto_amd has no CPU path)')
+        if y.dim() != 3 or y.shape[0] != 3:
+            raise ValueError('toYuv expects a (3,H,W) image, got {}'.format(tuple(y.shape)))
+        if y.dtype not in _DT:
+            y = y.float()
+        y = y.contiguous()
+        _, H, W = y.shape
+        out = _yuvOut('toYuv', fmt, W, H, out, y.device)
+        cur = torch.cuda.current_stream(y.device)
+        _lib.check(_lib.lib().moe_to_yuv(y.data_ptr(), _DT[y.dtype], H, W, depth, mat, ordr, out.data_ptr(), y.device.index or 0, cur.cuda_stream))
+        y.record_stream(cur)
+        return out
+    return f
 
 
 def toNumPy(bitDepth):
