@@ -19,8 +19,8 @@
 //                 (steps 0 .. 2), which writes acc[3] / acc[0] for the first time in its steps 2 / 3
 //   everything else (weights resident in AGPR + VGPR, LDS images, raw-buffer DMA / loads / stores, micro-op tables, counted waits) as arsb32.hip.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
-#include <type_traits>
 
 // experiment (tools/mk_variant.sh nolo arsb32c.hip -DA32_NOLO): the low-part stream's descriptors cover nothing -- its loads return zero, its stores are dropped, the
 // instruction stream is the same: what the launch would take without those bytes through HBM (profiles/r03/o_stream_bytes.txt)
@@ -55,17 +55,7 @@ constexpr int ROWB = XW * 128;                 // bytes of a patch row
 constexpr int MBYTES = MH * ROWB;              // 52,224
 constexpr int LDS_BYTES = 2 * XBYTES + MBYTES + 512;      // 159,232 (+512: the ninth 1-KiB piece of the two extra x rows of a range start ends 4 pixels behind m)
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_P, OP_MW, OP_XLO, OP_XHI, OP_RES, OP_SPL, OP_ST, OP_MCP };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[48] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-    constexpr void append(const OpList& o) { for (int i = 0; i < o.n; ++i) { op[n] = o.op[i]; ++n; } }
-};
 constexpr OpList interleave(const OpList& x, const OpList& y)
 {
     OpList r;
@@ -182,7 +172,6 @@ template <bool LO, int KS>
 __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const unsigned mbase = lds0 + 2u * XBYTES;
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
     // 16 (q >> 1) + 8 h' + 4 (q & 1) + e, so that a lane's registers 8g .. 8g+7 are eight consecutive channels = one 16-byte slot) --------------
     half8_t w1[36], w2[36];
     {
-        const int wi = lane & 31, wq = wi >> 3;
+        const int wi = lane & 31, wq = wi >> 3;      // (weight_row of mfma_stream.h, spelled out: through the helper this kernel's instruction order changes)
         const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
 #pragma unroll
         for (int f = 0; f < 36; ++f) {
@@ -288,7 +277,6 @@ __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
         const half2_t s2 = {(half_t)a.slope, (half_t)a.slope};
         slope2 = __builtin_bit_cast(unsigned, s2);
     }
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4];
     half8_t fr[14];           // fragment f of row step t (0..6 conv_1, 7..13 conv_2) lives in fr[(f - t) mod 14]
@@ -509,10 +497,7 @@ __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
                     if constexpr (o.kind == OP_ST) op_st(std::integral_constant<int, o.a>{}, std::integral_constant<int, o.b>{});
                 }
             };
-#define A32_OP(I) run(std::integral_constant<int, I>{});
-            A32_OP(0) A32_OP(1) A32_OP(2) A32_OP(3) A32_OP(4) A32_OP(5) A32_OP(6) A32_OP(7) A32_OP(8) A32_OP(9) A32_OP(10) A32_OP(11) A32_OP(12) A32_OP(13) A32_OP(14) A32_OP(15)
-            A32_OP(16) A32_OP(17) A32_OP(18) A32_OP(19) A32_OP(20) A32_OP(21) A32_OP(22) A32_OP(23) A32_OP(24) A32_OP(25) A32_OP(26) A32_OP(27) A32_OP(28) A32_OP(29) A32_OP(30) A32_OP(31)
-#undef A32_OP
+            static_for<L.n>(run);
         };
 
         // ================= conv_1: m rows 2+5h .. 6+5h from x rows 5h .. 5h+6 ==============================================================================
@@ -542,23 +527,14 @@ __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
 #endif
                 if (s < 6) fr[(f + 13 - s) % 14] = *(lds_h8_t)(fa[f] + (unsigned)((s + 1) * ROWB));
                 run_ops(std::integral_constant<int, 0>{}, S_, std::integral_constant<int, dx * KS + ks>{});
-#pragma unroll
-                for (int i_ = 0; i_ < 3; ++i_) {
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i_ == 0 && s < 6) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, 5, 0);
-                }
+                pin_mfmas<nm, s < 6 ? 1 : 0, 5>();
                 __builtin_amdgcn_sched_barrier(0);
             };
-#define A32_CHUNK(F) chunk(std::integral_constant<int, F>{});
-            A32_CHUNK(0) A32_CHUNK(1) A32_CHUNK(2) A32_CHUNK(3) A32_CHUNK(4) A32_CHUNK(5) A32_CHUNK(6) A32_CHUNK(7) A32_CHUNK(8) A32_CHUNK(9) A32_CHUNK(10) A32_CHUNK(11)
-#undef A32_CHUNK
+            static_for<12>(chunk);
             __builtin_amdgcn_s_waitcnt(0xC07F);
             A32_STAMP(1 + s)
         };
-#define A32_STEP(S) step1(std::integral_constant<int, S>{});
-        A32_STEP(0) A32_STEP(1) A32_STEP(2) A32_STEP(3) A32_STEP(4) A32_STEP(5) A32_STEP(6)
-#undef A32_STEP
+        static_for<7>(step1);
         run_ops(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});      // m row 4 of the wave has no MFMAs of its own conv left to ride in
         // conv_2 pads with ZEROS: m pixels outside the image must be 0, not conv_1 evaluated there (border patches only; in-order LDS: behind the row writes)
         if ((y0 + TH + 1 > a.H) | (x0 == 0) | (x0 + TW + 1 >= a.W)) {
@@ -617,23 +593,14 @@ __global__ __launch_bounds__(256) void arsb32c_kernel(ArsbArgs a)
                 if (s < 6) fr[(f + 13 - (7 + s)) % 14] = *(lds_h8_t)(fa[f] + (unsigned)((s + 1) * ROWB));
                 else fr[f] = *(lds_h8_t)(fa[f]);            // row 0 of patch p+1's conv_1 (landed and published by barrier B): (f - 14) mod 14 = f
                 run_ops(std::integral_constant<int, 1>{}, S_, std::integral_constant<int, dx * KS + ks>{});
-#pragma unroll
-                for (int i_ = 0; i_ < 3; ++i_) {
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, 5, 0);
-                }
+                pin_mfmas<nm, 1, 5>();
                 __builtin_amdgcn_sched_barrier(0);
             };
-#define A32_CHUNK(F) chunk(std::integral_constant<int, F>{});
-            A32_CHUNK(0) A32_CHUNK(1) A32_CHUNK(2) A32_CHUNK(3) A32_CHUNK(4) A32_CHUNK(5) A32_CHUNK(6) A32_CHUNK(7) A32_CHUNK(8) A32_CHUNK(9) A32_CHUNK(10) A32_CHUNK(11)
-#undef A32_CHUNK
+            static_for<12>(chunk);
             __builtin_amdgcn_s_waitcnt(0xC07F);
             A32_STAMP(11 + s)
         };
-#define A32_STEP(S) step2(std::integral_constant<int, S>{});
-        A32_STEP(0) A32_STEP(1) A32_STEP(2) A32_STEP(3) A32_STEP(4) A32_STEP(5) A32_STEP(6)
-#undef A32_STEP
+        static_for<7>(step2);
         so3p = row_so(3);                                     // slot 1 of output row 3 and row 4 of the wave: their epilogues ride in the next patch's conv_1
         so4p = row_so(4);
         vop = vo;

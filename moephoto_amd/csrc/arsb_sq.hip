@@ -20,10 +20,10 @@
 // Arithmetic: per conv the operands, products and scales of conv64_q8.hip / conv64_sq.hip; m crosses as the same (fp16, fp8 low word) pair those kernels store.
 // The results agree with the two-launch form to the fp32 rounding of a row's sums (tests/test_gpu_parity.py).
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #ifndef AQ_FILL
 #define AQ_FILL 5
@@ -46,21 +46,9 @@ constexpr int OFF_TAB = OFF_DUMP + 1024;       // 128,512: [entry 5][thread 256]
 constexpr int NPW = 5;                         // DMA pieces a wave issues per block: a_hi 4 i + w (i < 3; nine exist), a_lo8 4 (i - 3) + w (five exist)
 constexpr int LDS_BYTES = OFF_TAB + NPW * 1024;   // 133,632
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-typedef int i8v_t __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-typedef const __attribute__((address_space(3))) u4_t* lds_u4_t;
 typedef const __attribute__((address_space(3))) u2_t* lds_u2_t;
 
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_CVR, OP_CVW, OP_ACT, OP_SPL, OP_MW, OP_RHI, OP_ADD, OP_ST };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[48] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-};
 // DMA ops (e = 1, dealt to chunks 0..7): half 0 the lane's table word, half 1 select + issue, the word of piece i + 1 read in front of piece i's issue
 constexpr OpList dma_ops(int e)
 {
@@ -125,7 +113,6 @@ template <bool OUT8>
 __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1\n\ts_nop 3" ::: "memory");      // MODE.FP16_OVFL: the fp8 conversions saturate (conv64_q8.hip)
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
@@ -136,17 +123,14 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
     const int H = a.H, W = a.W;
 
     const int px = (W + TW - 1) / TW, nyb = H / RB;
-    const int g = blockIdx.x, G = gridDim.x;
-    const long long nitems = (long long)a.B * px * nyb;
-    int item = (int)(nitems * g / G);
-    const int item_end = (int)(nitems * (g + 1) / G);
-    if (item >= item_end) return;
+    StripRange range(a.B, px, nyb, blockIdx.x, gridDim.x);
+    if (!range.more()) return;
 
     // ---- weights of the wave's conv (conv64_sq.hip)
     half8_t w16[36];
     i8v_t wl8[9], wh8[9];
     {
-        const int wi = lane & 31, wq = wi >> 3;
+        const int wi = lane & 31, wq = wi >> 3;      // (weight_row of mfma_stream.h, spelled out: through the helper this kernel's instruction order changes)
         const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
         const half_t* p16 = role ? a.w16[1] : a.w16[0];
         const unsigned char* pl = role ? a.wl8[1] : a.wl8[0];
@@ -224,7 +208,7 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
         const int cc = j + dx;
-        fa[dx] = lds0 + (unsigned)(cc * 128 + ((((cc >> 1) & 7) ^ hh) << 4));
+        fa[dx] = frag_addr(lds0, cc, hh);
         fq[dx] = lds0 + (unsigned)(cc * 64 + (((2 * hh) ^ ((cc >> 2) & 3)) << 4));
         asm volatile("" : "+v"(fa[dx]), "+v"(fq[dx]));
     }
@@ -241,25 +225,6 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
         cv_src = lds0 + (unsigned)(q * 128 + (((2 * s8) ^ ((q >> 1) & 7)) << 4));
         cv_dst = lds0 + (unsigned)OFF_Q8 + (unsigned)(q * 64 + ((s8 ^ ((q >> 2) & 3)) << 4));
     }
-    const float quarter = 4.0f;
-    auto cvt4 = [&](unsigned a0, unsigned a1, unsigned b0, unsigned b1, unsigned& p0, unsigned& p1) __attribute__((always_inline)) {
-        asm volatile("v_cvt_scalef32_pk_fp8_f16 %0, %2, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %4, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %0, %3, %6 op_sel:[0,0,1]\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %5, %6 op_sel:[0,0,1]\n\t"
-                     "s_nop 0"
-                     : "=&v"(p0), "=&v"(p1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(quarter));
-    };
-    auto cvt16 = [&](const u4_t& w0, const u4_t& w1) {
-        u4_t d = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            unsigned p0, p1;
-            cvt4(w0[2 * k], w0[2 * k + 1], w1[2 * k], w1[2 * k + 1], p0, p1);
-            d[k] = p0; d[2 + k] = p1;
-        }
-        return d;
-    };
     // this lane's two 16-byte slots (channels 32 c + 16 o + 8 hh .. +7): P writes m column j -- m_hi slot (4 c + 2 o + hh) ^ ((j >> 1) & 7); the fp8 rows' 16-channel
     // slot 2 c + o, bytes 8 hh .. 8 hh + 7.  C reads the residual at x ring column j + 2 in the same forms.
     unsigned mw[2], mw8[2], xa[2], xa8[2];
@@ -272,7 +237,6 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
         xa8[o] = lds0 + (unsigned)OFF_LO8 + (unsigned)(xc * 64 + ((s8 ^ ((xc >> 2) & 3)) << 4) + 8 * hh);
     }
     const unsigned lane_ob = (unsigned)(j * 128 + (32 * c + 8 * hh) * 2);
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4];
 #pragma unroll
@@ -285,14 +249,10 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
 
     auto body = [&](auto ROLE_) __attribute__((always_inline)) {
         constexpr int ROLE = decltype(ROLE_)::value;
-        while (item < item_end) {
-            const int s0 = item % nyb;
-            const int t_ = item / nyb;
-            const int pxi = t_ % px, b = t_ / px;
-            const int s1 = min(nyb, s0 + (item_end - item));
-            item += s1 - s0;
-            const int x0 = pxi * TW;
-            const int ya = RB * s0, yb = RB * s1;
+        while (range.more()) {
+            const Strip st = range.next();
+            const int b = st.b, x0 = st.pxi * TW;
+            const int ya = RB * st.s0, yb = RB * st.s1;
             const int nblk = (yb - ya) / RB + 4;              // steps t = 0 .. yb - ya + 7: x rows ya - 2 .. yb + 5 (the last output row, yb - 1, is finished at x row yb + 4)
             const bool mokx = (unsigned)(x0 - 1 + j) < (unsigned)W;
             const unsigned vo = ((j < TW) & (x0 + j < W)) ? lane_ob : kOOR;
@@ -471,9 +431,7 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
                                     op_dma(std::integral_constant<int, o.a>{}, std::integral_constant<int, o.b>{});
                                 }
                             };
-#define AQ_OP(I) rund(std::integral_constant<int, I>{});
-                            AQ_OP(0) AQ_OP(1) AQ_OP(2) AQ_OP(3) AQ_OP(4) AQ_OP(5) AQ_OP(6) AQ_OP(7) AQ_OP(8) AQ_OP(9) AQ_OP(10) AQ_OP(11) AQ_OP(12) AQ_OP(13) AQ_OP(14) AQ_OP(15)
-#undef AQ_OP
+                            static_for<LD.n>(rund);
                             constexpr int ND = ops_chunks(ROLE);
                             constexpr int lo_ = ai < ND ? ai * L.n / ND : L.n, hi_ = ai < ND ? (ai + 1) * L.n / ND : L.n;
                             auto run = [&](auto I_) __attribute__((always_inline)) {
@@ -490,32 +448,15 @@ __global__ __launch_bounds__(256) void arsb_sq_kernel(ArsbSqArgsK a)
                                     if constexpr (o.kind == OP_ST) op_st(std::integral_constant<int, o.a>{});
                                 }
                             };
-#define AQ_OP(I) run(std::integral_constant<int, I>{});
-                            AQ_OP(0) AQ_OP(1) AQ_OP(2) AQ_OP(3) AQ_OP(4) AQ_OP(5) AQ_OP(6) AQ_OP(7) AQ_OP(8) AQ_OP(9) AQ_OP(10) AQ_OP(11) AQ_OP(12) AQ_OP(13) AQ_OP(14) AQ_OP(15)
-                            AQ_OP(16) AQ_OP(17) AQ_OP(18) AQ_OP(19) AQ_OP(20) AQ_OP(21) AQ_OP(22) AQ_OP(23)
-#undef AQ_OP
+                            static_for<L.n>(run);
                         }
 #ifndef AQ_NOPIN
-#pragma unroll
-                        for (int i_ = 0; i_ < 3; ++i_) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x006, AQ_FILL, 0);
-                        }
-                        if (ks == 1 || ks == 3) {
-#pragma unroll
-                            for (int i_ = 0; i_ < 3; ++i_) {
-                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                                if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, (ks == 3 && dx == 2) ? 4 : 2, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x006, 2 * AQ_FILL, 0);
-                            }
-                        }
+                        pin_mfmas<3, 1, AQ_FILL>();
+                        if constexpr (ks == 1 || ks == 3) pin_mfmas<3, (ks == 3 && dx == 2) ? 4 : 2, 2 * AQ_FILL>();
 #endif
                         __builtin_amdgcn_sched_barrier(0);
                     };
-#define AQ_CHUNK(A) chunk(std::integral_constant<int, A>{});
-                    AQ_CHUNK(0) AQ_CHUNK(1) AQ_CHUNK(2) AQ_CHUNK(3) AQ_CHUNK(4) AQ_CHUNK(5) AQ_CHUNK(6) AQ_CHUNK(7) AQ_CHUNK(8) AQ_CHUNK(9) AQ_CHUNK(10) AQ_CHUNK(11)
-#undef AQ_CHUNK
+                    static_for<12>(chunk);
                 };
                 step(std::integral_constant<int, 0>{});
                 step(std::integral_constant<int, 1>{});

@@ -17,13 +17,11 @@
 // LDS: weights NCH x 8 KiB (x2 with split operands) + bias + 4 waves x RING x (4 | 8) KiB.  Round 6: the split-operand four-chunk stages of the 48-channel nets (lite's
 // default arithmetic; template NKS = 3: the all-zero fourth k-slice is not computed) hold their 48 weight fragments in registers (192 AGPRs): no weight bytes in LDS, RING = 4.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 
 namespace {
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
 typedef const __attribute__((address_space(3))) float4_t* lds_f4_t;
 
 template <bool X3, int NCH, bool TAIL, int NKS = 4>
@@ -51,7 +49,6 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(Conv1x1Args a)
     using C = Cfg<X3, NCH, TAIL, NKS>;
     constexpr bool WREG = C::WREG;
     constexpr int R = NCH == 4 ? 2 : 1, RING = C::RING, SEG = X3 ? 2 : 1;
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -63,7 +60,7 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(Conv1x1Args a)
     // of a 32x32 result lands in register 4q + e of the lanes hh = h; giving row i the channel 16 (q >> 1) + 8 h + 4 (q & 1) + e makes registers
     // 8g .. 8g+7 of lane (j, hh) the consecutive channels 32 nb + 16 g + 8 hh ..
     {
-        const int wi = lane & 31, wq = wi >> 3;
+        const int wi = lane & 31, wq = wi >> 3;      // (weight_row of mfma_stream.h, spelled out: through the helper this kernel's instruction order changes)
         const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
         if constexpr (WREG) {
 #pragma unroll

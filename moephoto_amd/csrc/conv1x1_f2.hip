@@ -13,14 +13,12 @@
 //
 // Arithmetic: per layer the same products in the same order, the same roundings (hi / lo split between the stages) as conv1x1.hip's kernels: the same bits.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include <algorithm>
-#include <type_traits>
 
 namespace {
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
 typedef const __attribute__((address_space(3))) float4_t* lds_f4_t;
 
 constexpr int NKS = 3;                          // k-slices of 16 input channels that are not all zeros (48-channel nets)
@@ -34,7 +32,6 @@ constexpr int LDS = WB + BIASB + 4 * RING * TILE;      // 149,504
 __global__ __launch_bounds__(256) void conv1x1_f2_kernel(Conv1x1F2Args a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -45,8 +42,7 @@ __global__ __launch_bounds__(256) void conv1x1_f2_kernel(Conv1x1F2Args a)
     // registers 8g .. 8g+7 of lane (j, hh) the consecutive channels 32 nb + 16 g + 8 hh .. (conv1x1.hip).  Stage A: registers; stage B: LDS
     half8_t wr[4][2][2 * NKS];
     {
-        const int wi = lane & 31, wq = wi >> 3;
-        const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
+        const int src = weight_row(j, hh);
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll

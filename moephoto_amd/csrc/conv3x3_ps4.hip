@@ -31,10 +31,10 @@
 // Arithmetic: the conv sums are bit-identical to conv3x3_rw's (same MFMAs in the same order, bias as the accumulators' initial value); the tail's
 // nine products per output pixel are the same, associated differently in fp32.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include "../../include/moephoto_amd.h"
 #include <algorithm>
-#include <type_traits>
 
 #ifndef PS4_FILL
 #define PS4_FILL 5        // VALU / SALU slots pinned behind each MFMA of a chunk
@@ -62,20 +62,8 @@ constexpr int OFF_TW = OFF_BIAS + 1024;         // bias: [wave 4][cg 2][hh 2][16
 constexpr int OFF_DUMP = OFF_TW + 8 * 1024;     // tail weights: 8 A fragments;  dump: where the 17th DMA piece of waves 1..3 lands (nothing)
 constexpr int LDS_BYTES = OFF_DUMP + 1024;      // 119,808
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-
 // ---- what rides in the MFMA stream of a row step, as micro-ops (conv3x3_rw.hip, arsb32c.hip: an MFMA hides ~5 other instructions) --------------------
 enum OpKind : int { OP_NONE = 0, OP_P, OP_WL, OP_TM, OP_TW, OP_BI, OP_DMA, OP_FA, OP_FR, OP_FS, OP_AR, OP_AS, OP_ST };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[64] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-    constexpr void append(const OpList& o) { for (int i = 0; i < o.n; ++i) { op[n] = o.op[i]; ++n; } }
-};
 // The row epilogue: per 16 channels (cg, half q) four PReLU ops (one channel pair each with the split, two without), then the tail MFMA(s) of that
 // slice.  Tail-weight fragments come from LDS into two rotating register sets (WL n -> set n & 1, TM n reads set n & 1).
 constexpr OpList row_ops(int epi)      // 0: store (PReLU, pixel shuffle), 1: fused tail, 2: fused tail with split activations
@@ -127,7 +115,6 @@ constexpr OpList extra_ops(int e, bool tail)
     if (e == 1) for (int m = 1; m < 5; ++m) { r.push(OP_DMA, m, 0); r.push(OP_DMA, m, 1); }
     return r;
 }
-constexpr int count_kind(const OpList& l, int lo, int hi, int kind) { int n = 0; for (int i = lo; i < hi; ++i) n += l.op[i].kind == kind; return n; }
 
 // EPI 0: PReLU + pixel-shuffle stores (the other upsampler stages), 1: fused tail, 2: fused tail with the activation operand split (hi + lo 2^-11)
 template <int EPI, bool MASK>
@@ -136,7 +123,6 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool TAIL = EPI >= 1, SPLIT = EPI == 2;
     constexpr bool PERM = !TAIL;         // store form: channel order that makes a lane's registers 8g .. 8g+7 eight consecutive channels (16-byte stores, conv3x3_rw.hip)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(1024))) char smem[];      // (fragment addresses XOR their k-slice bits: the base must be 128-byte aligned)
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -159,8 +145,7 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
         const half_t* wsrc = a.wpk + (long long)w4 * (72 * 512);
         int src = lane;
         if (PERM) {      // MFMA row i = 8q + 4h' + e (register 4q + e of the lanes hh = h') is given channel 16 (q >> 1) + 8 h' + 4 (q & 1) + e of its group
-            const int wi = lane & 31, wq = wi >> 3;
-            src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
+            src = weight_row(j, hh);
         }
 #pragma unroll
         for (int f = 0; f < 36; ++f) {
@@ -216,8 +201,7 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
     unsigned fa[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-        const int cc = j + dx, z = (cc >> 1) & 7;
-        fa[dx] = lds0 + (unsigned)(cc * 128 + ((z ^ hh) << 4));
+        fa[dx] = frag_addr(lds0, j + dx, hh);
         asm volatile("" : "+v"(fa[dx]));
     }
     // ---- tap image: byte offset (inside a row record) of the slot each of the lane's five T values goes to: value k = tap 4 hh + k (k < 4), tap 8 (k = 4,
@@ -246,7 +230,6 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
         const half2_t s2 = {(half_t)a.slope, (half_t)a.slope};
         slope2 = __builtin_bit_cast(unsigned, s2);
     }
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4][2];      // out row o lives in slot o & 3
     half8_t fr[3];            // fragment of chunk f in fr[f % 3], read two chunks ahead
@@ -259,7 +242,7 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
 
     while (item < item_end) {
         // ===== one strip: plane b, column pxi, blocks [s0, s1) = conv rows [4 s0, 4 s1) =====================================================================
-        const int s0 = item % nyb;
+        const int s0 = item % nyb;                            // (StripRange of mfma_stream.h, spelled out: through the struct this kernel compiles to other code)
         const int t_ = item / nyb;
         const int pxi = t_ % px, b = t_ / px;
         const int s1 = min(nyb, s0 + (item_end - item));
@@ -316,8 +299,8 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
             const int yf = Rk - 7 + w4;
             const bool f_ok = (yf >= ylo) & (yf < yhi);
             unsigned fb[3];
-            float2_t fs[2] = {{0.f, 0.f}, {0.f, 0.f}};
-            float2_t fv[2];
+            f2_t fs[2] = {{0.f, 0.f}, {0.f, 0.f}};
+            f2_t fv[2];
             float av[3];
 
             auto step = [&](auto E_) __attribute__((always_inline)) {
@@ -404,8 +387,8 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
                     constexpr int dy = decltype(DY_)::value, dx = decltype(DX_)::value;
                     constexpr int j0 = dx == 1 ? 0 : 1, j1 = dx == 1 ? 1 : 0;
                     if constexpr (dx > 0 || dy > 0) { fs[0] = fs[0] + fv[0]; fs[1] = fs[1] + fv[1]; }      // the pair read one op earlier
-                    fv[0] = *(const __attribute__((address_space(3))) float2_t*)(fb[dy] + (unsigned)((j0 * 9 + dx) * 128));
-                    fv[1] = *(const __attribute__((address_space(3))) float2_t*)(fb[dy] + (unsigned)((j1 * 9 + dx) * 128));
+                    fv[0] = *(const __attribute__((address_space(3))) f2_t*)(fb[dy] + (unsigned)((j0 * 9 + dx) * 128));
+                    fv[1] = *(const __attribute__((address_space(3))) f2_t*)(fb[dy] + (unsigned)((j1 * 9 + dx) * 128));
                 };
                 auto op_fs = [&]() __attribute__((always_inline)) {
                     fs[0] = fs[0] + fv[0]; fs[1] = fs[1] + fv[1];
@@ -502,45 +485,27 @@ __global__ __launch_bounds__(256) void conv3x3_ps4_kernel(Ps4Args a)
                                 if constexpr (o.kind == OP_AS) op_as();
                             }
                         };
-#define PS4_M(I) runm(std::integral_constant<int, I>{});
-                        PS4_M(0) PS4_M(1) PS4_M(2) PS4_M(3) PS4_M(4) PS4_M(5) PS4_M(6) PS4_M(7) PS4_M(8) PS4_M(9) PS4_M(10) PS4_M(11) PS4_M(12) PS4_M(13) PS4_M(14) PS4_M(15)
-                        PS4_M(16) PS4_M(17) PS4_M(18) PS4_M(19) PS4_M(20) PS4_M(21) PS4_M(22) PS4_M(23) PS4_M(24) PS4_M(25) PS4_M(26) PS4_M(27) PS4_M(28) PS4_M(29) PS4_M(30) PS4_M(31)
-                        PS4_M(32) PS4_M(33) PS4_M(34) PS4_M(35) PS4_M(36) PS4_M(37) PS4_M(38) PS4_M(39) PS4_M(40) PS4_M(41) PS4_M(42) PS4_M(43) PS4_M(44) PS4_M(45) PS4_M(46) PS4_M(47)
-#undef PS4_M
-#define PS4_X(I) runx(std::integral_constant<int, I>{});
-                        PS4_X(0) PS4_X(1) PS4_X(2) PS4_X(3) PS4_X(4) PS4_X(5) PS4_X(6) PS4_X(7) PS4_X(8) PS4_X(9) PS4_X(10) PS4_X(11) PS4_X(12) PS4_X(13) PS4_X(14) PS4_X(15)
-#undef PS4_X
+                        static_for<LM.n>(runm);
+                        static_for<LX.n>(runx);
                         if (f == 10 && hc == 1 && !(PS4_ABL & 4)) op_bi(std::integral_constant<int, 0>{});
                         if (f == 11 && hc == 1 && !(PS4_ABL & 4)) op_bi(std::integral_constant<int, 1>{});
                     };
                     half(std::integral_constant<int, 0>{});
                     half(std::integral_constant<int, 1>{});
 #ifndef PS4_NOPIN
-#pragma unroll
-                    for (int hc = 0; hc < (ZERO ? 0 : 2); ++hc) {
-                        const int h = 2 * f + hc;
-                        const int MH = TAIL ? 20 : 10;
-                        const int m_lo = h < MH ? h * LM.n / MH : LM.n, m_hi = h < MH ? (h + 1) * LM.n / MH : LM.n;
-                        const int ntm = (PS4_ABL & 33) ? 0 : count_kind(LM, m_lo, m_hi, OP_TM);
-#pragma unroll
-                        for (int i_ = 0; i_ < 3; ++i_) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            if (i_ == 0 && hc == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x006, PS4_FILL, 0);
-                        }
-#pragma unroll
-                        for (int i_ = 0; i_ < 2; ++i_)
-                            if (TAIL && i_ < ntm) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x006, PS4_FILL, 0); }
-                    }
+                    static_for<ZERO ? 0 : 2>([&](auto HC_) __attribute__((always_inline)) {
+                        constexpr int hc = decltype(HC_)::value, h = 2 * f + hc, MH = TAIL ? 20 : 10;
+                        constexpr int m_lo = h < MH ? h * LM.n / MH : LM.n, m_hi = h < MH ? (h + 1) * LM.n / MH : LM.n;
+                        pin_mfmas<3, hc == 0 ? 1 : 0, PS4_FILL>();
+                        pin_mfmas<(!TAIL || (PS4_ABL & 33)) ? 0 : count_kind(LM, m_lo, m_hi, OP_TM), 0, PS4_FILL>();      // the half's tail MFMAs, each with fillers behind it
+                    });
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 };
 #if PS4_ABL
                 if constexpr (!LAST) asm volatile("" ::"v"(acc[SL][0]), "v"(acc[SL][1]), "v"(Gt));      // (ablation builds: the row's results stay live without its epilogue)
 #endif
-#define PS4_CHUNK(F) chunk(std::integral_constant<int, F>{});
-                PS4_CHUNK(0) PS4_CHUNK(1) PS4_CHUNK(2) PS4_CHUNK(3) PS4_CHUNK(4) PS4_CHUNK(5) PS4_CHUNK(6) PS4_CHUNK(7) PS4_CHUNK(8) PS4_CHUNK(9) PS4_CHUNK(10) PS4_CHUNK(11)
-#undef PS4_CHUNK
+                static_for<12>(chunk);
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});

@@ -26,10 +26,10 @@
 // Arithmetic: the conv sums are bit-identical to conv3x3_sp's / conv3x3_rw's (same MFMAs in the same order, bias as the accumulators' initial value); the tail's
 // nine products per output pixel are the same, associated differently in fp32.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include "../../include/moephoto_amd.h"
 #include <algorithm>
-#include <type_traits>
 
 #ifndef PS9_FILL
 #define PS9_FILL 5        // VALU / SALU slots pinned behind each MFMA of a chunk
@@ -60,18 +60,10 @@ constexpr int OFF_TW = OFF_BIAS + 1024;         // bias: [wave 3][cg 2][hh 2][16
 constexpr int OFF_DUMP = OFF_TW + 8 * 1024;     // tail weights: 8 A fragments;  dump: where a piece that is nobody's lands (nothing)
 constexpr int LDS_BYTES = OFF_DUMP + 1024;      // 73,216
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u3_t __attribute__((ext_vector_type(3)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
 
 // ---- what rides in the MFMA stream of a row step, as micro-ops (conv3x3_ps4.hip: an MFMA hides ~5 other instructions) ----------------------------------
 enum OpKind : int { OP_NONE = 0, OP_P, OP_WL, OP_TM, OP_TW, OP_DMA, OP_FA, OP_FR, OP_FS, OP_AR, OP_AS };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[64] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-};
 // The row epilogue: per 16 channels (cg, half q) the PReLU ops (one channel pair each with the split, two without), then the tail MFMA(s) of that slice.
 // Tail-weight fragments come from LDS into two rotating register sets (WL n -> set n & 1, TM n reads set n & 1).
 constexpr OpList row_ops(bool split)
@@ -109,14 +101,12 @@ constexpr OpList extra_ops(int e)
     if (e == 1) for (int m = 2; m < NM; ++m) { r.push(OP_DMA, m, 0); r.push(OP_DMA, m, 1); }
     return r;
 }
-constexpr int count_kind(const OpList& l, int lo, int hi, int kind) { int n = 0; for (int i = lo; i < hi; ++i) n += l.op[i].kind == kind; return n; }
 
 // SPLIT: the tail conv's activation operand as hi + lo 2^-11 (MOE_PREC_MIXED, R branch); MASK: ragged width (W % 32 != 0)
 template <bool SPLIT, bool MASK>
 __global__ __launch_bounds__(NT) void conv3x3_ps9_kernel(Ps9Args a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(1024))) char smem[];      // (fragment addresses XOR their k-slice bits: the base must be 128-byte aligned)
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -204,8 +194,7 @@ __global__ __launch_bounds__(NT) void conv3x3_ps9_kernel(Ps9Args a)
     unsigned fa[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-        const int cc = j + dx, z = (cc >> 1) & 7;
-        fa[dx] = lds0 + (unsigned)(cc * 128 + ((z ^ hh) << 4));
+        fa[dx] = frag_addr(lds0, j + dx, hh);
         asm volatile("" : "+v"(fa[dx]));
     }
     // ---- tap image: byte offset (inside a row record) of the slot each of the lane's five T values goes to: value k = tap 4 hh + k (k < 4), tap 8 (k = 4,
@@ -231,7 +220,6 @@ __global__ __launch_bounds__(NT) void conv3x3_ps9_kernel(Ps9Args a)
         const half2_t s2 = {(half_t)a.slope, (half_t)a.slope};
         slope2 = __builtin_bit_cast(unsigned, s2);
     }
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4][2];      // out row o lives in slot o & 3
     half8_t fr[3];            // fragment of chunk f in fr[f % 3], read two chunks ahead
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(NT) void conv3x3_ps9_kernel(Ps9Args a)
 
     while (item < item_end) {
         // ===== one strip: plane b, column pxi, blocks [s0, s1) = conv rows [4 s0, 4 s1) =====================================================================
-        const int s0 = item % nyb;
+        const int s0 = item % nyb;                            // (StripRange of mfma_stream.h, spelled out: through the struct this kernel compiles to other code)
         const int t_ = item / nyb;
         const int pxi = t_ % px, b = t_ / px;
         const int s1 = min(nyb, s0 + (item_end - item));
@@ -470,42 +458,24 @@ __global__ __launch_bounds__(NT) void conv3x3_ps9_kernel(Ps9Args a)
                                 if constexpr (o.kind == OP_AS) op_as(std::integral_constant<int, o.a>{});
                             }
                         };
-#define PS9_M(I) runm(std::integral_constant<int, I>{});
-                        PS9_M(0) PS9_M(1) PS9_M(2) PS9_M(3) PS9_M(4) PS9_M(5) PS9_M(6) PS9_M(7) PS9_M(8) PS9_M(9) PS9_M(10) PS9_M(11) PS9_M(12) PS9_M(13) PS9_M(14) PS9_M(15)
-                        PS9_M(16) PS9_M(17) PS9_M(18) PS9_M(19) PS9_M(20) PS9_M(21) PS9_M(22) PS9_M(23) PS9_M(24) PS9_M(25) PS9_M(26) PS9_M(27) PS9_M(28) PS9_M(29) PS9_M(30) PS9_M(31)
-                        PS9_M(32) PS9_M(33) PS9_M(34) PS9_M(35) PS9_M(36) PS9_M(37) PS9_M(38) PS9_M(39) PS9_M(40) PS9_M(41) PS9_M(42) PS9_M(43) PS9_M(44) PS9_M(45) PS9_M(46) PS9_M(47)
-#undef PS9_M
-#define PS9_X(I) runx(std::integral_constant<int, I>{});
-                        PS9_X(0) PS9_X(1) PS9_X(2) PS9_X(3) PS9_X(4) PS9_X(5) PS9_X(6) PS9_X(7) PS9_X(8) PS9_X(9) PS9_X(10) PS9_X(11) PS9_X(12) PS9_X(13) PS9_X(14) PS9_X(15)
-#undef PS9_X
+                        static_for<LM.n>(runm);
+                        static_for<LX.n>(runx);
                         if (f == 10 && hc == 1) op_bi(std::integral_constant<int, 0>{});
                         if (f == 11 && hc == 1) op_bi(std::integral_constant<int, 1>{});
                     };
                     half(std::integral_constant<int, 0>{});
                     half(std::integral_constant<int, 1>{});
 #ifndef PS9_NOPIN
-#pragma unroll
-                    for (int hc = 0; hc < (ZERO ? 0 : 2); ++hc) {
-                        const int h = 2 * f + hc;
-                        const int MH = 20;
-                        const int m_lo = h < MH ? h * LM.n / MH : LM.n, m_hi = h < MH ? (h + 1) * LM.n / MH : LM.n;
-                        const int ntm = count_kind(LM, m_lo, m_hi, OP_TM);
-#pragma unroll
-                        for (int i_ = 0; i_ < 3; ++i_) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            if (i_ == 0 && hc == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x006, PS9_FILL, 0);
-                        }
-#pragma unroll
-                        for (int i_ = 0; i_ < 2; ++i_)
-                            if (i_ < ntm) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x006, PS9_FILL, 0); }
-                    }
+                    static_for<ZERO ? 0 : 2>([&](auto HC_) __attribute__((always_inline)) {
+                        constexpr int hc = decltype(HC_)::value, h = 2 * f + hc, MH = 20;
+                        constexpr int m_lo = h < MH ? h * LM.n / MH : LM.n, m_hi = h < MH ? (h + 1) * LM.n / MH : LM.n;
+                        pin_mfmas<3, hc == 0 ? 1 : 0, PS9_FILL>();
+                        pin_mfmas<count_kind(LM, m_lo, m_hi, OP_TM), 0, PS9_FILL>();      // the half's tail MFMAs, each with fillers behind it
+                    });
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 };
-#define PS9_CHUNK(F) chunk(std::integral_constant<int, F>{});
-                PS9_CHUNK(0) PS9_CHUNK(1) PS9_CHUNK(2) PS9_CHUNK(3) PS9_CHUNK(4) PS9_CHUNK(5) PS9_CHUNK(6) PS9_CHUNK(7) PS9_CHUNK(8) PS9_CHUNK(9) PS9_CHUNK(10) PS9_CHUNK(11)
-#undef PS9_CHUNK
+                static_for<12>(chunk);
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});

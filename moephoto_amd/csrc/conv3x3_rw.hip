@@ -31,8 +31,8 @@
 //
 // LDS: 2 x 45,056 (patches) + 3 x 19,984 (tap images) = 150,064 B.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
-#include <type_traits>
 
 #ifndef RW_HOIST
 #define RW_HOIST 1        // fused tail: the bookkeeping of patch p+2 (item, origin, border key) as a micro-op of row step 4 (0: at the end of the iteration)
@@ -58,13 +58,6 @@ constexpr int LDS_BYTES = 2 * PATCH_BYTES + 3 * XCH_BYTES;         // 150,064
 // chunk f the slice [f N / 12, (f + 1) N / 12) of it.  A lump of 30-40 VALU instructions in one chunk leaves the MFMA pipe idle for as many
 // issue slots (the first version of this epilogue: 18 such gaps per patch, rw<7> 10 % slower than conv3x3_sp<7>); beside an MFMA only ~5 fit.
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_RD, OP_P, OP_TM, OP_TW, OP_FF, OP_FA, OP_FS, OP_AF, OP_AS, OP_ADV, OP_ST };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[40] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-    constexpr void append(const OpList& o) { for (int i = 0; i < o.n; ++i) { op[n] = o.op[i]; ++n; } }
-};
 // both lists in order, proportionally interleaved (Bresenham)
 constexpr OpList interleave(const OpList& x, const OpList& y)
 {
@@ -164,9 +157,6 @@ constexpr OpList tail_ops(int R)
     return r;
 }
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-
 struct Item { int b, pyi, pxi; };
 
 // MASK (fused tail only): the image is ragged against the 8 x 32 patches (H % 8 or W % 32 != 0), so the products of patch pixels outside the
@@ -177,7 +167,6 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
 #if defined(__HIP_DEVICE_COMPILE__)      // (the host pass only needs the launch stub)
     constexpr bool TAIL = EPI == 3 || EPI == 7, TAIL2 = EPI == 7, POOL = EPI == 4;
     constexpr bool PERM = !TAIL;         // EPI 1: channel order that makes registers 8g..8g+7 eight consecutive channels (16-byte stores)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
     {
         int src = lane;
         if (PERM) {      // MFMA row i = 8q + 4h' + e (register 4q + e of the lanes hh = h') is given channel 16 (q >> 1) + 8 h' + 4 (q & 1) + e
-            const int wi = lane & 31, wq = wi >> 3;
+            const int wi = lane & 31, wq = wi >> 3;      // (weight_row of mfma_stream.h, spelled out: through the helper this kernel's instruction order changes)
             src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
         }
         const half_t* wsrc = a.wpk + (long long)chunk * (72 * 512);
@@ -388,7 +377,6 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
         ap_base = (tl.CO + ph * (unsigned)(a.B * tl.py * tl.px)) * 4u; ap_sb = (unsigned)(tl.py * tl.px) * 4u; ap_sy = (unsigned)tl.px * 4u; ap_sx = 4u;
     }
 
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float16_t acc[5];                      // output rows 0..2 of the patch in slots 0..2, row 3 in slot 3 (even patches) / 4 (odd): it is read out during the next patch
     half8_t fr[2][12];
     float v2[16], v3[16];                  // output rows 2 and 3 of the previous patch, read out of their accumulators late in that patch
@@ -681,7 +669,8 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
                 //   the next patch, finished in its steps 1, 2;   DMA of patch p+1 in steps 0..2.
                 constexpr OpList L = TAIL ? tail_ops<TAIL2>(R) : plain_ops(R);
                 constexpr int o_lo = f * L.n / 12, o_hi = (f + 1) * L.n / 12;
-                int ntm = 0;                         // tail-GEMM MFMAs issued by this chunk (they need slots of their own in the pattern below)
+                constexpr int ntm = count_kind(L, o_lo, o_hi, OP_TM) * (TAIL2 ? 4 : 2);      // tail-GEMM MFMAs issued by this chunk (they need slots of their own in the pattern below)
+                static_assert(ntm <= 4, "one tail GEMM per chunk");
                 {
                     auto run = [&](auto I_) __attribute__((always_inline)) {
                         constexpr int I = decltype(I_)::value;
@@ -701,36 +690,19 @@ __global__ __launch_bounds__(256) void conv3x3_rw_kernel(ConvArgs a)
                             if constexpr (o.kind == OP_ST) store_row(o.a < 2 ? it : itp, 4 * h + o.a, o.a < 2 ? true : ep3, hA, hB);
                         }
                     };
-#define RW_OP(I) run(std::integral_constant<int, I>{});
-                    RW_OP(0) RW_OP(1) RW_OP(2) RW_OP(3) RW_OP(4) RW_OP(5) RW_OP(6) RW_OP(7) RW_OP(8) RW_OP(9) RW_OP(10) RW_OP(11) RW_OP(12) RW_OP(13)
-                    RW_OP(14) RW_OP(15) RW_OP(16) RW_OP(17) RW_OP(18) RW_OP(19) RW_OP(20) RW_OP(21) RW_OP(22) RW_OP(23) RW_OP(24) RW_OP(25) RW_OP(26)
-                    RW_OP(27) RW_OP(28) RW_OP(29) RW_OP(30) RW_OP(31) RW_OP(32) RW_OP(33) RW_OP(34) RW_OP(35) RW_OP(36) RW_OP(37) RW_OP(38) RW_OP(39)
-#undef RW_OP
-                    for (int I = o_lo; I < o_hi; ++I) ntm += L.op[I].kind == OP_TM ? (TAIL2 ? 4 : 2) : 0;
+                    static_for<L.n>(run);
                 }
 #ifndef RW_NOPIN
-#pragma unroll
-                for (int i_ = 0; i_ < 3; ++i_) {
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, RW_FILL, 0);
-                }
-#pragma unroll
-                for (int i_ = 0; i_ < 4; ++i_) {      // the tail GEMM's MFMAs, each with fillers behind it
-                    if (i_ < ntm) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x006, RW_FILL, 0); }
-                }
+                pin_mfmas<nm, 1, RW_FILL>();
+                pin_mfmas<ntm, 0, RW_FILL>();      // the tail GEMM's MFMAs, each with fillers behind it
 #endif
                 __builtin_amdgcn_sched_barrier(0);
             };
-#define RW_CHUNK(F) chunk_f(std::integral_constant<int, F>{});
-            RW_CHUNK(0) RW_CHUNK(1) RW_CHUNK(2) RW_CHUNK(3) RW_CHUNK(4) RW_CHUNK(5) RW_CHUNK(6) RW_CHUNK(7) RW_CHUNK(8) RW_CHUNK(9) RW_CHUNK(10) RW_CHUNK(11)
-#undef RW_CHUNK
+            static_for<12>(chunk_f);
             // the fragments of the next row step have landed before it starts (one wait the compiler's count pass can see, see conv3x3_sp.hip)
             __builtin_amdgcn_s_waitcnt(0xC07F);
         };
-#define RW_STEP(S) step(std::integral_constant<int, S>{});
-        RW_STEP(0) RW_STEP(1) RW_STEP(2) RW_STEP(3) RW_STEP(4) RW_STEP(5)
-#undef RW_STEP
+        static_for<6>(step);
         if (!RW_HOIST) adv();
         it_pp = it_prev; it_prev = it_cur; it_cur = it_next; it_next = it_nn; it_nn = nn2;
         org_next = org_n2; key_next = key_n2;

@@ -32,8 +32,8 @@
 //   loads and stores in separate stretches (arsb32c.hip): DMA and residual loads before row step 3 of the long pass, stores from there on; the wait that
 //   opens a patch counts (all but the sixteen stores behind the last DMA piece).
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
-#include <type_traits>
 #include <vector>
 #include <cstdio>
 
@@ -50,23 +50,10 @@ constexpr int NDMA8_W = 6;                     // IN8: 1-KiB pieces of the fp8 a
 constexpr int DUMP = 3 * XBYTES + Q8BYTES;     // 1 KiB nobody reads
 constexpr int LDS_BYTES = DUMP + 1024;         // 158,720
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-typedef int i8v_t __attribute__((ext_vector_type(8)));
 typedef _Float16 h2v_t __attribute__((ext_vector_type(2)));
 typedef short s2v_t __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-typedef const __attribute__((address_space(3))) u4_t* lds_u4_t;
 
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_RLD, OP_RADD, OP_ACT, OP_SPL, OP_ST };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[40] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-    constexpr void append(const OpList& o) { for (int i = 0; i < o.n; ++i) { op[n] = o.op[i]; ++n; } }
-};
 // OP_DMA(image, piece, half): image 0 = a_lo of this patch, 1 = a_hi of the next one; half 0 = address, 1 = validity + issue
 constexpr OpList dma_ops(int img, int i0, int i1)
 {
@@ -158,7 +145,6 @@ template <int EPI, bool IN8, bool OUT8>
 __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     constexpr bool RES = EPI == 2, ACT = EPI == 1;
     // MODE.FP16_OVFL for the whole kernel: with it the fp8 conversions saturate at +-448 (without: NaN beyond 464, i.e. for activations beyond 1856 --
     // tools/micro/cvt_ovfl_probe.hip).  The epilogue's fp16 conversions then clamp at 65504 where IEEE gives infinity: beyond the range either way.
@@ -201,8 +187,7 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
     half8_t w16[36];
     i8v_t wl8[9], wh8[9];
     {
-        const int wi = lane & 31, wq = wi >> 3;
-        const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
+        const int src = weight_row(j, hh);
 #pragma unroll
         for (int f = 0; f < 36; ++f) w16[f] = *(const half8_t*)(a.wq_hi16 + ((f * 2 + c) * 64 + src) * 8);
 #pragma unroll
@@ -288,27 +273,12 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
         fq[dx] = qbase + (unsigned)(4 * h * ROWB8) + (unsigned)(cc * 64 + (((2 * hh) ^ z) << 4));      // slot 2 hh; slot 2 hh + 1 is this address ^ 16
     }
     const unsigned lane_ob = (unsigned)(j * 128 + (32 * c + 8 * hh) * 2);      // byte offset of slot o = 0 of output column j inside a patch row of the tensors
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     // fp16 patch -> fp8 image (all 256 threads): unit u = (pixel q, 16-channel slot s8): two 16-byte reads, eight conversions (value / 4), one 16-byte
     // write; six units per thread, all twelve reads first.  Units behind the last pixel repeat unit (339, s8): same data to the same place, no branch.
-    const float quarter = 4.0f;                               // the source is DIVIDED by the scale operand
-    // four packed fp16 pairs -> two words of four fp8 each.  One block, the two words' conversions alternating, a wait state at its end: a conversion writes
-    // HALF a register, and gfx950 wants one wait state between such a write and the next VALU use of the register (the half-word is not forwarded).  The
-    // compiler's hazard recognizer places that state for its own instructions and cannot see into inline asm: issued back to back, the second conversion
-    // of a word at times kept a stale first half -- results that changed from run to run (tools/diag_q8_batch.py).
-    // (inline asm: through __builtin_amdgcn_cvt_scalef32_pk_fp8_f16 this compiler converted the first word of a slot four times and read nothing else of
-    // it -- found with the constant-image experiment of tools/diag_q8.py)
-    auto cvt4 = [&](unsigned a0, unsigned a1, unsigned b0, unsigned b1, unsigned& p0, unsigned& p1) __attribute__((always_inline)) {
-        asm volatile("v_cvt_scalef32_pk_fp8_f16 %0, %2, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %4, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %0, %3, %6 op_sel:[0,0,1]\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %5, %6 op_sel:[0,0,1]\n\t"
-                     "s_nop 0"
-                     : "=&v"(p0), "=&v"(p1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(quarter));
-    };
+    // (the conversion itself, four packed fp16 pairs -> two words of four fp8 each, value / 4: cvt4 of mfma_stream.h)
     auto to_fp8_image = [&](unsigned srcbase) {
-        auto cvt16 = [&](const u4_t& w0, const u4_t& w1) {
+        auto cvt16 = [&](const u4_t& w0, const u4_t& w1) {      // (mfma_stream.h has this without the debug switch)
             u4_t d = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -512,11 +482,7 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
                     if constexpr (o.kind == OP_ST) op_st(std::integral_constant<int, o.a>{}, std::integral_constant<int, o.b>{});
                 }
             };
-#define Q8_OP(I) run(std::integral_constant<int, I>{});
-            Q8_OP(0) Q8_OP(1) Q8_OP(2) Q8_OP(3) Q8_OP(4) Q8_OP(5) Q8_OP(6) Q8_OP(7) Q8_OP(8) Q8_OP(9) Q8_OP(10) Q8_OP(11) Q8_OP(12) Q8_OP(13) Q8_OP(14) Q8_OP(15)
-            Q8_OP(16) Q8_OP(17) Q8_OP(18) Q8_OP(19) Q8_OP(20) Q8_OP(21) Q8_OP(22) Q8_OP(23) Q8_OP(24) Q8_OP(25) Q8_OP(26) Q8_OP(27) Q8_OP(28) Q8_OP(29) Q8_OP(30) Q8_OP(31)
-            Q8_OP(32) Q8_OP(33) Q8_OP(34) Q8_OP(35) Q8_OP(36) Q8_OP(37) Q8_OP(38) Q8_OP(39)
-#undef Q8_OP
+            static_for<L.n>(run);
         };
         auto read_q8 = [&](int dx, int row, unsigned rel = 0u) {      // the fp8 B fragment dx of image row 4h + row (rel: the image's offset from qbase, a multiple of 32)
             unsigned ad = fq[dx];
@@ -544,12 +510,7 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
                 }
                 if (s < 5) fr8[(dx + 3 - (s & 3)) & 3] = read_q8(dx, s + 1, qshort);
                 run_ops(std::integral_constant<int, 1>{}, S_, DX_);
-#pragma unroll
-                for (int i_ = 0; i_ < 3; ++i_) {
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i_ == 0 && s < 5) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, 12, 0);
-                }
+                pin_mfmas<nm, s < 5 ? 2 : 0, 12>();
                 __builtin_amdgcn_sched_barrier(0);
             };
             chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{}); chunk(std::integral_constant<int, 2>{});
@@ -559,9 +520,7 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
 #endif
             Q8_STAMP(4 + s)
         };
-#define Q8_STEP(S) step_s(std::integral_constant<int, S>{});
-        Q8_STEP(0) Q8_STEP(1) Q8_STEP(2) Q8_STEP(3) Q8_STEP(4) Q8_STEP(5)
-#undef Q8_STEP
+        static_for<6>(step_s);
         if (RES) { op_radd(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}); op_radd(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}); }
         Q8_STAMP(10)
         __builtin_amdgcn_s_barrier();                                    // nobody reads the fp8 image (a_lo) any more
@@ -617,13 +576,8 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
                     }
                 }
                 run_ops(std::integral_constant<int, 2>{}, S_, F_);
-#pragma unroll
-                for (int i_ = 0; i_ < 3; ++i_) {
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i_ == 0 && s < 5) __builtin_amdgcn_sched_group_barrier(0x100, (ks == 0 && !late8) ? 3 : 1, 0);
-                    if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, 5, 0);
-                }
-                if (late8 && f == 11) {
+                pin_mfmas<nm, s < 5 ? ((ks == 0 && !late8) ? 3 : 1) : 0, 5>();
+                if (late8 && f == 11) {      // (its own spelling: DS reads behind EVERY one of the three fp8 MFMAs, not only the first)
 #pragma unroll
                     for (int i_ = 0; i_ < 3; ++i_) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -631,26 +585,16 @@ __global__ __launch_bounds__(256) void conv64_q8_kernel(ConvX3Args a)
                         __builtin_amdgcn_sched_group_barrier(0x006, 10, 0);
                     }
                 }
-                if (!late8 && ks == 3) {
-#pragma unroll
-                    for (int i_ = 0; i_ < 3; ++i_) {
-                        if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i_ < nm) __builtin_amdgcn_sched_group_barrier(0x006, 10, 0);
-                    }
-                }
+                if constexpr (!late8 && ks == 3) pin_mfmas<nm, 0, 10>();
                 __builtin_amdgcn_sched_barrier(0);
             };
-#define Q8_CHUNK(F) chunk(std::integral_constant<int, F>{});
-            Q8_CHUNK(0) Q8_CHUNK(1) Q8_CHUNK(2) Q8_CHUNK(3) Q8_CHUNK(4) Q8_CHUNK(5) Q8_CHUNK(6) Q8_CHUNK(7) Q8_CHUNK(8) Q8_CHUNK(9) Q8_CHUNK(10) Q8_CHUNK(11)
-#undef Q8_CHUNK
+            static_for<12>(chunk);
 #ifdef Q8_STEPWAIT
             __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
             Q8_STAMP(15 + s)
         };
-#define Q8_STEP(S) step_l(std::integral_constant<int, S>{});
-        Q8_STEP(0) Q8_STEP(1) Q8_STEP(2) Q8_STEP(3) Q8_STEP(4) Q8_STEP(5)
-#undef Q8_STEP
+        static_for<6>(step_l);
         run_ops(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});      // output row 3 of the wave
         Q8_STAMP(21)
         it_cur = itn;

@@ -14,10 +14,10 @@
 // 64->64 conv moves 256 bytes for 73,728 FLOP per pixel, 4.2 TB/s at that speed: it sits at the machine's balance point and no schedule helps; SEDN's rblock.0 stays
 // on conv3x3_rw.  What would help there is fewer bytes: rblock.0 + rblock.2 in one kernel.
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #ifndef S64_FILL
 #define S64_FILL 5
@@ -35,17 +35,7 @@ constexpr int OFF_TAB = OFF_DUMP + 1024;       // 28,672: [entry 7][thread 128] 
 constexpr int OFF_RES = OFF_TAB + 8 * 512;     // 32,768
 constexpr int LDS_PLAIN = OFF_RES, LDS_RES = OFF_RES + NRING * RESBLKB;      // 32,768 / 57,344
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-typedef const __attribute__((address_space(3))) u4_t* lds_u4_t;
-
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_RHI, OP_ACT, OP_ST };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[48] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-};
 constexpr OpList dma_ops(int e, int np)      // (conv64_sq.hip: half 0 the lane's table word, half 1 select + issue)
 {
     OpList r;
@@ -78,7 +68,6 @@ template <int EPI>
 __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     constexpr bool RES = EPI == 6, PLANEW = EPI == 6;
     constexpr int NP = 5 + (RES ? 4 : 0);       // DMA pieces a wave issues per block: a_hi 2i + c (nine exist), residual 2i + c (eight)
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -89,15 +78,11 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
     const int H = a.H, W = a.W;
 
     const int px = (W + TW - 1) / TW, nyb = H / RB;
-    const int g = blockIdx.x, G = gridDim.x;
-    const long long nitems = (long long)a.B * px * nyb;
-    int item = (int)(nitems * g / G);
-    const int item_end = (int)(nitems * (g + 1) / G);
-    if (item >= item_end) return;
+    StripRange range(a.B, px, nyb, blockIdx.x, gridDim.x);
+    if (!range.more()) return;
 
     half8_t w16[36];
-    const int wi = lane & 31, wq = wi >> 3;
-    const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));      // MFMA row -> channel order (conv3x3_rw.hip)
+    const int src = weight_row(j, hh);
     auto load_weights = [&](int b) {
         const half_t* wp = a.wpk + (PLANEW ? (long long)b * 72 * 512 : 0ll);
 #pragma unroll
@@ -159,8 +144,7 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
     unsigned fa[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-        const int cc = j + dx;
-        fa[dx] = lds0 + (unsigned)(cc * 128 + ((((cc >> 1) & 7) ^ hh) << 4));
+        fa[dx] = frag_addr(lds0, j + dx, hh);
         asm volatile("" : "+v"(fa[dx]));
     }
     unsigned ra[2];
@@ -172,7 +156,6 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
         const half2_t s2 = {(half_t)a.slope, (half_t)a.slope};
         slope2 = __builtin_bit_cast(unsigned, s2);
     }
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4];
 #pragma unroll
@@ -181,14 +164,10 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
     u4_t rh[2];
     unsigned sh[4];
 
-    while (item < item_end) {
-        const int s0 = item % nyb;
-        const int t_ = item / nyb;
-        const int pxi = t_ % px, b = t_ / px;
-        const int s1 = min(nyb, s0 + (item_end - item));
-        item += s1 - s0;
-        const int x0 = pxi * TW;
-        const int ya = RB * s0, yb = RB * s1;
+    while (range.more()) {
+        const Strip st = range.next();
+        const int b = st.b, x0 = st.pxi * TW;
+        const int ya = RB * st.s0, yb = RB * st.s1;
         const int nblk = (yb - ya) / RB + 2;
         const unsigned vo = (x0 + j < W) ? lane_ob : kOOR;
 
@@ -291,10 +270,7 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
                                 op_dma(std::integral_constant<int, o.a>{}, std::integral_constant<int, o.b>{});
                             }
                         };
-#define S64_OP(I) rund(std::integral_constant<int, I>{});
-                        S64_OP(0) S64_OP(1) S64_OP(2) S64_OP(3) S64_OP(4) S64_OP(5) S64_OP(6) S64_OP(7) S64_OP(8) S64_OP(9) S64_OP(10) S64_OP(11) S64_OP(12) S64_OP(13) S64_OP(14) S64_OP(15)
-                        S64_OP(16) S64_OP(17) S64_OP(18) S64_OP(19)
-#undef S64_OP
+                        static_for<LD.n>(rund);
                         constexpr int lo_ = ai * L.n / 12, hi_ = (ai + 1) * L.n / 12;
                         auto run = [&](auto I_) __attribute__((always_inline)) {
                             constexpr int I = decltype(I_)::value;
@@ -305,23 +281,14 @@ __global__ __launch_bounds__(128) void conv64_s_kernel(ConvArgs a)
                                 if constexpr (o.kind == OP_ST) op_st(std::integral_constant<int, o.a>{});
                             }
                         };
-#define S64_OP(I) run(std::integral_constant<int, I>{});
-                        S64_OP(0) S64_OP(1) S64_OP(2) S64_OP(3) S64_OP(4) S64_OP(5) S64_OP(6) S64_OP(7) S64_OP(8) S64_OP(9) S64_OP(10) S64_OP(11)
-#undef S64_OP
+                        static_for<L.n>(run);
                     }
 #ifndef S64_NOPIN
-#pragma unroll
-                    for (int i_ = 0; i_ < 3; ++i_) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x006, S64_FILL, 0);
-                    }
+                    pin_mfmas<3, 1, S64_FILL>();
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 };
-#define S64_CHUNK(A) chunk(std::integral_constant<int, A>{});
-                S64_CHUNK(0) S64_CHUNK(1) S64_CHUNK(2) S64_CHUNK(3) S64_CHUNK(4) S64_CHUNK(5) S64_CHUNK(6) S64_CHUNK(7) S64_CHUNK(8) S64_CHUNK(9) S64_CHUNK(10) S64_CHUNK(11)
-#undef S64_CHUNK
+                static_for<12>(chunk);
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});

@@ -25,10 +25,10 @@
 // Same operands, same products, same scales as conv64_q8.hip, one accumulator set; only the order of the sums inside a row differs: results agree to fp32
 // rounding, and -- through the fp8 low words between the layers -- to a few 1e-5 at the net's output (tests/test_gpu_parity.py).
 #include "common.h"
+#include "mfma_stream.h"
 #include "rowtile.h"
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #ifndef SQ_FILL
 #define SQ_FILL 5
@@ -61,20 +61,7 @@ constexpr int OFF_TAB = OFF_DUMP + 1024;       // 48,640: the lanes' DMA source 
 constexpr int OFF_RES = OFF_TAB + 10 * 512;    // 53,760
 constexpr int LDS_PLAIN = OFF_RES, LDS_RES = OFF_RES + NRING * RESBLKB;      // 53,760 / 78,336
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-typedef int i8v_t __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(3))) half8_t* lds_h8_t;
-typedef const __attribute__((address_space(3))) u4_t* lds_u4_t;
-
 enum OpKind : int { OP_NONE = 0, OP_DMA, OP_CVR, OP_CVW, OP_RHI, OP_ADD, OP_ACT, OP_SPL, OP_ST, OP_XLO };
-struct Op { int kind, a, b, c; };
-struct OpList {
-    int n = 0;
-    Op op[64] = {};
-    constexpr void push(int kind, int a = 0, int b = 0, int c = 0) { op[n] = Op{kind, a, b, c}; ++n; }
-};
 // The side work of a row step, two lists dealt to its chunks proportionally.  dma_ops (e = 1, chunks 0..7): the wave's DMA pieces of the block after the next --
 // half 0: the lane's table word, half 1: select + issue; the word of piece i + 1 is read in front of piece i's issue.  step_ops (chunks 0..11, behind the
 // chunk's DMA ops): the wave's two units of the next row's fp8 image (in LDS before the barrier at chunk 10); the two 16-byte slots of output row r - 2 --
@@ -135,7 +122,6 @@ template <int EPI, bool OUT8>
 __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr unsigned kOOR = 0xFFFF0000u;
     constexpr bool RES = EPI == 2;
     constexpr int NP = 5 + 3 + (RES ? 4 : 0);   // DMA pieces a wave issues per block: a_hi 2i + c (nine exist), a_lo8 2i + c (five exist), residual 2i + c (eight)
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1\n\ts_nop 3" ::: "memory");      // MODE.FP16_OVFL: the fp8 conversions saturate (conv64_q8.hip)
@@ -147,18 +133,14 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
     const int H = a.H, W = a.W;
 
     const int px = (W + TW - 1) / TW, nyb = H / RB;
-    const int g = blockIdx.x, G = gridDim.x;
-    const long long nitems = (long long)a.B * px * nyb;
-    int item = (int)(nitems * g / G);
-    const int item_end = (int)(nitems * (g + 1) / G);
-    if (item >= item_end) return;
+    StripRange range(a.B, px, nyb, blockIdx.x, gridDim.x);
+    if (!range.more()) return;
 
     // ---- weights (conv64_q8.hip: MFMA row i = 8q + 4h' + e is given channel 16 (q >> 1) + 8 h' + 4 (q & 1) + e: a lane's registers 8g .. 8g+7 are one 16-byte slot)
     half8_t w16[36];
     i8v_t wl8[9], wh8[9];
     {
-        const int wi = lane & 31, wq = wi >> 3;
-        const int src = (lane & 32) | (16 * (wq >> 1) + 8 * ((wi >> 2) & 1) + 4 * (wq & 1) + (wi & 3));
+        const int src = weight_row(j, hh);
 #pragma unroll
         for (int f = 0; f < 36; ++f) w16[f] = *(const half8_t*)(a.wq_hi16 + ((f * 2 + c) * 64 + src) * 8);
 #pragma unroll
@@ -253,7 +235,7 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
         const int cc = j + dx;
-        fa[dx] = lds0 + (unsigned)(cc * 128 + ((((cc >> 1) & 7) ^ hh) << 4));
+        fa[dx] = frag_addr(lds0, cc, hh);
         fq[dx] = lds0 + (unsigned)(cc * 64 + (((2 * hh) ^ ((cc >> 2) & 3)) << 4));
         asm volatile("" : "+v"(fa[dx]), "+v"(fq[dx]));
     }
@@ -271,32 +253,11 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
         cv_src[u] = lds0 + (unsigned)(q * 128 + (((2 * s8) ^ ((q >> 1) & 7)) << 4));      // slot 2 s8; slot 2 s8 + 1 is this address ^ 16
         cv_dst[u] = lds0 + (unsigned)OFF_Q8 + (unsigned)(q * 64 + ((s8 ^ ((q >> 2) & 3)) << 4));
     }
-    const float quarter = 4.0f;                               // the source is DIVIDED by the scale operand
-    // four packed fp16 pairs -> two words of four fp8 each (one block, the conversions of the two words alternating, a wait state at its end: conv64_q8.hip)
-    auto cvt4 = [&](unsigned a0, unsigned a1, unsigned b0, unsigned b1, unsigned& p0, unsigned& p1) __attribute__((always_inline)) {
-        asm volatile("v_cvt_scalef32_pk_fp8_f16 %0, %2, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %4, %6\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %0, %3, %6 op_sel:[0,0,1]\n\t"
-                     "v_cvt_scalef32_pk_fp8_f16 %1, %5, %6 op_sel:[0,0,1]\n\t"
-                     "s_nop 0"
-                     : "=&v"(p0), "=&v"(p1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(quarter));
-    };
-    auto cvt16 = [&](const u4_t& w0, const u4_t& w1) {
-        u4_t d = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            unsigned p0, p1;
-            cvt4(w0[2 * k], w0[2 * k + 1], w1[2 * k], w1[2 * k + 1], p0, p1);
-            d[k] = p0; d[2 + k] = p1;
-        }
-        return d;
-    };
     // this lane's two 16-byte slots (channels 32 c + 16 o + 8 hh .. +7) of pixel column j: in the residual ring at slot (4 c + 2 o + hh) ^ ((j >> 1) & 7)
     unsigned ra[2];
 #pragma unroll
     for (int o = 0; o < 2; ++o) ra[o] = lds0 + (unsigned)OFF_RES + (unsigned)(j * 128 + (((4 * c + 2 * o + hh) ^ ((j >> 1) & 7)) << 4));
     const unsigned lane_ob = (unsigned)(j * 128 + (32 * c + 8 * hh) * 2);      // byte offset of slot o = 0 of output column j inside a row of the stream tensors
-    const float16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     float16_t acc[4];                          // step t (input row ya - 1 + t): output row t + 1 - dy (relative to ya - 1) in acc[(t + 3 - dy) & 3]
 #pragma unroll
@@ -308,14 +269,10 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
     unsigned sh[4], sl[4];
     xl[0][0] = xl[0][1] = xl[1][0] = xl[1][1] = u2_t{0u, 0u};
 
-    while (item < item_end) {
-        const int s0 = item % nyb;
-        const int t_ = item / nyb;
-        const int pxi = t_ % px, b = t_ / px;
-        const int s1 = min(nyb, s0 + (item_end - item));
-        item += s1 - s0;
-        const int x0 = pxi * TW;
-        const int ya = RB * s0, yb = RB * s1;
+    while (range.more()) {
+        const Strip st = range.next();
+        const int b = st.b, x0 = st.pxi * TW;
+        const int ya = RB * st.s0, yb = RB * st.s1;
         const int nblk = (yb - ya) / RB + 2;                  // steps t = 0 .. yb - ya + 3: input rows ya - 1 .. yb + 2 (the last output row completes with row yb and is finished a step later)
 #if SQ_ABL & 128     // (timing experiment: every store is issued and dropped by the buffer's range check)
         const unsigned vo = kOOR, vo8 = kOOR;
@@ -490,10 +447,7 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
                                 op_dma(std::integral_constant<int, o.a>{}, std::integral_constant<int, o.b>{});
                             }
                         };
-#define SQ_OP(I) rund(std::integral_constant<int, I>{});
-                        SQ_OP(0) SQ_OP(1) SQ_OP(2) SQ_OP(3) SQ_OP(4) SQ_OP(5) SQ_OP(6) SQ_OP(7) SQ_OP(8) SQ_OP(9) SQ_OP(10) SQ_OP(11) SQ_OP(12) SQ_OP(13) SQ_OP(14) SQ_OP(15)
-                        SQ_OP(16) SQ_OP(17) SQ_OP(18) SQ_OP(19) SQ_OP(20) SQ_OP(21) SQ_OP(22) SQ_OP(23) SQ_OP(24) SQ_OP(25) SQ_OP(26) SQ_OP(27) SQ_OP(28) SQ_OP(29) SQ_OP(30) SQ_OP(31)
-#undef SQ_OP
+                        static_for<LD.n>(rund);
                         constexpr int lo_ = ai * L.n / 12, hi_ = (ai + 1) * L.n / 12;
                         auto run = [&](auto I_) __attribute__((always_inline)) {
                             constexpr int I = decltype(I_)::value;
@@ -509,33 +463,15 @@ __global__ __launch_bounds__(128) void conv64_sq_kernel(ConvX3Args a)
                                 if constexpr (o.kind == OP_XLO) op_xlo(std::integral_constant<int, o.a>{});
                             }
                         };
-#define SQ_OP(I) run(std::integral_constant<int, I>{});
-                        SQ_OP(0) SQ_OP(1) SQ_OP(2) SQ_OP(3) SQ_OP(4) SQ_OP(5) SQ_OP(6) SQ_OP(7) SQ_OP(8) SQ_OP(9) SQ_OP(10) SQ_OP(11) SQ_OP(12) SQ_OP(13) SQ_OP(14) SQ_OP(15)
-                        SQ_OP(16) SQ_OP(17) SQ_OP(18) SQ_OP(19) SQ_OP(20) SQ_OP(21) SQ_OP(22) SQ_OP(23) SQ_OP(24) SQ_OP(25) SQ_OP(26) SQ_OP(27) SQ_OP(28) SQ_OP(29) SQ_OP(30) SQ_OP(31)
-                        SQ_OP(32) SQ_OP(33) SQ_OP(34) SQ_OP(35) SQ_OP(36) SQ_OP(37) SQ_OP(38) SQ_OP(39) SQ_OP(40) SQ_OP(41) SQ_OP(42) SQ_OP(43) SQ_OP(44) SQ_OP(45) SQ_OP(46) SQ_OP(47)
-#undef SQ_OP
+                        static_for<L.n>(run);
                     }
 #ifndef SQ_NOPIN
-#pragma unroll
-                    for (int i_ = 0; i_ < 3; ++i_) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x006, SQ_FILL, 0);
-                    }
-                    if (ks == 1 || ks == 3) {
-#pragma unroll
-                        for (int i_ = 0; i_ < 3; ++i_) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            if (i_ == 0) __builtin_amdgcn_sched_group_barrier(0x100, (ks == 3 && dx == 2) ? 4 : 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x006, 2 * SQ_FILL, 0);
-                        }
-                    }
+                    pin_mfmas<3, 1, SQ_FILL>();
+                    if constexpr (ks == 1 || ks == 3) pin_mfmas<3, (ks == 3 && dx == 2) ? 4 : 2, 2 * SQ_FILL>();
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 };
-#define SQ_CHUNK(A) chunk(std::integral_constant<int, A>{});
-                SQ_CHUNK(0) SQ_CHUNK(1) SQ_CHUNK(2) SQ_CHUNK(3) SQ_CHUNK(4) SQ_CHUNK(5) SQ_CHUNK(6) SQ_CHUNK(7) SQ_CHUNK(8) SQ_CHUNK(9) SQ_CHUNK(10) SQ_CHUNK(11)
-#undef SQ_CHUNK
+                static_for<12>(chunk);
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});

@@ -1,5 +1,8 @@
-// rowtile.h -- epilogue helpers shared by the register-weight kernels (arsb_fused.hip, conv64_x3.hip): a finished output row is two
-// 16x16 MFMA tiles per wave (lane (n, q): 4 channels 16w + 4q.. of pixel columns n and 16 + n).
+// rowtile.h -- epilogue arithmetic shared by the MFMA kernels (included by conv3x3_sp.hip, conv3x3_rw.hip, conv3x3_ps4.hip, conv3x3_ps9.hip,
+// arsb32c.hip, conv64_x3.hip, conv64_q8.hip, conv64_sq.hip, arsb_sq.hip, conv64_s.hip, conv1x1.hip, conv1x1_f2.hip): mix_lo / mix_hi and split2 for
+// all of them; finish_row for conv64_x3.hip, where a finished output row is two 16x16 MFMA tiles per wave (lane (n, q): 4 channels 16w + 4q.. of
+// pixel columns n and 16 + n).
+// (The stream machinery of the register-weight kernels -- op tables, dealing, pinning -- is mfma_stream.h's.)
 //
 // The epilogues ride in the MFMA stream of a single wave per SIMD; beside 16-cycle MFMAs only ~2 other instructions per MFMA are
 // hidden (profiles/r02: a row's 36 MFMAs take 640 cycles bare, +6.4 cycles for every filler beyond ~70), so these helpers are
