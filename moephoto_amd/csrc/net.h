@@ -331,15 +331,26 @@ struct Fwd {
     template <typename T> T* blob(size_t off) const { return (T*)(n.blob + off); }
     template <typename T> T* small(const std::string& k) const { return (T*)(n.blob + n.small.at(k)); }
 
+    // tap `name`: the activation as fp32, hi + lo 2^-11 where it has a low part.  That sum does not say which fp16 value a single-pass reader of the pair takes
+    // (a low part of exactly half an ulp puts the sum midway between two fp16 values), so a pair also leaves tap `name`.hi: its fp16 part alone
     void tap(const std::string& name, const Act& a, int H, int W, int cs, int C)
     {
         if (!n.debug || dry()) return;
+        tap_part(name, a.hi, a.lo, H, W, cs, C);
+        if (a.lo) tap_part(name + ".hi", a.hi, nullptr, H, W, cs, C);
+        else {      // (no stale fp16 part of an earlier forward that kept a pair here)
+            auto it = rt->taps.find(name + ".hi");
+            if (it != rt->taps.end()) { if (it->second.dev) (void)hipFree(it->second.dev); rt->taps.erase(it); }
+        }
+    }
+    void tap_part(const std::string& name, const half_t* hi, const half_t* lo, int H, int W, int cs, int C)
+    {
         auto& t = rt->taps[name];
         if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
         const size_t nel = (size_t)B * C * H * W;
         if (hipMalloc((void**)&t.dev, nel * 4) != hipSuccess) return;
         t.shape[0] = B; t.shape[1] = C; t.shape[2] = H; t.shape[3] = W;
-        launch_nhwc_to_nchw_f32(a.hi, a.lo, t.dev, B, H, W, cs, C, s);
+        launch_nhwc_to_nchw_f32(hi, lo, t.dev, B, H, W, cs, C, s);
     }
 
     // MIXED: which fused-tail launches also split the activation operand.  The R branch (trunk -> upsampler -> tail) carries the larger

@@ -26,13 +26,33 @@ import golden_defs as gd  # noqa: E402
 
 
 def r16(x):
-    return x.half().float()
+    """x rounded to fp16 (nearest even), in x's own dtype.  float64 goes through numpy, which rounds a double to half in one step (torch goes through
+    fp32: a double rounding on one value in 2^13)."""
+    if x.dtype == torch.float64:
+        return torch.from_numpy(x.contiguous().numpy().astype(np.float16).astype(np.float64))
+    return x.half().to(x.dtype)
 
 
 def q8(x, shift):
-    """x rounded to OCP fp8 e4m3 after scaling by 2^shift (saturating at +-448), as a scaled-MFMA operand would carry it."""
-    v = torch.clamp(x * float(2 ** shift), -448.0, 448.0)
-    return v.to(torch.float8_e4m3fn).float() * float(2.0 ** -shift)
+    """x rounded to OCP fp8 e4m3 after scaling by 2^shift (saturating at +-448), as a scaled-MFMA operand would carry it.  `x` holds fp16 values (or fp16
+    values times a power of two), so the step through fp32 is exact."""
+    v = torch.clamp(x * float(2.0 ** shift), -448.0, 448.0)
+    return v.float().to(torch.float8_e4m3fn).to(x.dtype) * float(2.0 ** -shift)
+
+
+def hilo(v):
+    """(hi, lo) of rowtile.h's split2: hi = fp16(v), lo = fp16((v - hi) 2^11) -- the stored form of the stem output and the trunk stream in 'mixed';
+    the value a reader of the pair sees is hi + lo 2^-11."""
+    h = r16(v)
+    return h, r16((v - h) * 2048.0)
+
+
+def prelu16(h, slope):
+    """PReLU of the kernels that store an fp16 activation (arsb32c.hip op_p, conv3x3_rw.hip act8, conv3x3_sp.hip EPI 1, conv3x3_ps4 / ps9 without the
+    split): the value is rounded to fp16 FIRST (`h`), then max(h, fp16(h * fp16(slope))) on packed halves -- the slope is an fp16 number there and the
+    negative branch is rounded twice."""
+    s = float(np.float16(slope))
+    return torch.maximum(h, r16(h * s))
 
 
 def q6_block(x, dim, fmt='e2m3'):
@@ -109,59 +129,103 @@ def layer_names(arch):
     return out
 
 
-def forward(arch, sd, x, w16=(), a16=(), stream16=False, corr8=(), shifts=(8, 4), lo8=False, corr6=None, wino=(), wino_mode='v1'):
+def forward(arch, sd, x, w16=(), a16=(), stream16=False, corr8=(), shifts=(8, -2), lo8=False, corr6=None, wino=(), wino_mode='v1', pairs=None, taps=None):
     """w16 / a16: names of the convs whose weights / input activations are rounded to fp16 ('all' = every conv);
     stream16: the trunk stream is stored as fp16 after conv_input2 and after every ARSB.
-    corr8: convs computed as  conv(w16, a16) + conv(fp8(w - w16), fp8(a16)) + conv(fp8(w16), fp8(a - a16))  -- the split-operand form with its two
-    correction products on fp8 operands (scaled by 2^shifts[0] for weights, 2^shifts[1] for activations): a study for the block-scaled fp8 MFMA, which
-    runs at twice the fp16 rate (`python tests/emu_precision.py corr8`).
+    corr8: convs computed as  conv(w_hi, a_hi) + 2^-11 (conv(fp8(w_lo), fp8(a_hi)) + conv(fp8(w_hi), fp8(a_lo)))  -- the split-operand form with its two
+    correction products on fp8 operands, the fp16 parts and the fp16 remainders (units of 2^-11) scaled by 2^shifts[0] for weights and 2^shifts[1] for
+    activations.  (8, -2) is what ships: weights.cpp pack_q8 stores e4m3(w 2^8), conv64_q8.hip converts a / 4 (mfma_stream.h cvt4) -- so an activation's fp16
+    part below 2^-4 is an e4m3 subnormal, and its remainder reaches the fp8 word as (a - a_hi) 2^9 (`python tests/emu_precision.py corr8` has other scalings).
     lo8: the trunk stream is stored as fp16 + an fp8 e4m3 low part ((t - fp16(t)) 2^9, the operand the fp8 correction product reads anyway): 192 instead of
-    256 bytes a pixel through HBM, ~15 bits of the value (`python tests/emu_precision.py lo8`)."""
+    256 bytes a pixel through HBM, ~15 bits of the value (`python tests/emu_precision.py lo8`).
+    pairs: what 'mixed' keeps to ~22 bits is stored as hi + lo 2^-11 (`hilo`): the stem output, the trunk stream, conv_1's output inside a split-operand ARSB,
+    the activations of the R branch's fused tail, the tail convs' weights; a single-pass reader of a pair takes its fp16 part `hi`.  None: on whenever
+    something is rounded and the stream is not fp16.
+    An fp16 activation is PReLU'd AFTER its rounding, on packed halves (`prelu16`), as the kernels do; a pair in fp32, before it.
+    taps: a dict that receives the engine's debug taps by name (stem, input2, arsb1..6, r.up*, u.up*), and NAME.hi for the fp16 part of a pair."""
     T = lambda k: torch.from_numpy(np.asarray(sd[k], dtype=np.float32))
     r = 3 if arch == 'net3x' else 2
+    every16 = 'all' in a16
+    if pairs is None:
+        pairs = bool(w16 or a16 or corr8) and not stream16
 
-    def conv(name, v, w, b=None):
+    def P(name, v):
+        """v as it is stored: (value, fp16 part or None)"""
+        h = None
+        if pairs:
+            h, l = hilo(v)
+            v = h + l * (1.0 / 2048.0)
+        if taps is not None and name:
+            taps[name] = v.clone()
+            if h is not None:
+                taps[name + '.hi'] = h.clone()
+        return v, h
+
+    def conv(name, v, w, b=None, vh=None):
         if name in wino:                 # Winograd-domain kernel: fp16 activations in, U and V rounded to fp16
             return wino_conv(r16(v), w, b, wino_mode)
+        if vh is None:
+            vh = r16(v)
         if name in corr8 and corr6:      # the two correction products on block-scaled fp6 operands (blocks of 32 input channels)
-            wh, vh = r16(w), r16(v)
+            wh = r16(w)
             return (F.conv2d(vh, wh, b, padding=1) + F.conv2d(q6_block(vh, 1, corr6), q6_block(w - wh, 1, corr6), None, padding=1)
                     + F.conv2d(q6_block(v - vh, 1, corr6), q6_block(wh, 1, corr6), None, padding=1))
         if name in corr8:
-            wh, vh = r16(w), r16(v)
+            wh, wl = hilo(w)
+            vl = r16((v - vh) * 2048.0)
             sw, sa = shifts
-            return F.conv2d(vh, wh, b, padding=1) + F.conv2d(q8(vh, sa), q8(w - wh, sw + 11), None, padding=1) + F.conv2d(q8(v - vh, sa + 11), q8(wh, sw), None, padding=1)
+            return F.conv2d(vh, wh, b, padding=1) + (F.conv2d(q8(vh, sa), q8(wl, sw), None, padding=1) + F.conv2d(q8(vl, sa), q8(wh, sw), None, padding=1)) * (1.0 / 2048.0)
         if name in w16 or 'all' in w16:
             w = r16(w)
-        if name in a16 or 'all' in a16:
-            v = r16(v)
+        if name in a16 or every16:
+            v = vh
         return F.conv2d(v, w, b, padding=1)
+
+    def w22(w):                          # a tail conv's weights to ~22 bits (weights.cpp Packer::tail: fp16 part + fp16 remainder)
+        if not pairs:
+            return w
+        h, l = hilo(w)
+        return h + l * (1.0 / 2048.0)
     x = torch.from_numpy(np.asarray(x, dtype=np.float32))
-    out = prelu(F.conv2d(x, T('conv_input.weight'), padding=1), float(T('relu.weight')[0]))       # the stem is fp32 in every mode
-    t = conv('input2', out, T('conv_input2.weight'))
+    out, outh = P('stem', prelu(F.conv2d(x, T('conv_input.weight'), padding=1), float(T('relu.weight')[0])))       # the stem is fp32 in every mode
+    t = conv('input2', out, T('conv_input2.weight'), vh=outh)
     s8 = (lambda v: r16(v) + q8(v - r16(v), 9)) if lo8 else (lambda v: v)
     if stream16:
         t = r16(t)
+    t, th = P('input2', t)
     t = s8(t)
     for i in range(1, 7):
         p = 'convt_F{}.0.'.format(i)
-        m = prelu(conv('c1_%d' % i, t, T(p + 'conv_1.weight')), float(T(p + 'relu.weight')[0]))
-        t = t + conv('c2_%d' % i, m, T(p + 'conv_2.weight') * float(T(p + 'scale.scale')[0]))    # ScaleLayer folded into the weights (fp32 product)
+        slope = float(T(p + 'relu.weight')[0])
+        m = conv('c1_%d' % i, t, T(p + 'conv_1.weight'), vh=th)
+        if 'c2_%d' % i in a16 or every16:      # single-pass block: conv_1's output is an fp16 operand
+            m, mh = prelu16(r16(m), slope), None
+        else:
+            m, mh = P(None, prelu(m, slope))
+        t = t + conv('c2_%d' % i, m, T(p + 'conv_2.weight') * float(T(p + 'scale.scale')[0]), vh=mh)    # ScaleLayer folded into the weights (fp32 product)
         if stream16:
             t = r16(t)
+        t, th = P('arsb%d' % i, t)
         t = s8(t)
     if arch == 'netdn':
-        return conv('r.tail', t, T('convt_R1.weight')) + conv('u.tail', out, T('u.weight'))
+        return conv('r.tail', t, w22(T('convt_R1.weight')), vh=th) + conv('u.tail', out, w22(T('u.weight')), vh=outh)
 
-    def ups(pre, tag, v):
+    def ups(pre, tag, v, vh):
         k = 0
         while '{}{}.0.weight'.format(pre, k) in sd:
             p = '{}{}.'.format(pre, k)
-            v = conv('%s.up%d' % (tag, k), v, T(p + '0.weight'), T(p + '0.bias'))
-            v = prelu(shuffle(v, r), float(T(p + '2.weight')[0]))
+            v = shuffle(conv('%s.up%d' % (tag, k), v, T(p + '0.weight'), T(p + '0.bias'), vh=vh), r)
             k += 1
-        return conv('%s.tail' % tag, v, T('{}{}.weight'.format(pre, k)))
-    return ups('convt_R1.', 'r', t) + ups('u.', 'u', out)
+            nxt = '%s.up%d' % (tag, k) if '{}{}.0.weight'.format(pre, k) in sd else '%s.tail' % tag
+            slope = float(T(p + '2.weight')[0])
+            if nxt in a16 or every16:
+                v, vh = prelu16(r16(v), slope), None
+                if taps is not None:
+                    taps['%s.up%d' % (tag, k - 1)] = v.clone()
+            else:
+                v, vh = P('%s.up%d' % (tag, k - 1), prelu(v, slope))
+        return conv('%s.tail' % tag, v, w22(T('{}{}.weight'.format(pre, k))), vh=vh)
+    return ups('convt_R1.', 'r', t, th) + ups('u.', 'u', out, outh)
 
 
 def mode_sets(arch, mode, n_exact=0):
@@ -359,7 +423,7 @@ def main(argv):
                     want = forward(arch, sd, x)
                     w16, a16, s16 = mode_sets(arch, 'mixed', n)
                     line = '%-9s %-8s n=%d: split fp16x3 %.3e' % (key, kind, n, float((forward(arch, sd, x, w16, a16, s16) - want).abs().max()))
-                    for sh in ((8, 4), (6, 2), (10, 6)):
+                    for sh in ((8, -2), (8, 4), (6, 2), (10, 6)):      # (8, -2) ships
                         line += ' | fp8 corrections 2^%d/2^%d %.3e' % (sh[0], sh[1], float((forward(arch, sd, x, w16, a16, s16, corr8=ex, shifts=sh) - want).abs().max()))
                     line += ' | no corrections (n=0, input2 fp16) %.3e' % float((forward(arch, sd, x, set(layer_names(arch)) - {'r.tail', 'u.tail'}, set(layer_names(arch)) - ({'r.tail', 'u.tail'} if arch == 'netdn' else {'r.tail'}), False) - want).abs().max())
                 print(line, flush=True)
