@@ -19,6 +19,7 @@
  *                         device resident, batched over same-shaped tiles
  *   moe_run_plan_ens      the SR self-ensemble around doCrop (python/imageProcess.py:563-572, runSR.py:26): moe_sym_pad / moe_sym_fold are its two passes
  *   moe_to_float/_output  toTorch / toOutput (python/imageProcess.py:245-263)
+ *   moe_*_planes*         no counterpart: a video chain on the decoder's own Y'CbCr 4:2:0 planes instead of the bgr24 / bgr48le pipe (python/video.py:24,219)
  *
  * All functions return 0 on success or a negative MOE_E* code; moe_last_error() returns a
  * thread-local description (the Python wrapper raises RuntimeError / MemoryError from it, matching
@@ -304,6 +305,26 @@ int moe_stitch_yuv(const moe_plan* plan, int device, const float* tiles_dev, con
 /* moe_run_plan_out with its final fold replaced by moe_stitch_yuv. */
 int moe_run_plan_yuv(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                      int canvas_dtype, int depth, int matrix, int order, void* dst, int max_tiles_per_batch, void* stream);
+
+/* ---- chains on the decoder's own Y'CbCr 4:2:0 planes ------------------------------------------------------
+ * The reference asks its decoder for bgr24 / bgr48le (python/video.py:24,219) and sends three full planes through the net.  None of the SR / DN nets convolves planes
+ * jointly (planes are the batch: python/runSR.py:37-40), so a chain can run on the decoder's planes as they are: Y' as a (1, H, W) image, Cb and Cr as a (2, H / 2, W / 2)
+ * image -- half the plane-pixels, no colour matrix at either end, limited range kept as it is.  The definition is moephoto_amd/pixfmt.py (toPlanes / fromPlanes): a value is
+ * code * 2^-depth at every depth (8 bits: / 256, so a depth change is a shift and neutral chroma is 0.5), a sample is moe_to_output's quantiser with bits = depth.
+ *
+ * moe_planes_to_float: src = a planar frame of H x W on the device (uint8 for depth 8, little-endian uint16 for depth 10, 12, 16; the Y plane, then Cb, then Cr; codes
+ * are taken as they are, high bits are not masked) -> dst_y = (1, H, W), dst_c = (2, H / 2, W / 2), contiguous, of dst_dtype MOE_F32 (exact) / MOE_F16 (rounded to
+ * nearest even), in one launch.  H and W even, 2 at least; src 2-byte aligned for depth > 8 (16-byte aligned is the fast path). */
+int moe_planes_to_float(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, int device, void* stream);
+/* moe_stitch_out's fold with a planar result at `depth` 8, 10, 12 or 16: dst = C (1 .. 4) planes of out_h x out_w samples, plane c at dst + c * out_h * out_w elements,
+ * uint8 for depth 8, else uint16 -- per sample the bytes moe_stitch -> moe_to_output(H = C * out_h, W = out_w, C = 1, bits = depth) give, and for C = 1 at depth 8 or 16
+ * those of moe_stitch_out.  dst: any 2-byte aligned address (any address for depth 8) -- the Cb plane of a frame starts wherever its Y plane ends.  tile_off_dev: on the
+ * DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+int moe_stitch_planes(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int depth,
+                      void* dst, void* stream);
+/* moe_run_plan_out with its final fold replaced by moe_stitch_planes (C = the plan's planes). */
+int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                        int canvas_dtype, int depth, void* dst, int max_tiles_per_batch, void* stream);
 
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.

@@ -448,6 +448,7 @@ struct StitchArgs {
 };
 void launch_stitch(const StitchArgs& a, hipStream_t s);
 bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s);      // the fold + the canvas dtype's rounding + to_output's quantiser: a.out = interleaved u8 / u16
+void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s);     // the same quantiser at `depth` bits, planar: a.out = a.C planes of out_h x out_w u8 (depth 8) / u16
 // The DN step's edge inside the stitch (stitch_mix_kernel, plans of scale 1): what RGBFilter does behind doCrop.  T = the canvas dtype.
 struct StitchMix {
     const void* inp; long long sC, sH, sW;           // the image the net saw, dtype T: element (c, y, x) at inp + c sC + y sH + x sW (elements); its top-left out_h x out_w is read
@@ -508,6 +509,8 @@ void launch_wire(bool pack, float* tiles, unsigned* wire, const WireRec* recs, i
 
 void launch_to_float(const void* src, int src_dtype, float inv_or_div, bool divide, int H, int W, int C, void* dst, int dst_dtype, hipStream_t s);
 void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s);
+// a planar 4:2:0 frame of H x W (u8 for depth 8, else u16) -> dst_y (1, H, W) and dst_c (2, H / 2, W / 2), code * 2^-depth (moephoto_amd/pixfmt.py: toPlanes)
+void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, hipStream_t s);
 // (C, H, W) -> (C, h, w); mode 0 nearest, 1 bilinear, 2 bicubic (torch F.interpolate semantics, align_corners = False)
 void launch_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, hipStream_t s);
 // max |a - b| over n floats, atomically folded into *out as the bits of a non-negative float (zero it first)

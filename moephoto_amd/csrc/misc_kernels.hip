@@ -1149,6 +1149,36 @@ __global__ __launch_bounds__(256) void to_output3_kernel(const TS* __restrict__ 
     *(VecN<TD, 24>*)(dst + p0 * 3) = o;
 }
 
+// A planar Y'CbCr 4:2:0 frame as the net's two images (moe_planes_to_float; the definition: pixfmt.toPlanes): the frame is HW Y samples, then HW / 4 Cb and HW / 4 Cr,
+// contiguous, and so are the results -- dst_y = (1, H, W), dst_c = (2, H / 2, W / 2) -- so sample i of the frame goes to dst_y[i] or to dst_c[i - HW], value
+// code * 2^-depth (exact in fp32; fp16 rounds to nearest even).  One launch over all 1.5 HW samples, eight per thread: a thread whose run lies inside one of the two
+// images with both its ends of the copy aligned loads it as one vector (16 bytes of u16 samples, 8 bytes of u8) and stores 16-byte vectors; the run that straddles
+// the Y / Cb border (HW % 8 == 4), the ragged end, an unaligned src or an image behind an odd border go sample by sample.
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void to_float_planes_kernel(const TS* __restrict__ src, TD* __restrict__ dst_y, TD* __restrict__ dst_c, long long HW, float inv)
+{
+    const long long n = HW + HW / 2, i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i0 >= n) return;
+    const bool luma = i0 < HW;
+    TD* const d = luma ? dst_y + i0 : dst_c + (i0 - HW);
+    const bool whole = i0 + 8 <= n && (!luma || i0 + 8 <= HW);
+    if (whole && ((uintptr_t)(src + i0) & (alignof(VecN<TS, 8>) - 1)) == 0 && ((uintptr_t)d & 15) == 0) {
+        const VecN<TS, 8> in = *(const VecN<TS, 8>*)(src + i0);
+        VecN<TD, 8> o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.e[e] = (TD)((float)in.e[e] * inv);
+        *(VecN<TD, 8>*)d = o;
+        return;
+    }
+    for (int e = 0; e < 8; ++e) {
+        const long long i = i0 + e;
+        if (i >= n) break;
+        const TD v = (TD)((float)src[i] * inv);
+        if (i < HW) dst_y[i] = v;
+        else dst_c[i - HW] = v;
+    }
+}
+
 __global__ void nhwc_to_nchw_kernel(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1337,6 +1367,20 @@ void launch_to_float(const void* src, int src_dtype, float d, bool divide, int H
     } else {
         if (dst_dtype == MOE_F16) hipLaunchKernelGGL((to_float_kernel<uint16_t, half_t>), grid, blk, 0, s, (const uint16_t*)src, (half_t*)dst, H, W, C, d, divide);
         else hipLaunchKernelGGL((to_float_kernel<uint16_t, float>), grid, blk, 0, s, (const uint16_t*)src, (float*)dst, H, W, C, d, divide);
+    }
+}
+
+void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, hipStream_t s)
+{
+    const long long HW = (long long)H * W, runs = (HW + HW / 2 + 7) / 8;
+    const dim3 grid((unsigned)((runs + 255) / 256)), blk(256);
+    const float inv = 1.f / (float)(1 << depth);
+    if (depth == 8) {
+        if (dst_dtype == MOE_F16) hipLaunchKernelGGL((to_float_planes_kernel<uint8_t, half_t>), grid, blk, 0, s, (const uint8_t*)src, (half_t*)dst_y, (half_t*)dst_c, HW, inv);
+        else hipLaunchKernelGGL((to_float_planes_kernel<uint8_t, float>), grid, blk, 0, s, (const uint8_t*)src, (float*)dst_y, (float*)dst_c, HW, inv);
+    } else {
+        if (dst_dtype == MOE_F16) hipLaunchKernelGGL((to_float_planes_kernel<uint16_t, half_t>), grid, blk, 0, s, (const uint16_t*)src, (half_t*)dst_y, (half_t*)dst_c, HW, inv);
+        else hipLaunchKernelGGL((to_float_planes_kernel<uint16_t, float>), grid, blk, 0, s, (const uint16_t*)src, (float*)dst_y, (float*)dst_c, HW, inv);
     }
 }
 

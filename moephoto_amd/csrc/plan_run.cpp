@@ -175,8 +175,9 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // {row0, row1, strip}: the rows of tile rows [row0, row1) only, strip != 0 with tile row row1 present as the strips of its blend band.
 // edge: NULL = `out` is the canvas (C, rows, out_w) of out_dtype; else `out` is the quantised interleaved image (out_h, out_w, C) of out_dtype MOE_U8 / MOE_U16
 // (moe_stitch_out: the whole canvas only); with mix the DN step's blend and alpha ride in the fold too (moe_stitch_mix: canvas or samples, mix->quant says which);
-// with yuv `out` is the planar Y'CbCr 4:2:0 frame (moe_stitch_yuv: three planes, the whole canvas).
-struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; };
+// with yuv `out` is the planar Y'CbCr 4:2:0 frame (moe_stitch_yuv: three planes, the whole canvas); with planes_depth `out` is C planes of samples at that depth
+// (moe_stitch_planes: the whole canvas).
+struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; int planes_depth = 0; };
 static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
                   const OutEdge* edge = nullptr)
 {
@@ -231,6 +232,10 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
         launch_stitch_yuv(a, *edge->yuv, s);
         return launched("stitch_yuv");
     }
+    if (edge && edge->planes_depth) {
+        launch_stitch_planes(a, edge->canvas_dtype, edge->planes_depth, s);
+        return launched("stitch_planes");
+    }
     if (edge && edge->mix) {
         if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
         return launched("stitch_mix");
@@ -252,6 +257,21 @@ static int out_edge_args(const char* who, int planes, int canvas_dtype, int bits
     if (bits != 8 && bits != 16) return fail(MOE_EINVAL, "%s: %d bits (8 or 16)", who, bits);
     if (dst_dtype != MOE_U8 && dst_dtype != MOE_U16) return fail(MOE_EINVAL, "%s: dst dtype must be MOE_U8 or MOE_U16", who);
     if (dst_dtype == MOE_U8 && bits > 8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
+    return MOE_OK;
+}
+
+static bool plane_depth(int depth) { return depth == 8 || depth == 10 || depth == 12 || depth == 16; }
+
+// What moe_stitch_planes and moe_run_plan_planes check of their edge before any device call, and the edge itself.  planes: the C the kernel is asked for.
+static int plane_edge_args(const char* who, int planes, int canvas_dtype, int depth, const void* dst, OutEdge* edge)
+{
+    if (!dst) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "%s: %d planes (1 to 4 are supported)", who, planes);
+    if (canvas_dtype != MOE_F32 && canvas_dtype != MOE_F16) return fail(MOE_EINVAL, "%s: canvas dtype must be MOE_F32 or MOE_F16", who);
+    if (!plane_depth(depth)) return fail(MOE_EINVAL, "%s: depth %d (8, 10, 12 or 16)", who, depth);
+    if (depth > 8 && ((uintptr_t)dst & 1)) return fail(MOE_EINVAL, "%s: dst is not 2-byte aligned (depth %d: uint16 samples)", who, depth);
+    *edge = OutEdge{canvas_dtype, (float)(1 << depth)};
+    edge->planes_depth = depth;
     return MOE_OK;
 }
 
@@ -488,6 +508,15 @@ int moe_stitch_out(const moe_plan* p, int device, const float* tiles_dev, const 
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
+int moe_stitch_planes(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int depth, void* dst, void* stream)
+{
+    if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_planes: NULL argument");
+    OutEdge edge{};
+    const int rc = plane_edge_args("moe_stitch_planes", C, canvas_dtype, depth, dst, &edge);
+    if (rc) return rc;
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, depth == 8 ? MOE_U8 : MOE_U16, nullptr, (hipStream_t)stream, &edge);
+}
+
 int moe_stitch_mix(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, const void* inp, int inp_dtype, int64_t sC, int64_t sH, int64_t sW,
                    const void* alpha, int64_t aH, int64_t aW, double strength, int bits, void* dst, int dst_dtype, void* stream)
 {
@@ -548,6 +577,16 @@ int moe_run_plan_out(moe_net* n, const moe_plan* pl, const void* img, int img_dt
     if (rc) return rc;
     const OutEdge edge{canvas_dtype, (float)(1 << bits)};
     return run_plan("moe_run_plan_out", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
+}
+
+int moe_run_plan_planes(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
+                        int canvas_dtype, int depth, void* dst, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_planes: NULL argument");
+    OutEdge edge{};
+    const int rc = plane_edge_args("moe_run_plan_planes", pl->p.C, canvas_dtype, depth, dst, &edge);
+    if (rc) return rc;
+    return run_plan("moe_run_plan_planes", n, pl, img, img_dtype, sC, sH, sW, dst, depth == 8 ? MOE_U8 : MOE_U16, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
 int moe_run_plan_yuv(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
@@ -742,6 +781,20 @@ int moe_to_float(const void* src, int src_dtype, int bits, int H, int W, int C, 
     if (src_dtype == MOE_U8) launch_to_float(src, src_dtype, 255.f, true, H, W, C, dst, dst_dtype, (hipStream_t)stream);
     else launch_to_float(src, src_dtype, 1.f / (float)(1 << bits), false, H, W, C, dst, dst_dtype, (hipStream_t)stream);
     return MOE_OK;
+}
+
+int moe_planes_to_float(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, int device, void* stream)
+{
+    if (!src || !dst_y || !dst_c) return fail(MOE_EINVAL, "moe_planes_to_float: NULL argument");
+    if (!plane_depth(depth)) return fail(MOE_EINVAL, "moe_planes_to_float: depth %d (8, 10, 12 or 16)", depth);
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(MOE_EINVAL, "moe_planes_to_float: size %d x %d (a 4:2:0 frame has an even width and height, 2 at least)", W, H);
+    if (dst_dtype != MOE_F32 && dst_dtype != MOE_F16) return fail(MOE_EINVAL, "moe_planes_to_float: dst dtype must be MOE_F32 or MOE_F16");
+    if (depth > 8 && ((uintptr_t)src & 1)) return fail(MOE_EINVAL, "moe_planes_to_float: src is not 2-byte aligned (depth %d: uint16 samples)", depth);
+    const uintptr_t es = dst_dtype == MOE_F16 ? 2 : 4;
+    if (((uintptr_t)dst_y | (uintptr_t)dst_c) & (es - 1)) return fail(MOE_EINVAL, "moe_planes_to_float: dst_y / dst_c are not aligned to their %d-byte elements", (int)es);
+    HIP_TRY(hipSetDevice(device));
+    launch_to_float_planes(src, depth, H, W, dst_y, dst_c, dst_dtype, (hipStream_t)stream);
+    return launched("to_float_planes");
 }
 
 int moe_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, int device, void* stream)

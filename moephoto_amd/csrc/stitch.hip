@@ -1,4 +1,4 @@
-// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv): one skeleton, three edges on
+// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_planes, moe_stitch_mix, moe_stitch_yuv): one skeleton, four edges on
 // it and the Y'CbCr 4:2:0 edge over the same fold with a body of its own (chroma needs row pairs).
 //
 // Stitch: per-pixel fold of doCrop's sequential blend (imageProcess.py:120-131,167-170).  Every HR pixel visits,
@@ -9,6 +9,7 @@
 // What leaves the fold is the edge's business (an edge = a small policy type handed to stitch_fold):
 //     CanvasEdge     the (C, rows, out_w) planes of the fp16 / fp32 canvas, or a band of its rows                                       stitch8r_kernel
 //     SamplesEdge    the encoder's interleaved u8 / u16 samples: the canvas dtype's rounding and to_output_kernel's quantiser            stitch_out_kernel
+//     PlaneEdge      the same samples at depth 8 / 10 / 12 / 16 as planes, one per blockIdx.z: the planes of a planar 4:2:0 frame            stitch_planes_kernel
 //     MixEdge        the DN step: strengthOp's blend with the image the net saw and the alpha plane, in canvas or sample form            stitch_mix_kernel
 //     (YuvEdge)      the encoder's planar Y'CbCr 4:2:0 frame from SamplesEdge's 16-bit samples: half the bytes of the interleaved image      stitch_yuv_kernel
 // The fold itself (stitch_classify, stitch_fold_row, stitch_pixel) exists once, so the bit equalities the tests demand between the edges (moe_stitch_out == moe_stitch ->
@@ -256,6 +257,38 @@ template <typename TD, int C, int R>
 __global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float quant, int f16)
 {
     stitch_fold<R>(a, SamplesEdge<TD, C>{quant, f16 != 0});
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The same samples as PLANES (moe_stitch_planes): a.out = a.C planes of out_h x out_w quantised samples at depth 8 (u8), 10, 12 or 16 (u16), plane c at
+// a.out + c * out_h * out_w elements -- the Y' plane, or the Cb and Cr planes, of a planar 4:2:0 frame whose chain ran on the decoder's own planes (pixfmt.toPlanes /
+// fromPlanes).  SamplesEdge's quantiser on CanvasEdge's layout: one plane per blockIdx.z, so a thread writes one run of eight samples per row.  The base is aligned
+// only by luck (the Cb plane starts wherever the Y plane ends, inside a frame): every run goes through stitch_store.
+// ---------------------------------------------------------------------------------------------------
+template <typename TD>
+struct PlaneEdge {
+    static constexpr int NP = 1, NOUT = 1;
+    typedef StitchRun<TD, 8> Row;
+    float quant; bool f16;
+    __device__ __forceinline__ int c0() const { return blockIdx.z; }
+    __device__ __forceinline__ int np(const StitchArgs&) const { return 1; }
+    __device__ __forceinline__ long long at(const StitchArgs& a, int X, int Y) const { return ((long long)blockIdx.z * a.out_h + Y) * a.out_w + X; }
+    __device__ __forceinline__ void emit(const StitchArgs&, int, int, const float (&cur)[1][8], Row& o) const
+    {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.e[e] = stitch_out_quant<TD>(cur[0][e], f16, quant);
+    }
+    __device__ __forceinline__ void store(const StitchArgs& a, int X0, int Y, const Row& o) const { stitch_store((TD*)a.out + at(a, X0, Y), o); }
+    __device__ __forceinline__ void pixel(const StitchArgs& a, int X, int Y, int) const
+    {
+        ((TD*)a.out)[at(a, X, Y)] = stitch_out_quant<TD>(stitch_pixel(a, X, Y, blockIdx.z), f16, quant);
+    }
+};
+
+template <typename TD, int R>
+__global__ __launch_bounds__(256) void stitch_planes_kernel(StitchArgs a, float quant, int f16)
+{
+    stitch_fold<R>(a, PlaneEdge<TD>{quant, f16 != 0});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -595,6 +628,24 @@ bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipSt
 {
     const int f16 = canvas_dtype == MOE_F16;
     return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s) : launch_stitch_out_t<uint16_t>(a, quant, f16, s);
+}
+
+template <typename TD>
+static void launch_stitch_planes_t(const StitchArgs& a, float quant, int f16, hipStream_t s)
+{
+    // rows per thread: the sample edge's four, or one where four leave fewer than launch_stitch_mix_t's 1024 workgroups (a.C planes of them: blockIdx.z) -- the
+    // chroma planes of a small frame
+    const unsigned gx = ((a.out_w + 7) / 8 + 255) / 256;
+    if ((long long)gx * ((a.out_h + 3) / 4) * a.C >= 1024) hipLaunchKernelGGL((stitch_planes_kernel<TD, 4>), dim3(gx, (a.out_h + 3) / 4, a.C), dim3(256), 0, s, a, quant, f16);
+    else hipLaunchKernelGGL((stitch_planes_kernel<TD, 1>), dim3(gx, a.out_h, a.C), dim3(256), 0, s, a, quant, f16);
+}
+
+// a.out: a.C planes of out_h x out_w samples at `depth` bits, uint8 for depth 8, else uint16; the whole canvas (y0 = 0, rows = out_h, row_lo = 0)
+void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s)
+{
+    const int f16 = canvas_dtype == MOE_F16;
+    if (depth == 8) launch_stitch_planes_t<uint8_t>(a, 256.f, f16, s);
+    else launch_stitch_planes_t<uint16_t>(a, (float)(1 << depth), f16, s);
 }
 
 template <typename T, typename TD, int R>

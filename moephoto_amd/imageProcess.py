@@ -10,6 +10,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   RGBFilter, strengthOp, alpha helpers :350-377, 562   -> moe_run_plan_filter (blend with the input and alpha inside the final fold)
   toTorch / toFloat / toOutput         :238-263         -> moe_to_float / moe_to_output kernels
   doCropYuv, toYuv                     (python/video.py:24,219,230 fix the pipe to bgr24 / bgr48le) -> moe_run_plan_yuv / moe_to_yuv: the encoder's 4:2:0 planes
+  fromPlanes, doCropPlanes, toPlanes   (python/video.py:24,219 ask the decoder for bgr24 / bgr48le) -> moe_planes_to_float / moe_run_plan_planes / moe_to_output: chains on
+                                       the decoder's own 4:2:0 planes, Y' as a (1, H, W) image and Cb / Cr as a (2, H / 2, W / 2) image (pixfmt.toPlanes / fromPlanes)
   readFile / writeFile                 :265-302         (PIL, host)
 
 There is no CPU path: models must be moephoto_amd.models.EngineModule instances on a HIP device.
@@ -269,10 +271,23 @@ def _yuvOut(who, fmt, w, h, out, device):
     return out
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None):
+def _planesOut(who, depth, C, h, w, out, device):
+    """The flat uint8 device tensor C planes of h x w samples at `depth` bits are written into (a frame, or a view into one: the Y plane, the two chroma planes)."""
+    if depth not in pixfmt.FORMATS.values():
+        raise ValueError('{}: depth must be one of {}, got {!r}'.format(who, sorted(pixfmt.FORMATS.values()), depth))
+    n = C * h * w * (1 if depth == 8 else 2)
+    if out is None:
+        return torch.empty((n,), dtype=torch.uint8, device=device)
+    if tuple(out.shape) != (n,) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device or out.data_ptr() % (1 if depth == 8 else 2):
+        raise ValueError('{}: out must be a flat contiguous uint8 tensor of {} bytes ({} planes of {} x {} at {} bits) on {}'.format(who, n, C, w, h, depth, device))
+    return out
+
+
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None):
     """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
     alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold, with yuv = (pixFmt, matrix, order) moe_run_plan_yuv: the
-    encoder's planar frame from the final fold) and its one retry after a MemoryError."""
+    encoder's planar frame from the final fold, with planes = depth moe_run_plan_planes: the image's own planes as samples of that depth) and its one retry after
+    a MemoryError."""
     model = opt.modelCached
     if not isinstance(model, EngineModule):
         raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
@@ -301,6 +316,10 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None):
         if C != 3:
             raise ValueError('{}: a three-plane image expected, got {} planes'.format(who, C))
         out = _yuvOut(who, yuv[0], plan.outW, plan.outH, out, x.device)
+    elif planes is not None:
+        if not 1 <= C <= 4:
+            raise ValueError('{}: an image of 1 to 4 planes expected, got {}'.format(who, C))
+        out = _planesOut(who, planes, C, plan.outH, plan.outW, out, x.device)
     elif bitDepth is None:
         out = xp.new_empty((C, plan.outH, plan.outW))
     elif out is None:
@@ -315,7 +334,10 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None):
         if yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
             _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth, matrix, order,
                                           out.data_ptr(), int(config.tilesPerBatch), stream))
-        elif mix is not None:      # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
+        elif planes is not None:
+            _lib.check(L.moe_run_plan_planes(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(planes),
+                                             out.data_ptr(), int(config.tilesPerBatch), stream))
+        elif mix is not None:     # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
             _lib.check(L.moe_run_plan_filter(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
                                              strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
         elif bitDepth is None:
@@ -355,6 +377,13 @@ def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr'):
     video path's frames) or red.  Half the bytes of the interleaved image.  Returns a flat uint8 device tensor of pixfmt.frameBytes(fmt, outW, outH); out: one to write into."""
     pixfmt.check(fmt, matrix, order)
     return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order))
+
+
+def doCropPlanes(opt, x, depth, out=None):
+    """doCrop(opt, x) quantised plane by plane at `depth` bits (8, 10, 12, 16), as ONE call (moe_run_plan_planes): the final fold rounds each pixel as the canvas of x's
+    dtype would have and writes C = 1 .. 4 planes of outH x outW samples (uint8 for depth 8, else little-endian uint16) -- the Y plane or the two chroma planes of a
+    planar 4:2:0 frame (pixfmt.fromPlanes).  Returns a flat uint8 device tensor of those bytes; out: one to write into, e.g. a view into a frame at a plane's offset."""
+    return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth))
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------
@@ -655,6 +684,59 @@ def toYuv(fmt, matrix='bt709', order='bgr'):
         out = _yuvOut('toYuv', fmt, W, H, out, y.device)
         cur = torch.cuda.current_stream(y.device)
         _lib.check(_lib.lib().moe_to_yuv(y.data_ptr(), _DT[y.dtype], H, W, depth, mat, ordr, out.data_ptr(), y.device.index or 0, cur.cuda_stream))
+        y.record_stream(cur)
+        return out
+    return f
+
+
+def fromPlanes(fmt, w, h, dtype=None):
+    """The source edge of a chain on the decoder's planes (moe_planes_to_float; the definition: pixfmt.toPlanes): f(raw_dev, outY=None, outC=None) takes the planar
+    4:2:0 frame as a flat uint8 device tensor of pixfmt.frameBytes(fmt, w, h) and returns Y (1, h, w) and C (2, h / 2, w / 2) of dtype (default: config.dtype()),
+    code * 2^-depth; outY / outC: tensors of those shapes to write into."""
+    (yh, yw), (ch, cw) = pixfmt.planeShapes(fmt, w, h)
+    depth, n = pixfmt.FORMATS[fmt], pixfmt.frameBytes(fmt, w, h)
+
+    def f(raw_dev, outY=None, outC=None):
+        if raw_dev.device.type != 'cuda':
+            raise _lib.EngineError('fromPlanes: input must live on a HIP device (moephoto_amd has no CPU path)')
+        if tuple(raw_dev.shape) != (n,) or raw_dev.dtype != torch.uint8 or not raw_dev.is_contiguous():
+            raise ValueError('fromPlanes: a flat contiguous uint8 tensor of {} bytes ({} at {} x {}) expected, got {} {}'.format(n, fmt, w, h, raw_dev.dtype, tuple(raw_dev.shape)))
+        dt = dtype if dtype is not None else config.dtype()
+        if dt not in _DT:
+            raise ValueError('fromPlanes: dtype must be torch.float16 or torch.float32, got {}'.format(dt))
+        outs = []
+        for o, shape in ((outY, (1, yh, yw)), (outC, (2, ch, cw))):
+            if o is None:
+                o = torch.empty(shape, dtype=dt, device=raw_dev.device)
+            elif tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous() or o.device != raw_dev.device:
+                raise ValueError('fromPlanes: a contiguous {} tensor of shape {} on {} expected'.format(dt, shape, raw_dev.device))
+            outs.append(o)
+        cur = torch.cuda.current_stream(raw_dev.device)
+        _lib.check(_lib.lib().moe_planes_to_float(raw_dev.data_ptr(), depth, yh, yw, outs[0].data_ptr(), outs[1].data_ptr(), _DT[dt], raw_dev.device.index or 0, cur.cuda_stream))
+        raw_dev.record_stream(cur)
+        return outs[0], outs[1]
+    return f
+
+
+def toPlanes(depth):
+    """The unfused form of doCropPlanes (moe_to_output on the dense planes: H = C * h, W = w, C = 1, bits = depth): f(y, out=None) quantises a (C, h, w) fp16 / fp32 device
+    image plane by plane into a flat uint8 device tensor of C * h * w samples (uint8 for depth 8, else uint16); out as doCropPlanes'."""
+    if depth not in pixfmt.FORMATS.values():
+        raise ValueError('toPlanes: depth must be one of {}, got {!r}'.format(sorted(pixfmt.FORMATS.values()), depth))
+
+    def f(y, out=None):
+        if y.device.type != 'cuda':
+            raise _lib.EngineError('toPlanes: input must live on a HIP device (moephoto_amd has no CPU path)')
+        if y.dim() != 3:
+            raise ValueError('toPlanes expects a (C,H,W) image, got {}'.format(tuple(y.shape)))
+        if y.dtype not in _DT:
+            y = y.float()
+        y = y.contiguous()
+        C, H, W = y.shape
+        out = _planesOut('toPlanes', depth, C, H, W, out, y.device)
+        cur = torch.cuda.current_stream(y.device)
+        _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], C * H, W, 1, int(depth), out.data_ptr(), _lib.U8 if depth == 8 else _lib.U16,
+                                            y.device.index or 0, cur.cuda_stream))
         y.record_stream(cur)
         return out
     return f

@@ -1,4 +1,5 @@
-"""The encoder's planar Y'CbCr 4:2:0 frames: the definition the device kernels (stitch_yuv_kernel, to_output_yuv_kernel) are held to, in numpy.
+"""The encoder's planar Y'CbCr 4:2:0 frames: the definition the device kernels (stitch_yuv_kernel, to_output_yuv_kernel) are held to, in numpy.  (Below it, the
+definition of chains that run on such planes as they come from the decoder, with no conversion at all: planeShapes, toPlanes, fromPlanes.)
 
 The reference fixes the pipe's pixel format to bgr24 / bgr48le (python/video.py:24,219,230) and leaves the conversion to the encoder's side; here the last pass over a
 frame can write the encoder's own planes.  This module is the written specification and the comparator of the tests; it is on no hot path.
@@ -59,6 +60,63 @@ def planeOffsets(fmt, w, h):
 
 def frameBytes(fmt, w, h):
     return planeOffsets(fmt, w, h)[3]
+
+
+# ---- chains on the decoder's own planes ----------------------------------------------------------------------------------------------------
+# None of the SR / DN nets convolves planes jointly (planes are the batch), so a chain can run on a 4:2:0 source as it is: Y' as a one-plane image at full size, Cb and
+# Cr as a two-plane image at half size -- half the plane-pixels of the bgr48le pipe, and no colour matrix at either end.  The definition the device kernels
+# (to_float_planes_kernel, stitch_planes_kernel, to_output_kernel) are held to:
+#
+#     toPlanes     value = code * 2^-D for every depth D -- 8 bits is / 256, NOT the RGB path's / 255: a depth change is then an exact shift and neutral chroma
+#                  (128 << (D - 8)) is 0.5 at every depth.  uint16 codes are taken as they are (high bits are not masked).  Rounded to dtype: fp32 is exact, fp16
+#                  rounds to nearest even.
+#     fromPlanes   per sample moe_to_output's quantiser with bits = D': fp32(v) * 2^D', clamped to [0, 2^D' - 1], truncated, NaN = 0.
+#
+# Limited range is preserved, not expanded: the net sees code / 2^D.
+def planeShapes(fmt, w, h):
+    """((h, w), (h // 2, w // 2)): the Y plane and each chroma plane of a frame; ValueError for an unknown format or a width / height that is odd or below 2."""
+    if fmt not in FORMATS:
+        raise ValueError('pixFmt "{}" is not supported ({})'.format(fmt, ', '.join(FORMATS)))
+    w, h = int(w), int(h)
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise ValueError('a {} frame needs an even width and height of 2 at least, got {} x {}'.format(fmt, w, h))
+    return (h, w), (h // 2, w // 2)
+
+
+def toPlanes(frame_bytes, fmt, w, h, dtype=np.float32):
+    """The frame's bytes -> Y of shape (1, h, w) and C of shape (2, h / 2, w / 2) (Cb, then Cr), code * 2^-D rounded to dtype (float32 or float16)."""
+    (yh, yw), (ch, cw) = planeShapes(fmt, w, h)
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError('toPlanes: dtype must be float32 or float16, got {}'.format(dtype))
+    D = FORMATS[fmt]
+    _, cb, _, end = planeOffsets(fmt, w, h)
+    if len(frame_bytes) != end:
+        raise ValueError('toPlanes: a {} frame of {} x {} is {} bytes, got {}'.format(fmt, w, h, end, len(frame_bytes)))
+    codes = np.frombuffer(frame_bytes, np.uint8 if D == 8 else np.dtype('<u2'))
+    v = (codes.astype(np.float32) * np.float32(2.0 ** -D)).astype(dtype)          # (the product is exact in fp32: 16 bits times a power of two)
+    return v[:yh * yw].reshape(1, yh, yw), v[yh * yw:].reshape(2, ch, cw)
+
+
+def fromPlanes(Y, C, fmt):
+    """Y (1, h, w) [or (h, w)] and C (2, h / 2, w / 2) -> the frame's bytes at fmt's depth, laid out as planeOffsets says."""
+    Y, C = np.asarray(Y), np.asarray(C)
+    if Y.ndim == 2:
+        Y = Y[None]
+    if Y.ndim != 3 or Y.shape[0] != 1 or C.ndim != 3 or C.shape[0] != 2:
+        raise ValueError('fromPlanes: Y of shape (1, h, w) and C of shape (2, h / 2, w / 2) expected, got {} and {}'.format(Y.shape, C.shape))
+    (_, _), chroma = planeShapes(fmt, Y.shape[2], Y.shape[1])
+    if tuple(C.shape[1:]) != chroma:
+        raise ValueError('fromPlanes: chroma planes of {} expected for a Y plane of {}, got {}'.format(chroma, Y.shape[1:], C.shape[1:]))
+    D = FORMATS[fmt]
+    q = np.float32(1 << D)
+
+    def quantise(p):
+        with np.errstate(invalid='ignore', over='ignore'):
+            v = p.astype(np.float32) * q
+            v = np.fmin(np.fmax(v, np.float32(0)), q - np.float32(1))          # (fmaxf / fminf: a NaN gives way to the bound, so NaN = 0)
+        return v.astype(np.int64).astype(np.uint8 if D == 8 else np.dtype('<u2'))
+    return quantise(Y).tobytes() + quantise(C).tobytes()
 
 
 def fromSamples16(hwc, fmt, matrix='bt709', order='bgr'):

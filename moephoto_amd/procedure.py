@@ -13,6 +13,9 @@ steps.  Ops other than file / buffer / DN / SR / resize / output belong to other
 
 `genFrameStream(steps, width, height, depth)` builds the same chain for a video source as a ring of `depth` frames in flight -- upload, compute and download on
 three queues, the last fold writing the encoder's samples itself (imageProcess.doCropOut) -- and `runFramesStreamed` is `runFrames` over it.
+
+With {'op': 'buffer', 'pixFmt': 'yuv420p' | 'yuv420p10le' | 'yuv420p12le' | 'yuv420p16le'} as the source step both builders take the decoder's planar Y'CbCr 4:2:0
+frames as they are and run the chain on Y' and on Cb / Cr as two images.
 """
 import math
 import time
@@ -20,7 +23,8 @@ from functools import reduce
 
 from . import _lib, pixfmt, runDN, runSR
 from .config import config
-from .imageProcess import RGBFilter, apply, doCropOut, doCropYuv, filterOut, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toTorch, toYuv, writeFile, _DT, _outStorage
+from .imageProcess import (RGBFilter, apply, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
+                           toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -43,6 +47,90 @@ def _outputFormat(steps):
     return None
 
 
+# ---- chains on the decoder's own planes -----------------------------------------------------------------------------------------------------
+# {'op': 'buffer', 'pixFmt': 'yuv420p10le'} as the source step: a frame is the decoder's planar Y'CbCr 4:2:0 frame (pixfmt.frameBytes bytes), the chain runs on Y' as a
+# (1, h, w) image and then on Cb / Cr as a (2, h / 2, w / 2) image -- every step treats each as it treats any (C, H, W) image, plans cached per shape on the step's
+# Option -- and the frame returned is planar 4:2:0 again, at the source's format or at the one an {'op': 'output', 'pixFmt': ..} step names.  No colour conversion
+# takes place anywhere.
+def _planeFormats(steps, width=None, height=None):
+    """(source pixFmt, output pixFmt) of a step list whose source is planar, or None for every other list.  Everything such a chain refuses is refused here, as a
+    ValueError before any model is loaded: an unknown format, a resize step, matrix / order on the output step (there is no conversion they could steer), an odd size."""
+    if not steps or steps[0].get('op') != 'buffer' or steps[0].get('pixFmt') is None:
+        return None
+    src = dst = steps[0]['pixFmt']
+    if src not in pixfmt.FORMATS:
+        raise ValueError('buffer: pixFmt "{}" is not supported ({})'.format(src, ', '.join(pixfmt.FORMATS)))
+    for s in steps[1:]:
+        if s.get('op') == 'resize':
+            raise ValueError('a chain on {} planes cannot hold a resize step (chroma would need its own size)'.format(src))
+        if s.get('op') == 'output':
+            if 'matrix' in s or 'order' in s:
+                raise ValueError("output: 'matrix' / 'order' do not apply to a chain on {} planes: no colour conversion takes place".format(src))
+            if s.get('pixFmt') is not None:
+                dst = s['pixFmt']
+                if dst not in pixfmt.FORMATS:
+                    raise ValueError('output: pixFmt "{}" is not supported ({})'.format(dst, ', '.join(pixfmt.FORMATS)))
+    if width is not None:
+        pixfmt.planeShapes(src, width, height)
+    return src, dst
+
+
+def _planeChain(steps, fuse):
+    """The compute steps of a planar chain -> (funcs, nodes, scale, last): funcs map a (C, H, W) image to the next; with fuse, a last step whose final fold can write
+    the samples itself (an SR without ensemble, a DN of strength 1) is left out of funcs and returned as last = (Option, its prepare)."""
+    work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
+    for opt in work:
+        if opt['op'] not in stepOpts:
+            raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(opt['op']))
+    funcs, nodes, scale, last = [], [], 1, None
+    for k, opt in enumerate(work):
+        op, so = opt['op'], stepOpts[opt['op']]
+        convertValues(int, opt, so.get('toInt', []))
+        convertValues(float, opt, so.get('toFloat', []))
+        o = so['getOpt'].getOpt(opt)
+        if o is None:
+            raise ValueError('unknown model for step {}'.format(opt))
+        opt['opt'] = o
+        final = fuse and k == len(work) - 1
+        if op == 'SR':
+            if not opt['scale'] > 1:
+                raise TypeError('Invalid scale setting for SR.')
+            if final and o.ensemble == 0:
+                last = (o, identity)
+            else:
+                funcs.append(runSR.sr(o))
+            scale *= opt['scale']
+        elif final and o.strength == 1:
+            last = (o, o.prepare)
+        else:
+            funcs.append(RGBFilter(o))
+        nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
+    return funcs, nodes, scale, last
+
+
+def _genProcessPlanes(steps, fmts):
+    import numpy as np
+    import torch
+    src, dst = fmts
+    funcs, nodes, scale, _ = _planeChain(steps, False)
+    quantise = toPlanes(pixfmt.FORMATS[dst])
+
+    def run(frame):
+        raw, height, width = frame
+        pixfmt.planeShapes(src, width, height)
+        if len(raw) != pixfmt.frameBytes(src, width, height):
+            raise ValueError('short frame: {} of {} bytes'.format(len(raw), pixfmt.frameBytes(src, width, height)))
+        dev = torch.device(config.device())
+        y, c = fromPlanes(src, width, height, config.dtype())(torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev))
+        w, h = width * scale, height * scale
+        cb = pixfmt.planeOffsets(dst, w, h)[1]
+        out = torch.empty((pixfmt.frameBytes(dst, w, h),), dtype=torch.uint8, device=dev)
+        quantise(reduce(apply, funcs, y), out[:cb])
+        quantise(reduce(apply, funcs, c), out[cb:])
+        return out.cpu().numpy().tobytes()
+    return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
+
+
 class Context(object):
     imageMode = 'RGB'
     palette = None
@@ -50,6 +138,9 @@ class Context(object):
 
 def genProcess(steps, bitDepth=8, outFile=None):
     steps = [dict(s) for s in steps]
+    planar = _planeFormats(steps)
+    if planar:          # the decoder's own Y'CbCr 4:2:0 planes in, planar frames out
+        return _genProcessPlanes(steps, planar)
     ctx = Context()
     funcs, nodes = [], []
     has_file = bool(steps) and steps[0]['op'] == 'file'
@@ -101,11 +192,12 @@ def genProcess(steps, bitDepth=8, outFile=None):
     return (lambda im: reduce(apply, funcs, im)), nodes
 
 
-def runFrames(process, read, write, width, height, bitDepth=16, start=0, stop=-1):
+def runFrames(process, read, write, width, height, bitDepth=16, start=0, stop=-1, frameBytes=None):
     """The per-frame loop of SR_vid (python/video.py:349-360) without the ffmpeg plumbing: `read(nbytes)` yields raw frames of
-    width*height*3 samples, every frame from `start` on goes through `process` (a genProcess 'buffer' pipeline) and each
-    returned buffer is handed to `write`.  Returns the number of frames written."""
-    frameBytes = width * height * 3 * (1 if bitDepth <= 8 else 2)
+    width*height*3 samples (or of frameBytes bytes: a planar source, pixfmt.frameBytes), every frame from `start` on goes through `process` (a genProcess 'buffer'
+    pipeline) and each returned buffer is handed to `write`.  Returns the number of frames written."""
+    if frameBytes is None:
+        frameBytes = width * height * 3 * (1 if bitDepth <= 8 else 2)
     i = n = 0
     while stop < 0 or i <= stop:
         raw = read(frameBytes)
@@ -139,11 +231,14 @@ def _checkRing(depth, bitDepth):
 
 
 class FrameStream(object):
-    def __init__(self, backend, width, height, bitDepth, depth=2, nodes=()):
+    def __init__(self, backend, width, height, bitDepth, depth=2, nodes=(), frameBytes=None):
         _checkRing(depth, bitDepth)
         self.backend, self.depth, self.nodes = backend, depth, list(nodes)
         self.width, self.height, self.bitDepth = int(width), int(height), bitDepth
-        self.frameBytes = self.width * self.height * 3 * (1 if bitDepth <= 8 else 2)
+        if frameBytes is not None and (not isinstance(frameBytes, int) or isinstance(frameBytes, bool) or frameBytes < 1):
+            raise ValueError('frame stream: frameBytes must be a positive int, got {!r}'.format(frameBytes))
+        # (frameBytes: a source that is not width x height x 3 interleaved samples -- a planar 4:2:0 frame)
+        self.frameBytes = frameBytes if frameBytes is not None else self.width * self.height * 3 * (1 if bitDepth <= 8 else 2)
         self.events = [dict(uploaded=backend.event(), computed=backend.event(), downloaded=backend.event()) for _ in range(depth)]
         self.pushed = self.returned = 0       # frames enqueued / handed back; frame k lives in slot k % depth
         self.closed = self._released = False
@@ -218,15 +313,20 @@ class _DeviceBackend(object):
         self.slots = []
         oshape, o_dt = ((outHW[0], outHW[1], 3), out_dt) if outBytes is None else ((int(outBytes),), torch.uint8)      # (outBytes: a planar frame, flat)
         for _ in range(depth):
-            s = dict(pin_in=torch.empty((self.H, self.W, 3), dtype=out_dt, pin_memory=True), raw=torch.empty((self.H, self.W, 3), dtype=out_dt, device=self.dev),
-                     x=torch.empty((3, self.H, self.W), dtype=config.dtype(), device=self.dev),
-                     out=torch.empty(oshape, dtype=o_dt, device=self.dev), pin_out=torch.empty(oshape, dtype=o_dt, pin_memory=True))
+            s = self._slot(out_dt)
+            s.update(out=torch.empty(oshape, dtype=o_dt, device=self.dev), pin_out=torch.empty(oshape, dtype=o_dt, pin_memory=True))
             s['in_bytes'] = s['pin_in'].numpy().view('uint8').reshape(-1)
             s['out_np'] = s['pin_out'].numpy()
             if timing:
                 s.update(t_up=self.event(), t_comp=self.event(), t_down=self.event())
             self.slots.append(s)
         self.stats = dict(frames=0, memcpy_ms=0.0, h2d_ms=0.0, compute_ms=0.0, d2h_ms=0.0, tobytes_ms=0.0)
+
+    def _slot(self, in_dt):
+        """A slot's input side: the pinned and the device copy of the raw frame, and the image(s) the chain starts from."""
+        torch = self.torch
+        return dict(pin_in=torch.empty((self.H, self.W, 3), dtype=in_dt, pin_memory=True), raw=torch.empty((self.H, self.W, 3), dtype=in_dt, device=self.dev),
+                    x=torch.empty((3, self.H, self.W), dtype=config.dtype(), device=self.dev))
 
     def event(self):
         return self.torch.cuda.Event(enable_timing=self.timing)
@@ -289,6 +389,51 @@ class _DeviceBackend(object):
         self.slots = []
 
 
+class _PlanesBackend(_DeviceBackend):
+    """The same three queues for a chain on the decoder's planes: a slot's input is the flat planar frame (pinned and on the device), its images are Y (1, H, W) and
+    C (2, H / 2, W / 2), its output the flat planar frame of outBytes.  compute = moe_planes_to_float, the chain on Y and then on C, and edge(y, c, out)."""
+
+    def __init__(self, funcs, edge, fmt, width, height, depth, timing, outBytes):
+        self.convert, self.inBytes = fromPlanes(fmt, width, height, config.dtype()), pixfmt.frameBytes(fmt, width, height)
+        super().__init__(funcs, edge, 8 if pixfmt.FORMATS[fmt] == 8 else 16, width, height, None, depth, timing, outBytes)
+
+    def _slot(self, in_dt):
+        torch = self.torch
+        return dict(pin_in=torch.empty((self.inBytes,), dtype=torch.uint8, pin_memory=True), raw=torch.empty((self.inBytes,), dtype=torch.uint8, device=self.dev),
+                    y=torch.empty((1, self.H, self.W), dtype=config.dtype(), device=self.dev),
+                    c=torch.empty((2, self.H // 2, self.W // 2), dtype=config.dtype(), device=self.dev))
+
+    def compute(self, slot, wait, record):
+        s = self.slots[slot]
+
+        def work(stream):
+            y, c = self.convert(s['raw'], s['y'], s['c'])
+            self.edge(reduce(apply, self.funcs, y), reduce(apply, self.funcs, c), s['out'])
+        self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
+
+
+def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing):
+    src, dst = fmts
+    bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
+    _checkRing(depth, bitDepth)          # (before any model is loaded)
+    funcs, nodes, scale, last = _planeChain(steps, True)
+    w, h = int(width) * scale, int(height) * scale
+    D, cb = pixfmt.FORMATS[dst], pixfmt.planeOffsets(dst, w, h)[1]
+    if last:          # the last step's two folds write straight into the slot's frame, at the Y and at the Cb offset: no canvas exists
+        o, prepare = last
+        into, edgeName = (lambda x, out: doCropPlanes(o, prepare(x), D, out)), 'crop'
+    else:
+        into, edgeName = toPlanes(D), 'quantise'
+
+    def edge(y, c, out):
+        into(y, out[:cb])
+        into(c, out[cb:])
+    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h))
+    stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
+    stream.edge = edgeName
+    return stream
+
+
 def _quantiseInto(bitDepth):
     """The unfused output edge: moe_to_output straight on a step's (C, H, W) result.  toFloat's fp32 copy of an fp16 result is skipped: fp16 -> fp32 is exact and the
     kernel widens each value itself, so the samples are toOutput(toFloat(y))'s."""
@@ -315,10 +460,16 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
     (doCropOut: the canvas never exists); 'filter' -- a DN of any other finite strength does the same with the blend inside the fold (filterOut, under
     config.filterOnDevice); 'quantise' -- after a resize, an ensemble or otherwise the step's result is quantised in place.  Same bytes as genProcess + runFrames.
     With an {'op': 'output', 'pixFmt': ..} step the finished frames are the encoder's planar Y'CbCr 4:2:0 frames (moephoto_amd/pixfmt.py): the 'crop' edge folds its
-    tiles straight into them (doCropYuv); every other chain ends in toYuv on the step's result (a 'filter' chain blends in RGBFilter first)."""
+    tiles straight into them (doCropYuv); every other chain ends in toYuv on the step's result (a 'filter' chain blends in RGBFilter first).
+    With steps[0] = {'op': 'buffer', 'pixFmt': ..} the frames pushed are the decoder's planar Y'CbCr 4:2:0 frames (pixfmt.frameBytes bytes, even width and height), the
+    chain runs on Y' and on Cb / Cr as two images and the finished frames are planar again, at the source's format or the output step's: 'crop' -- two doCropPlanes
+    folds write straight into the frame -- or 'quantise' (toPlanes); no resize step, no matrix / order (ValueError before a model is loaded)."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
+    planar = _planeFormats(steps, width, height)
+    if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
+        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing)
     bitDepth = int(steps[0].get('bitDepth', 16))
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
