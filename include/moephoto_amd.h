@@ -178,7 +178,15 @@ int moe_net_set_exact_blocks(moe_net* net, int blocks);
  * have is reported on stderr and ignored); the forward path itself reads no
  * environment.  The reference has no such switches: its forward is torch.nn (python/imageProcess.py:391-395). */
 int moe_net_set_option(moe_net* net, const char* key, const char* value);
-/* keep fp32 copies of named intermediates during forwards (slow; debugging / layer-by-layer parity only) */
+/* keep fp32 copies of named intermediates during forwards (slow; debugging / layer-by-layer parity only).
+ * enable = 0: off.  1 (any other non-zero value): taps, and the forwards leave their fused forms so that every layer has a tensor to tap.
+ * 2: taps and nothing else -- no kernel choice changes, the forward is the production one and its result is bit-identical to enable = 0.  Defined for
+ *    SEDN (MOE_EINVAL for the other architectures); its fused block tail then leaves per block K: bK.rb0, bK.rb2 (fp16 activations), bK.mean (the 256 fp32
+ *    channel means, shape (B, 256, 1, 1)), bK.weff (the per-plane 64 x 64 x 9 weights as the fp16 MFMA A fragments lie in memory, shape (B, 72 * 512, 1, 1):
+ *    fragment tap * 8 + ks * 2 + nblk, lane l, element e = W_eff[cout 32 nblk + l % 32][cin 16 ks + 8 (l / 32) + e][tap]) and blockK.
+ * Where SEDN's forward takes the unfused form (enable = 1; more planes than workgroups; FP16X3) it leaves bK.rb0, bK.rb2, bK.rb4, bK.wtrans (the gated
+ * per-plane 1x1 weights in fragment order, shape (B, 64 * 256, 1, 1): fragment (seg * 4 + ks) * 2 + nblk = W[cout 32 nblk + l % 32][cin 64 seg + 16 ks + 8 (l / 32) + e])
+ * and blockK.  A tapped SEDN forward drops the taps of the forward before it. */
 int moe_net_set_debug(moe_net* net, int enable);
 /* copy a named intermediate of the LAST forward to host as fp32 NCHW (debug / layer-by-layer parity);
  * synchronises the stream.  Returns the element count written (<= capacity) or a negative error. */

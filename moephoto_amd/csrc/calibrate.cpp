@@ -118,10 +118,10 @@ int calibrate_blocks(moe_net& n, double target, hipStream_t s)
     int rc = cs.init();
     if (rc) return rc;
     const int prec0 = n.precision, blocks0 = n.exact_blocks;
-    const bool debug0 = n.debug;
-    n.debug = false;
+    const bool debug0 = n.debug, tap0 = n.tap_only;
+    n.debug = false; n.tap_only = false;
     auto restore = [&](int r) {
-        n.exact_blocks = blocks0; n.debug = debug0;
+        n.exact_blocks = blocks0; n.debug = debug0; n.tap_only = tap0;
         cs.give_back_workspace();
         return r;
     };
@@ -160,12 +160,12 @@ int calibrate_sedn(moe_net& n, double target, hipStream_t s, bool adopt)
     int rc = cs.init();
     if (rc) return rc;
     const int prec0 = n.precision;
-    const bool debug0 = n.debug;
-    n.debug = false;
+    const bool debug0 = n.debug, tap0 = n.tap_only;
+    n.debug = false; n.tap_only = false;
     int have = prec0;                  // the arithmetic of the weights on the device
     auto leave = [&](int r, int prec) {
         if (have != prec) { const int rc2 = build_device_weights(n, prec); if (!r) r = rc2; }
-        n.precision = prec; n.debug = debug0;
+        n.precision = prec; n.debug = debug0; n.tap_only = tap0;
         cs.give_back_workspace();
         return r;
     };

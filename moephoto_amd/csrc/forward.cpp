@@ -699,7 +699,10 @@ int64_t moe_net_max_tile_pixels(const moe_net* n)
 int moe_net_set_debug(moe_net* n, int enable)
 {
     if (!n) return fail(MOE_EINVAL, "moe_net_set_debug: NULL net");
-    n->debug = enable != 0;
+    if (enable == 2 && n->arch != MOE_ARCH_SEDN)
+        return fail(MOE_EINVAL, "moe_net_set_debug: value 2 (taps of the production forward) is defined for SEDN only; 1 taps this architecture's unfused forward");
+    n->debug = enable != 0 && enable != 2;
+    n->tap_only = enable == 2;
     return MOE_OK;
 }
 

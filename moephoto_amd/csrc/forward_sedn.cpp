@@ -15,6 +15,7 @@ int moe::forward_sedn(const moe_net& n, Fwd& f)
     const size_t wel = (size_t)Lt.nchunks * Lt.nfrag() * 512;
     half_t* wplane = (half_t*)f.ar.take(f.direct ? (size_t)B * 64 * 256 * 4 : (size_t)B * wel * 2);
     half_t* wplane_lo = f.x3 ? (half_t*)f.ar.take((size_t)B * wel * 2) : nullptr;
+    f.drop_taps();      // (the two forms leave different taps: none of another forward's stays behind to be read as this one's)
     f.stem(A);
     f.tap("stem", A, h, w, 64, 64);
     // fused block tail (see sedn_fuse in misc_kernels.hip): single-pass precision, fast kernel, planes fit the per-XCD split -- one 3x3 64->64 conv with per-plane
@@ -34,9 +35,11 @@ int moe::forward_sedn(const moe_net& n, Fwd& f)
     for (int b = 0; b < 16; ++b) {
         const std::string k = "b" + std::to_string(b);
         f.conv(k + ".rb0", A, Cc, nullptr, h, w);
+        f.tap(k + ".rb0", Cc, h, w, 64, 64);
         ConvExtra rb2;
         if (sfuse && spool) { rb2.pool = true; rb2.pool_out = xpool; rb2.pool_slabs = pslabs; }      // (the conv writes the first 2 min(G, py) slabs of every plane, all of them: no memset)
         const bool pooled = f.conv(k + ".rb2", Cc, Dd, nullptr, h, w, rb2).pooled;
+        f.tap(k + ".rb2", Dd, h, w, 64, 64);
         if (sfuse) {
             if (!f.dry()) {
                 SednFuseArgs fa{};
@@ -50,6 +53,8 @@ int moe::forward_sedn(const moe_net& n, Fwd& f)
                 fa.w_down = f.small<float>(k + ".down"); fa.w_up = f.small<float>(k + ".up");
                 fa.gate = fgate; fa.weff = weff;
                 launch_sedn_fuse(fa, s);
+                f.tap_f32(k + ".mean", fgate, 256);              // (the fused branch runs with n.debug off: these are moe_net_set_debug's value 2)
+                f.tap_raw16(k + ".weff", weff, 72 * 512);        // the A fragments as they lie in memory: the reader undoes pack_conv's order
                 ConvArgs a{};
                 a.in = Dd.hi; a.out = A.hi; a.res = A.hi; a.wpk = weff; a.plane_w = 1;
                 a.bias = f.small<float>("zero_bias"); a.bias_img = f.small<float>("zero_bias_img");
@@ -58,10 +63,12 @@ int moe::forward_sedn(const moe_net& n, Fwd& f)
                 a.px = (w + kTileW - 1) / kTileW; a.py = tf.py; a.G = tf.G;
                 a.slope = tf.slope; a.scale = tf.scale;
                 if (!(s64 ? launch_conv64_s(a, f.groups, s) : launch_conv3x3_sp(a, s))) return fail(MOE_EINVAL, "internal error: SEDN fused block tail: %s rejected the layer", s64 ? "conv64_s" : "conv3x3_sp");
+                f.tap("block" + std::to_string(b), A, h, w, 64, 64);
             }
             continue;
         }
         f.conv(k + ".rb4", Dd, T, nullptr, h, w);
+        f.tap(k + ".rb4", T, h, w, 256, 256);
         if (!f.dry()) {
             launch_pool_partial(T.hi, T.lo, partial, B, (long long)h * w, 256, nslab, s);
             const ConvLayer& L = n.convs[n.conv_index.at(k + ".trans")];
@@ -79,6 +86,7 @@ int moe::forward_sedn(const moe_net& n, Fwd& f)
                 a.trans_out = wplane; a.trans_out_lo = wplane_lo;
             }
             launch_sedn_se(a, s);
+            if (!f.direct) f.tap_raw16(k + ".wtrans", wplane, (long long)wel);      // the per-plane trans weights in fragment order (fp16 parts)
         }
         ConvExtra trans;
         trans.plane_w = wplane; trans.plane_w_lo = wplane_lo;

@@ -213,7 +213,9 @@ struct moe_net {
     std::map<std::string, float> scalars;
     int max_groups = 256;        // persistent workgroups per launch (one per CU, or option max_groups): set at finalize
     std::vector<std::string> prof_keys;          // comma-separated substrings of moe_net_set_profile
-    bool debug = false;          // debug taps wanted (moe_net_set_debug)
+    bool debug = false;          // debug taps wanted (moe_net_set_debug, value 1): the forwards also leave their fused forms, so that every layer has a tensor to tap
+    bool tap_only = false;       // moe_net_set_debug, value 2 (SEDN): taps wanted and NOTHING else changes -- no kernel choice reads this, the forward is the production one
+    bool tapping() const { return debug || tap_only; }
     // what forwards write: the stream set of ordinary forwards, the two sets of forwards that run ahead of the caller's stream, the records
     moe::StreamSet set;
     moe::PipeSet pipe[2];
@@ -335,7 +337,7 @@ struct Fwd {
     // (a low part of exactly half an ulp puts the sum midway between two fp16 values), so a pair also leaves tap `name`.hi: its fp16 part alone
     void tap(const std::string& name, const Act& a, int H, int W, int cs, int C)
     {
-        if (!n.debug || dry()) return;
+        if (!n.tapping() || dry()) return;
         tap_part(name, a.hi, a.lo, H, W, cs, C);
         if (a.lo) tap_part(name + ".hi", a.hi, nullptr, H, W, cs, C);
         else {      // (no stale fp16 part of an earlier forward that kept a pair here)
@@ -351,6 +353,27 @@ struct Fwd {
         if (hipMalloc((void**)&t.dev, nel * 4) != hipSuccess) return;
         t.shape[0] = B; t.shape[1] = C; t.shape[2] = H; t.shape[3] = W;
         launch_nhwc_to_nchw_f32(hi, lo, t.dev, B, H, W, cs, C, s);
+    }
+    void drop_taps()
+    {
+        if (!n.tapping() || dry()) return;
+        for (auto& t : rt->taps) if (t.second.dev) (void)hipFree(t.second.dev);      // (hipFree waits for the device: no copy of an earlier forward is still writing)
+        rt->taps.clear();
+    }
+    // ... a buffer as it lies in memory: per plane `per` fp16 values widened to fp32 (fragment-ordered weights), or `per` fp32 values copied on the launch stream; shape (B, per, 1, 1)
+    void tap_raw16(const std::string& name, const half_t* p, long long per)
+    {
+        if (!n.tapping() || dry()) return;
+        tap_part(name, p, nullptr, 1, 1, (int)per, (int)per);
+    }
+    void tap_f32(const std::string& name, const float* p, long long per)
+    {
+        if (!n.tapping() || dry()) return;
+        auto& t = rt->taps[name];
+        if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
+        if (hipMalloc((void**)&t.dev, (size_t)B * per * 4) != hipSuccess) return;
+        t.shape[0] = B; t.shape[1] = per; t.shape[2] = 1; t.shape[3] = 1;
+        if (hipMemcpyAsync(t.dev, p, (size_t)B * per * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t.dev); t.dev = nullptr; }
     }
 
     // MIXED: which fused-tail launches also split the activation operand.  The R branch (trunk -> upsampler -> tail) carries the larger

@@ -289,7 +289,9 @@ class EngineModule(object):
 
     # ---- debugging -----------------------------------------------------------------------------------
     def set_debug(self, flag=True):
-        _lib.check(_lib.lib().moe_net_set_debug(self._h, 1 if flag else 0))
+        """False / 0: off.  True / 1: keep fp32 copies of named intermediates; the forwards leave their fused forms so that every layer has one.  2 (SEDN): keep the copies
+        and change nothing else -- the forward is the production one, its fused block tail included (moe_net_set_debug)."""
+        _lib.check(_lib.lib().moe_net_set_debug(self._h, 2 if flag == 2 else 1 if flag else 0))
         return self
 
     def debug_tap(self, name):

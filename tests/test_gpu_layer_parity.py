@@ -10,7 +10,7 @@ that noise over 1e5 samples differ by well under 2x, and the other 2x is left fo
 unmeasured, and a complete run writes every observed ratio to profiles/layer_parity/summary.md.  tests/test_layer_models_cpu.py shows, on the reference
 alone, that these bounds catch a residual that drops the stream's low part, a lost border column of conv_1 and an R tail that reads fp16 activations.
 
-Not bounded here: SEDN and lite (lite is held at 2e-5 end to end), the untapped interior of the fp8 low-part chain (lo8), fp16 I/O edges."""
+Not bounded here: lite (held at 2e-5 end to end; SEDN has tests/test_gpu_sedn_layers.py), the untapped interior of the fp8 low-part chain (lo8), fp16 I/O edges."""
 import os
 
 import pytest

@@ -1,0 +1,211 @@
+"""tests/emu_sedn.py on the CPU: the per-layer float64 models behind tests/test_gpu_sedn_layers.py are the net they claim to be, the bounds they yield resolve the index
+slips they are there to find, the end-to-end tolerance does not, and the 'planes' input does make the per-plane gates differ."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import emu_sedn as es
+import golden_defs as gd
+from moephoto_amd.weights import load_state_dict_file
+
+SMALLEST, LARGEST = (3, 8, 16), (2, 40, 264)      # of the shapes tests/test_gpu_sedn_layers.py runs
+GPU_SHAPES = [(3, 8, 16), (3, 9, 35), (2, 40, 264), (5, 88, 40), (2, 131, 61), (2, 96, 40), (12, 16, 64)]
+KINDS = ('natural', 'noise', 'planes')
+TOL = 1e-3
+shape_id = lambda s: 'x'.join(map(str, s))
+
+_net, _chains = [], {}
+
+
+def net():
+    if not _net:
+        _net.append(es.Net(gd.state_dict_for('l25', load_state_dict_file)))
+    return _net[0]
+
+
+def image(kind, seed, shape):
+    if kind == 'noise':
+        return gd.noise_image(seed, shape)[:, None]
+    x = gd.natural_image(seed, shape)
+    return (es.planes_image(x) if kind == 'planes' else x)[:, None]
+
+
+def rounded_chain(shape, kind, bug=None):
+    """the fp32 chain of the rounded models on image(kind, es.SEED, shape), computed once per (shape, kind, bug) and left unchanged"""
+    if (shape, kind, bug) not in _chains:
+        with torch.no_grad():
+            _chains[(shape, kind, bug)] = es.chain(net(), image(kind, es.SEED, shape), torch.float32, bug=bug)
+    return _chains[(shape, kind, bug)]
+
+
+@pytest.fixture(autouse=True)
+def _threads():
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+
+
+def test_fragment_orders_undo_pack_conv():
+    """unpack_weff / unpack_wtrans against a packing written down from weights.cpp:118-129 (pack_conv's loops), element by element"""
+    rng = np.random.default_rng(0)
+    for taps, nseg, unpack in ((9, 1, es.unpack_weff), (1, 4, es.unpack_wtrans)):
+        cin = 64 * nseg
+        W = rng.standard_normal((2, 64, cin, taps)).astype(np.float32)
+        raw = np.zeros((2, nseg * taps * 8 * 512), np.float32)
+        for f in range(nseg * taps * 8):
+            nblk, ks, st = f & 1, (f >> 1) & 3, f >> 3
+            tap, seg = st % taps, st // taps
+            for l in range(64):
+                for e in range(8):
+                    raw[:, (f * 64 + l) * 8 + e] = W[:, nblk * 32 + (l & 31), seg * 64 + ks * 16 + 8 * (l >> 5) + e, tap]
+        got = unpack(raw[:, :, None, None]).numpy()
+        assert np.array_equal(got.reshape(2, 64, cin, taps), W)
+
+
+def test_path_restatement_reaches_what_the_gpu_cases_are_there_for():
+    """emu_sedn.path (a restatement of common.h:302-312 and forward_sedn.cpp:23-47) on the case table of the GPU test"""
+    P = es.path
+    assert P(3, 8, 16) == dict(form='fused', sums='epilogue', py=1, G=3, pooled_count=2, tail='conv64_s')
+    assert P(3, 9, 35)['tail'] == 'conv3x3_sp<6>' and P(3, 9, 35)['sums'] == 'epilogue'
+    assert P(5, 88, 40)['py'] == 11 and P(5, 88, 40)['G'] == 55 and P(5, 88, 40)['pooled_count'] == 22
+    assert P(2, 131, 61)['py'] == 17 and P(2, 131, 61)['G'] == 34                                                # G a multiple of py
+    assert P(2, 96, 40, groups=8) == dict(form='fused', sums='epilogue', py=12, G=6, pooled_count=12, tail='conv64_s')      # G a divisor of py
+    assert P(2, 131, 61, groups=8)['sums'] == 'xsum'                                                           # 17 rows on 8 groups: G = 1, pooled_groups_ok false
+    assert P(3, 9, 35, pool_fuse=0)['sums'] == 'xsum'
+    assert P(2, 40, 264, s64=0)['tail'] == 'conv3x3_sp<6>' and P(2, 40, 264)['tail'] == 'conv64_s'
+    assert P(12, 16, 64, groups=8)['form'] == 'unfused' and P(3, 9, 35, debug=1)['form'] == 'unfused'
+
+
+def test_chain_with_nothing_rounded_is_the_oracle_and_the_rounded_chain_holds_the_contract():
+    """The chain of exact models -- the FUSED algebra, W_eff = W_t diag(g) W_256 applied as one 3x3 conv -- in float64 against oracle.nets.sedn run in float64 (tensors
+    pass through it unchanged): float64 noise.  The rounded chain (fp32 sums) lies within the 1e-3 contract of the oracle, as the engine does."""
+    from oracle import nets as onets
+    n = net()
+    x = image('natural', 3, (2, 24, 40))
+    sd64 = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)) for k, v in n.sd.items()}
+    with torch.no_grad():
+        want = onets.sedn(sd64, torch.from_numpy(x).double())
+        _, y = es.chain(n, x, torch.float64, exact=True)
+        assert y.dtype == torch.float64
+        d = float((y - want).abs().max())
+        print('exact chain vs the oracle in float64: {:.3e}'.format(d))
+        assert d <= 1e-12 * max(1.0, float(want.abs().max()))
+        _, y16 = es.chain(n, x, torch.float32)
+        d16 = float((y16.double() - want).abs().max())
+        print('rounded chain vs the oracle: {:.3e}'.format(d16))
+        assert d16 <= TOL
+
+
+def _factor(got, m64, m32):
+    """how far `got` lies beyond the bounds: max over the two of distance / bound"""
+    ok, text, f = es.check2(got, m64, *m32)
+    return max(f['dm'] / f['bm'], f['dr'] / f['br']), ok, text
+
+
+@pytest.mark.parametrize('shape', (SMALLEST, LARGEST), ids=shape_id)
+def test_bounds_catch_the_modelled_bugs(shape):
+    """A condition on the reference alone: in every block, at the smallest and the largest shape of the GPU test (both ragged in W) and for every input kind, each modelled
+    bug's output lies outside the bounds the two correct models give from the same taps; the correct shifted-sum algebra in fp32 -- what sedn_fmean does -- lies inside.
+      'corner'    the shifted sums without the corner add-back                            -> `mean`
+      'ragged'    the channel totals include a column beyond W, replicated from W - 1     -> `mean`
+      'gateperm'  the gate applied with channels 8q..8q+3 and 8q+4..8q+7 swapped           -> `weff`
+    The inputs of each layer are the rounded models' own chain.  Also printed: what a relative error of 2e-7 of the gate (__expf) does to W_eff, in fp16 steps."""
+    n = net()
+    worst = {b: float('inf') for b in es.BUGS}
+    expf = 0.0
+    for kind in KINDS:
+        taps, _ = rounded_chain(shape, kind)
+        with torch.no_grad():
+            for k in range(16):
+                m64, m32 = es.mean(n, k, taps, torch.float64), [es.mean(n, k, taps, torch.float32, order=o) for o in (0, 1)]
+                fac, ok, text = _factor(es.mean_shifted(n, k, taps, torch.float32).value, m64, m32)
+                assert ok, (shape, kind, k, 'the correct shifted sums in fp32', text)
+                for bug in ('corner', 'ragged'):
+                    fac, ok, text = _factor(es.mean_shifted(n, k, taps, torch.float64, bug).value, m64, m32)
+                    worst[bug] = min(worst[bug], fac)
+                    assert not ok, (shape, kind, k, bug, text)
+                w64, w32 = es.weff(n, k, taps, torch.float64), [es.weff(n, k, taps, torch.float32, order=o) for o in es.GATE_ORDERS]
+                fac, ok, text = _factor(es.weff(n, k, taps, torch.float64, 'gateperm').value, w64, w32)
+                worst['gateperm'] = min(worst['gateperm'], fac)
+                assert not ok, (shape, kind, k, 'gateperm', text)
+                # |dW_eff| <= 2e-7 sum_m |W_t[co][m] g[m] W_256[m][k]| for a gate wrong by 2e-7 of itself
+                g = es.gate(n, k, taps['b%d.mean' % k].reshape(-1, 256), torch.float64)
+                mag = torch.matmul(n.blk(k, 'trans.0', torch.float64).reshape(64, 256).abs()[None] * g[:, None, :], n.blk(k, 'rblock.4', torch.float64).reshape(256, 576).abs())
+                expf = max(expf, 2e-7 * float(mag.max()) / w64.floor)
+    for bug in es.BUGS:
+        print('{} {}: beyond its bound by at least {:.1f} x (the smallest factor over 16 blocks and {} input kinds)'.format(shape_id(shape), bug, worst[bug], len(KINDS)))
+    print('{}: a gate wrong by 2e-7 of itself moves W_eff by at most {:.1e} of one fp16 step of its largest value'.format(shape_id(shape), expf))
+    assert expf < 0.05
+
+
+@pytest.mark.parametrize('shape', (SMALLEST, LARGEST), ids=shape_id)
+def test_the_end_to_end_tolerance_cannot_see_them(shape):
+    """The premise of the per-layer tests, checked: y of the chain with a bug in EVERY block against the oracle, with the 1e-3 every end-to-end SEDN test allows.  For the bugs
+    NOT named in SEEN_END_TO_END the distance stays within 1e-3 (asserted); for those named there it does not (asserted too, so that the list stays true).  Every value is
+    printed beside the correct chain's."""
+    from oracle import nets as onets
+    n = net()
+    bad = []
+    for kind in KINDS:
+        x = image(kind, es.SEED, shape)
+        with torch.no_grad():
+            want = onets.forward('sedn', n.sd, x)
+            base = float((rounded_chain(shape, kind)[1] - want).abs().max())
+            for bug in es.BUGS:
+                d = float((rounded_chain(shape, kind, bug)[1] - want).abs().max())
+                seen = bug in SEEN_END_TO_END
+                print('{} {} {}: y {:.3e} from the oracle (the correct chain: {:.3e}){}'.format(shape_id(shape), kind, bug, d, base, ' -- beyond 1e-3' if d > TOL else ''))
+                if (d > TOL) != seen:
+                    bad.append((kind, bug, d))
+    assert not bad, bad
+
+
+# The premise holds for the two slips of the pooled sums (y moves by less than the fp16 chain's own 2-7e-4).  It does NOT hold for the gate's k-pair swap: applied in all
+# sixteen blocks it moves y by 0.8e-2 to 2.5e-2 at both shapes and on every input kind, and every end-to-end SEDN test would see that one.
+SEEN_END_TO_END = ('gateperm',)
+
+
+@pytest.mark.parametrize('shape', GPU_SHAPES, ids=shape_id)
+def test_planes_input_separates_the_gates(shape):
+    """On the 'planes' input, in every block, every two planes' gates differ by at least 8 fp16 steps (4e-3: gates lie in [0.25, 1)) in some channel: a kernel that took
+    another plane's weights would move W_eff by many steps.  On the model alone (the rounded fp32 chain)."""
+    n = net()
+    taps, _ = rounded_chain(shape, 'planes')
+    least = float('inf')
+    for k in range(16):
+        g = es.gate(n, k, taps['b%d.mean' % k].reshape(-1, 256), torch.float64)
+        d = (g[:, None, :] - g[None, :, :]).abs().amax(dim=2) + torch.eye(g.shape[0]) * 1e9
+        least = min(least, float(d.min()))
+        assert float(d.min()) >= 4e-3, (shape, k, float(d.min()))
+    print('{}: the closest two planes differ by {:.2e} in their most different gate'.format(shape_id(shape), least))
+
+
+def test_debug_value_2_is_defined_for_sedn_only():
+    """moe_net_set_debug: 2 = taps of the production forward, SEDN; the other architectures refuse it with a message and keep 0 / 1"""
+    from moephoto_amd import _lib, models
+    for ctor in (models.Net2x, models.NetDN, lambda: models.Net(2)):
+        m = ctor()
+        with pytest.raises(_lib.EngineError, match='SEDN only'):
+            m.set_debug(2)
+        m.set_debug(True).set_debug(False)
+    models.SEDN().set_debug(2).set_debug(1).set_debug(0)
+
+
+@pytest.mark.parametrize('shape', (SMALLEST, LARGEST), ids=shape_id)
+def test_bounds_catch_a_block_that_takes_another_planes_weights(shape):
+    """What the 'planes' input is for, with the yardstick of the convolutions as the GPU test sizes it (emu_sedn.orders_of: 11 fp32 orders at the smallest shape): in every
+    block the output computed with the NEXT plane's W_eff lies outside the bounds the correct models give -- and by how much."""
+    n = net()
+    taps, _ = rounded_chain(shape, 'planes')
+    least = float('inf')
+    with torch.no_grad():
+        for k in range(16):
+            name = 'block%d' % k
+            m64 = es.block(n, k, taps, torch.float64)
+            m32 = [es.block(n, k, taps, torch.float32, order=o) for o in es.orders_of(name, m64.value.numel())]
+            wrong = dict(taps)
+            wrong['b%d.weff' % k] = torch.roll(taps['b%d.weff' % k], 1, dims=0)
+            fac, ok, text = _factor(es.block(n, k, wrong, torch.float64).value, m64, m32)
+            least = min(least, fac)
+            assert not ok, (shape, k, text)
+    print('{}: another plane\'s weights lie beyond the bound by at least {:.0f} x'.format(shape_id(shape), least))
