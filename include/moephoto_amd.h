@@ -361,6 +361,28 @@ int moe_run_plan_tiles(moe_net* net, const moe_plan* plan, const void* imgs, int
 int64_t moe_plan_pool_elems(const moe_plan* plan, int C);
 int moe_plan_tile_offsets(const moe_plan* plan, int C, int64_t* off);
 
+/* ---- reuse between the frames of a stream ------------------------------------------------------------------
+ * The reference computes every tile of every frame (python/video.py:349-360 -> python/imageProcess.py:157-172).  A tile's result depends on its own input rectangle
+ * alone, so a stream may keep each step's tile pool, run the tiles whose input changed and fold the whole pool as always: the same bytes (DESIGN.md section 14;
+ * moephoto_amd/reuse.py holds the rules, procedure.genFrameStream(reuse=True) the wiring).
+ *
+ * moe_changed_blocks: cur and prev each hold n dense byte matrices of rows x row_bytes, one after the other, on the device; map (device, ceil(rows / block_rows) x
+ * ceil(row_bytes / block_bytes) bytes, row-major, every byte written) gets map[i][j] = 1 iff some byte of block (i, j) -- block_rows x block_bytes, clipped at the
+ * bottom and right edges -- differs between cur and prev in any of the n matrices, else 0.  The same pass copies cur into prev: afterwards prev holds cur's bytes.  Bytes
+ * are compared, so NaN patterns and -0 need no special case.  One launch; 16-byte loads when cur, prev, row_bytes and block_bytes are multiples of 16, single bytes
+ * otherwise.  An interleaved bgr24 / bgr48le frame is one matrix with block_bytes = 16 * 3 * sample size, a planar frame's Y plane one matrix, its Cb and Cr planes
+ * n = 2 matrices folded into one map.  Refused before any device call: a NULL pointer, n, rows, row_bytes or a block size below 1, cur == prev, overlapping cur / prev,
+ * a map of more than 2^31 - 1 cells.  Asynchronous on `stream`. */
+int moe_changed_blocks(const void* cur, void* prev, int n, int rows, int64_t row_bytes, int block_rows, int block_bytes, uint8_t* map, int device, void* stream);
+/* moe_run_plan_ex(.., pool, 0, 1, do_stitch = 0, ..) for the tiles of a mask: tile k is computed iff run[k] != 0 (HOST array of n_tiles bytes) and its C planes go to
+ * pool + moe_plan_tile_offsets(plan, C)[k], the plan's own layout -- every moe_stitch* then takes the pool with tile_off_dev = NULL; nothing else in pool is touched.
+ * An all-ones mask launches exactly what moe_run_plan_ex launches, an all-zero mask nothing.  The call's offset tables do not go through the cache that serves
+ * moe_run_plan_tiles (a new mask per frame would cost it a synchronise, a free, an allocation and a blocking copy per call): they travel through a ring of 32 device
+ * buffers the plan owns, filled with hipMemcpyAsync from pinned memory on `stream`, a buffer taken again only behind the event recorded after the launch sets that
+ * read it.  After the first call on a plan nothing is allocated or freed; the host waits only when it is 32 calls ahead of the device.  Asynchronous on `stream`. */
+int moe_run_plan_subset(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW, const uint8_t* run /* n_tiles, HOST */,
+                        float* pool, int max_tiles_per_batch, void* stream);
+
 /* ---- self-ensemble ------------------------------------------------------------------------------ */
 /* The reference's ensemble (python/imageProcess.py:563-572) with runSR.sr's average (python/runSR.py:26):
  *     v = doCrop(opt, x);  for i < n: v = v + transInv[i](doCrop(opt, trans[i](x)));  v / (n + 1)

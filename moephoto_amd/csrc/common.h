@@ -515,4 +515,6 @@ void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_
 void launch_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, hipStream_t s);
 // max |a - b| over n floats, atomically folded into *out as the bits of a non-negative float (zero it first)
 void launch_maxabsdiff(const float* a, const float* b, long long n, unsigned* out, hipStream_t s);
+// map[i][j] = some byte of block (i, j) differs between cur and prev in any of their n matrices of rows x row_bytes; prev <- cur in the same pass (moe_changed_blocks)
+void launch_changed_blocks(const void* cur, void* prev, int n, int rows, long long row_bytes, int block_rows, int block_bytes, unsigned char* map, hipStream_t s);
 void launch_nhwc_to_nchw_f32(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C, hipStream_t s);

@@ -1510,3 +1510,53 @@ void launch_maxabsdiff(const float* a, const float* b, long long n, unsigned* ou
     const unsigned g = (unsigned)std::min<long long>(2048, (n + 255) / 256);
     hipLaunchKernelGGL(maxabsdiff_kernel, dim3(g ? g : 1), dim3(256), 0, s, a, b, n, out);
 }
+
+// Which 16 x 16-pixel cells of a raw frame differ from the frame before it, bit for bit (moe_changed_blocks: the frame stream's reuse).  cur and
+// prev hold n dense byte matrices of rows x row_bytes; one WAVE owns one cell (block_rows x block_bytes bytes of every matrix, clipped at the ragged edges), four cells
+// per workgroup.  A lane compares units of V -- 16 bytes when both bases, row_bytes and block_bytes are multiples of 16, else single bytes -- and writes cur's unit into
+// prev where the two differ (compare and retain: one read of each, prev == cur afterwards); lanes are laid over the cell as (rows per pass) x (units per row rounded up
+// to a power of two), so no index is divided.  The cell's flag is the wave's ballot, written by lane 0 with an ordinary store: every cell has exactly one writer.
+template <typename V> __device__ inline bool differs(const V& a, const V& b);
+template <> __device__ inline bool differs<unsigned char>(const unsigned char& a, const unsigned char& b) { return a != b; }
+template <> __device__ inline bool differs<uint4>(const uint4& a, const uint4& b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u; }
+
+template <typename V>
+__global__ __launch_bounds__(256) void maxabsdiff_kernel_bytes(const unsigned char* __restrict__ cur, unsigned char* __restrict__ prev, int n, int rows, long long row_bytes,
+                                                               int block_rows, int block_bytes, long long ncol, long long ncell, unsigned char* __restrict__ map)
+{
+    const long long cell = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= ncell) return;                                   // (a whole wave: the ballot below sees all 64 lanes or none)
+    const int lane = threadIdx.x & 63;
+    const long long bi = cell / ncol, bj = cell - bi * ncol;
+    const long long r0 = bi * block_rows, c0 = bj * block_bytes;
+    const int h = (int)(rows - r0 < block_rows ? rows - r0 : block_rows);
+    const long long wb = row_bytes - c0 < block_bytes ? row_bytes - c0 : block_bytes;
+    const int units = (int)(wb / (long long)sizeof(V));         // (V = 16 bytes: row_bytes and block_bytes are multiples of 16, so is every cell's width)
+    int lpr = 1;
+    while (lpr < units && lpr < 64) lpr <<= 1;
+    const int rpp = 64 / lpr, lr = lane / lpr, lv = lane & (lpr - 1);
+    bool diff = false;
+    for (int m = 0; m < n; ++m) {
+        const long long base = (long long)m * rows * row_bytes + r0 * row_bytes + c0;
+        for (int r = lr; r < h; r += rpp) {
+            const long long row = base + (long long)r * row_bytes;
+            for (int u = lv; u < units; u += lpr) {
+                const long long at = row + (long long)u * (long long)sizeof(V);
+                const V a = *(const V*)(cur + at);
+                const V b = *(const V*)(prev + at);
+                if (differs<V>(a, b)) { diff = true; *(V*)(prev + at) = a; }
+            }
+        }
+    }
+    const bool any = __ballot(diff) != 0ull;
+    if (lane == 0) map[cell] = any ? 1 : 0;
+}
+
+void launch_changed_blocks(const void* cur, void* prev, int n, int rows, long long row_bytes, int block_rows, int block_bytes, unsigned char* map, hipStream_t s)
+{
+    const long long ncol = (row_bytes - 1) / block_bytes + 1, ncell = (((long long)rows - 1) / block_rows + 1) * ncol;
+    const dim3 grid((unsigned)((ncell + 3) / 4)), blk(256);
+    const bool vec = (((uintptr_t)cur | (uintptr_t)prev | (uintptr_t)row_bytes | (uintptr_t)block_bytes) & 15) == 0;
+    if (vec) hipLaunchKernelGGL((maxabsdiff_kernel_bytes<uint4>), grid, blk, 0, s, (const unsigned char*)cur, (unsigned char*)prev, n, rows, row_bytes, block_rows, block_bytes, ncol, ncell, map);
+    else hipLaunchKernelGGL((maxabsdiff_kernel_bytes<unsigned char>), grid, blk, 0, s, (const unsigned char*)cur, (unsigned char*)prev, n, rows, row_bytes, block_rows, block_bytes, ncol, ncell, map);
+}

@@ -38,17 +38,39 @@ struct StitchTables {      // what the stitch kernel reads of a plan besides the
 
 struct UploadedOffsets { int device; std::vector<int64_t> host; void* dev; };   // a caller's pool layout passed to moe_stitch from the host
 
+// moe_run_plan_subset's offset tables.  Its mask is new with every frame, and the cache of tile tables would answer that with a stream synchronise, a hipFree, a hipMalloc
+// and a blocking copy per call once its 16 entries are taken.  The ring is one device block and one pinned host block of kSlots tables each, sized once for the plan's
+// largest table (every tile, C planes, x and y offsets) on first use; a call fills the next slot's host half, sends it with hipMemcpyAsync on the caller's stream in
+// front of its launch sets and records the slot's event behind them.  A slot is taken again kSlots calls later and only once that event has passed: both halves are then
+// free, whatever stream the next call runs on.  A caller that is fewer than kSlots calls ahead of the device -- the frame stream: ring depth x steps x images -- finds
+// the event passed; only one that is further ahead waits for that one event.  Nothing is allocated or freed after the first call, no stream is synchronised.
+struct TableRing {
+    static constexpr int kSlots = 32;
+    int device = -1;
+    size_t slot_bytes = 0;
+    char *host = nullptr, *dev = nullptr;
+    hipEvent_t done[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+};
+
 struct PlanDevice {
     static constexpr size_t kCached = 16;      // tile tables / uploaded layouts kept; the oldest goes first
     std::vector<TileTable> tables;
     std::vector<StitchTables> stitch;          // (a handful: one per device and channel count the plan is stitched with)
     std::vector<UploadedOffsets> uploaded;
+    std::vector<TableRing> rings;              // (one per device the plan's subsets ran on)
     DevBuf pool;                               // per-tile fp32 results when the caller passes no pool
     ~PlanDevice()
     {
         for (auto& t : tables) (void)hipFree(t.dev);
         for (auto& t : stitch) { (void)hipFree(t.dev); for (auto& e : t.strip_tabs) (void)hipFree(e.second); }
         for (auto& u : uploaded) (void)hipFree(u.dev);
+        for (auto& r : rings) {
+            for (hipEvent_t e : r.done) if (e) (void)hipEventDestroy(e);
+            (void)hipHostFree(r.host);
+            (void)hipFree(r.dev);
+        }
         pool.release();
     }
     // Room for one more entry of `tables` or `uploaded`.  The dropped entry's block may still be read by kernels in flight: the runners and the stitch enqueue on the
@@ -74,19 +96,11 @@ static int upload(const void* host, size_t bytes, void** dev)
 
 struct moe_plan { Plan p; mutable PlanDevice dev; };      // (the ABI's runners and stitches take the plan as const: the device state is a cache beside it)
 
-// the tile table of (input layout, destination table): tile_dst[f * n_tiles + k] is where frame f's tile k goes, -1 = not computed by this call
-static int tile_table(const moe_plan& pl, int device, int64_t frame_stride, int64_t sC, int64_t sH, int64_t sW, int n_frames, const int64_t* tile_dst,
-                      hipStream_t s, const TileTable** out)
+// The rows of a tile table: per plan group the (frame, tile) pairs tile_dst names with their planes' offsets in the images (x) and in the destination (y), and what
+// run_sets reads of the table besides them (the groups' slots, y_mult8).  At least one row, so that no table is empty.
+static void table_rows(const Plan& p, int64_t frame_stride, int64_t sC, int64_t sH, int64_t sW, int n_frames, const int64_t* tile_dst, TileTable& d,
+                       std::vector<long long>& off, std::vector<long long>& yo)
 {
-    const Plan& p = pl.p;
-    const size_t n = p.tiles.size() * (size_t)n_frames;      // (entries of tile_dst; equal n_frames: equal sizes)
-    for (const TileTable& c : pl.dev.tables)
-        if (c.device == device && c.sC == sC && c.sH == sH && c.sW == sW && c.frame_stride == frame_stride && c.n_frames == n_frames &&
-            std::equal(c.tile_dst.begin(), c.tile_dst.end(), tile_dst)) { *out = &c; return MOE_OK; }
-    int rc = PlanDevice::make_room(pl.dev.tables, s);
-    if (rc) return rc;
-    TileTable d;
-    std::vector<long long> off, yo;      // x_off, then y_off behind it
     int slot = 0;
     for (const auto& g : p.groups) {     // same-shaped tiles of ALL frames share launches
         d.group_first.push_back(slot);
@@ -107,6 +121,22 @@ static int tile_table(const moe_plan& pl, int device, int64_t frame_stride, int6
     if (off.empty()) { off.push_back(0); yo.push_back(0); }
     d.y_mult8 = true;
     for (long long v : yo) d.y_mult8 = d.y_mult8 && (v % 8 == 0);
+}
+
+// the tile table of (input layout, destination table): tile_dst[f * n_tiles + k] is where frame f's tile k goes, -1 = not computed by this call
+static int tile_table(const moe_plan& pl, int device, int64_t frame_stride, int64_t sC, int64_t sH, int64_t sW, int n_frames, const int64_t* tile_dst,
+                      hipStream_t s, const TileTable** out)
+{
+    const Plan& p = pl.p;
+    const size_t n = p.tiles.size() * (size_t)n_frames;      // (entries of tile_dst; equal n_frames: equal sizes)
+    for (const TileTable& c : pl.dev.tables)
+        if (c.device == device && c.sC == sC && c.sH == sH && c.sW == sW && c.frame_stride == frame_stride && c.n_frames == n_frames &&
+            std::equal(c.tile_dst.begin(), c.tile_dst.end(), tile_dst)) { *out = &c; return MOE_OK; }
+    int rc = PlanDevice::make_room(pl.dev.tables, s);
+    if (rc) return rc;
+    TileTable d;
+    std::vector<long long> off, yo;      // x_off, then y_off behind it
+    table_rows(p, frame_stride, sC, sH, sW, n_frames, tile_dst, d, off, yo);
     off.insert(off.end(), yo.begin(), yo.end());
     rc = upload(off.data(), off.size() * 8, &d.dev);
     if (rc) return rc;
@@ -341,6 +371,39 @@ static int run_plan(const char* who, moe_net* n, const moe_plan* pl, const void*
     rc = run_sets(*n, p, *d, img, img_dtype, sH, sW, pool, max_tiles, s);
     if (rc || !do_stitch) return rc;
     return stitch(*pl, n->device, pool, nullptr, false, p.C, out, out_dtype, nullptr, s, edge);
+}
+
+// The next slot of the plan's table ring on `device` (TableRing above), free to be written: created on first use, then only waited for when the caller is a whole ring
+// ahead of the device.
+static int ring_slot(const moe_plan& pl, int device, TableRing** ring, int* slot)
+{
+    TableRing* r = nullptr;
+    for (TableRing& c : pl.dev.rings) if (c.device == device) r = &c;
+    if (!r) {
+        TableRing t;
+        t.device = device;
+        t.slot_bytes = (std::max<size_t>(1, pl.p.tiles.size() * (size_t)pl.p.C) * 16 + 255) & ~(size_t)255;      // x and y offsets of every plane of every tile
+        HIP_TRY(hipMalloc((void**)&t.dev, t.slot_bytes * TableRing::kSlots));
+        hipError_t e = hipHostMalloc((void**)&t.host, t.slot_bytes * TableRing::kSlots, hipHostMallocDefault);
+        for (int i = 0; i < TableRing::kSlots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&t.done[i], hipEventDisableTiming);
+        if (e != hipSuccess) {
+            for (hipEvent_t ev : t.done) if (ev) (void)hipEventDestroy(ev);
+            if (t.host) (void)hipHostFree(t.host);
+            (void)hipFree(t.dev);
+        }
+        HIP_TRY(e);
+        pl.dev.rings.push_back(t);
+        r = &pl.dev.rings.back();
+    }
+    const int i = r->next;
+    if (r->used[i]) {
+        const hipError_t e = hipEventQuery(r->done[i]);
+        if (e == hipErrorNotReady) HIP_TRY(hipEventSynchronize(r->done[i]));
+        else HIP_TRY(e);
+    }
+    r->next = (i + 1) % TableRing::kSlots;
+    *ring = r; *slot = i;
+    return MOE_OK;
 }
 
 extern "C" {
@@ -626,6 +689,59 @@ int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img
     int rc = tile_table(*pl, n->device, frame_stride, sC, sH, sW, n_frames, tile_dst, s, &d);
     if (rc) return rc;
     return run_sets(*n, p, *d, imgs, img_dtype, sH, sW, dst, max_tiles, s);
+}
+
+int moe_run_plan_subset(moe_net* n, const moe_plan* pl, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW, const uint8_t* run,
+                        float* pool, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img || !run || !pool) return fail(MOE_EINVAL, "moe_run_plan_subset: NULL argument");
+    if (!n->finalized) return fail(MOE_ESTATE, "moe_run_plan_subset: net is not finalized");
+    const Plan& p = pl->p;
+    if (p.sc != n->scale) return fail(MOE_EINVAL, "moe_run_plan_subset: plan scale %d != net scale %d", p.sc, n->scale);
+    std::vector<int64_t> at(p.tile_off.begin(), p.tile_off.end());      // the masked tiles into the plan's own pool layout
+    bool any = false;
+    for (size_t k = 0; k < at.size(); ++k) {
+        if (run[k]) any = true;
+        else at[k] = -1;
+    }
+    if (!any) return MOE_OK;                                            // (nothing to compute: no device call)
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(n->device));
+    TileTable d;
+    std::vector<long long> off, yo;
+    table_rows(p, 0, sC, sH, sW, 1, at.data(), d, off, yo);
+    TableRing* ring = nullptr;
+    int slot = 0;
+    int rc = ring_slot(*pl, n->device, &ring, &slot);
+    if (rc) return rc;
+    const size_t rows = off.size(), at_slot = ring->slot_bytes * (size_t)slot;
+    memcpy(ring->host + at_slot, off.data(), rows * 8);
+    memcpy(ring->host + at_slot + rows * 8, yo.data(), rows * 8);
+    HIP_TRY(hipMemcpyAsync(ring->dev + at_slot, ring->host + at_slot, rows * 16, hipMemcpyHostToDevice, s));
+    ring->used[slot] = true;                                            // (from here on the slot's halves are in use until its event has passed)
+    d.x_off = (const long long*)(ring->dev + at_slot); d.y_off = d.x_off + rows;
+    rc = run_sets(*n, p, d, img, img_dtype, sH, sW, pool, max_tiles, s);
+    const hipError_t e = hipEventRecord(ring->done[slot], s);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return MOE_OK;
+}
+
+int moe_changed_blocks(const void* cur, void* prev, int n, int rows, int64_t row_bytes, int block_rows, int block_bytes, uint8_t* map, int device, void* stream)
+{
+    if (!cur || !prev || !map) return fail(MOE_EINVAL, "moe_changed_blocks: NULL argument");
+    if (n < 1 || rows < 1 || row_bytes < 1) return fail(MOE_EINVAL, "moe_changed_blocks: %d matrices of %d rows x %lld bytes (each must be 1 at least)", n, rows, (long long)row_bytes);
+    if (block_rows < 1 || block_bytes < 1) return fail(MOE_EINVAL, "moe_changed_blocks: blocks of %d rows x %d bytes (each must be 1 at least)", block_rows, block_bytes);
+    if (cur == prev) return fail(MOE_EINVAL, "moe_changed_blocks: cur and prev are the same buffer");
+    if (row_bytes > INT64_MAX / n / rows) return fail(MOE_EINVAL, "moe_changed_blocks: %d matrices of %d rows x %lld bytes do not fit 63 bits", n, rows, (long long)row_bytes);
+    const uint64_t bytes = (uint64_t)n * (uint64_t)rows * (uint64_t)row_bytes, a = (uint64_t)(uintptr_t)cur, b = (uint64_t)(uintptr_t)prev;
+    if ((a < b ? b - a : a - b) < bytes) return fail(MOE_EINVAL, "moe_changed_blocks: cur and prev overlap (%llu bytes each)", (unsigned long long)bytes);
+    const int64_t nrow = ((int64_t)rows - 1) / block_rows + 1, ncol = (row_bytes - 1) / block_bytes + 1;
+    const int64_t cells = ncol > INT32_MAX / nrow ? (int64_t)INT32_MAX + 1 : nrow * ncol;
+    if (cells > INT32_MAX) return fail(MOE_EINVAL, "moe_changed_blocks: a map of %lld cells (2^31 - 1 at most)", (long long)cells);
+    HIP_TRY(hipSetDevice(device));
+    launch_changed_blocks(cur, prev, n, rows, row_bytes, block_rows, block_bytes, map, (hipStream_t)stream);
+    return launched("changed_blocks");
 }
 
 int moe_run_plan_frames(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,

@@ -283,11 +283,14 @@ def _planesOut(who, depth, C, h, w, out, device):
     return out
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None):
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None, reuse=None):
     """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
     alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold, with yuv = (pixFmt, matrix, order) moe_run_plan_yuv: the
     encoder's planar frame from the final fold, with planes = depth moe_run_plan_planes: the image's own planes as samples of that depth) and its one retry after
-    a MemoryError."""
+    a MemoryError.
+    reuse (the frame stream's): a callable (plan, planes) -> (mask, pool) -- the plan's tiles that have to run for this image as n_tiles uint8 on
+    the host, and the fp32 device tensor of plan.pool_elems(planes) that holds every other tile's result from the previous frame.  The call is then moe_run_plan_subset
+    into that pool followed by the same edge's stitch-only entry point on it (moe_stitch, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv, moe_stitch_planes)."""
     model = opt.modelCached
     if not isinstance(model, EngineModule):
         raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
@@ -329,9 +332,31 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
     sC, sH, sW = xp.stride()
     stream = torch.cuda.current_stream(x.device).cuda_stream
     L = _lib.lib()
+    if reuse is not None:
+        mask, pool = reuse(plan, xp.shape[0])
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mask.shape != (plan.n_tiles,) or pool.dtype != torch.float32 or pool.numel() < plan.pool_elems(xp.shape[0]) or pool.device != x.device or not pool.is_contiguous():
+            raise ValueError('{}: reuse must give {} uint8 flags and a contiguous fp32 pool of {} elements on {}'.format(who, plan.n_tiles, plan.pool_elems(xp.shape[0]), x.device))
+        dev, P, dt = x.device.index or 0, xp.shape[0], _DT[xp.dtype]
+
+    def fold():        # the edge alone, on the stream's pool in the plan's own layout
+        if yuv is not None:
+            _lib.check(L.moe_stitch_yuv(plan._h, dev, pool.data_ptr(), None, dt, depth, matrix, order, out.data_ptr(), stream))
+        elif planes is not None:
+            _lib.check(L.moe_stitch_planes(plan._h, dev, pool.data_ptr(), None, P, dt, int(planes), out.data_ptr(), stream))
+        elif mix is not None:
+            _lib.check(L.moe_stitch_mix(plan._h, dev, pool.data_ptr(), None, P, xp.data_ptr(), dt, sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
+                                        strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, stream))
+        elif bitDepth is None:
+            _lib.check(L.moe_stitch(plan._h, dev, pool.data_ptr(), None, P, out.data_ptr(), _DT[out.dtype], stream))
+        else:
+            _lib.check(L.moe_stitch_out(plan._h, dev, pool.data_ptr(), None, P, dt, int(bitDepth), out.data_ptr(), lib_dt, stream))
 
     def run():
-        if yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
+        if reuse is not None:
+            _lib.check(L.moe_run_plan_subset(model._h, plan._h, xp.data_ptr(), dt, sC, sH, sW, mask.ctypes.data, pool.data_ptr(), int(config.tilesPerBatch), stream))
+            fold()
+        elif yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
             _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth, matrix, order,
                                           out.data_ptr(), int(config.tilesPerBatch), stream))
         elif planes is not None:
@@ -357,33 +382,33 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
     return out
 
 
-def doCrop(opt, x, *args, **_):
+def doCrop(opt, x, *args, reuse=None, **_):
     """python/imageProcess.py:157-172, entirely on the device: the planes of x (C,H,W) become the batch
     (runSR.py:37-40), tiles are gathered straight from x by the stem kernel, same-shaped tiles are batched
     through the net, and the gather-stitch kernel folds them with the reference's sequential blend."""
-    return _runPlan('doCrop', opt, x)
+    return _runPlan('doCrop', opt, x, reuse=reuse)
 
 
-def doCropOut(opt, x, bitDepth, out=None):
+def doCropOut(opt, x, bitDepth, out=None, reuse=None):
     """toOutput(bitDepth)(toFloat(doCrop(opt, x))) without the download, as ONE call (moe_run_plan_out): doCrop up to the final fold, which rounds each pixel as the
     canvas of x's dtype would have and writes the quantised (H, W, C) image (uint8, or uint16 samples in int16 storage) -- the canvas and its fp32 copy never exist
     (python/imageProcess.py:157-172,238-257).  out: a contiguous device tensor of that shape and dtype to write into (the frame stream's slot buffers), else a new one."""
-    return _runPlan('doCropOut', opt, x, bitDepth, out)
+    return _runPlan('doCropOut', opt, x, bitDepth, out, reuse=reuse)
 
 
-def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr'):
+def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr', reuse=None):
     """doCropOut(opt, x, 16) followed by pixfmt.fromSamples16, as ONE call (moe_run_plan_yuv): the final fold writes the encoder's planar Y'CbCr 4:2:0 frame -- fmt one of
     pixfmt.FORMATS (yuv420p, yuv420p10le, yuv420p12le, yuv420p16le), limited range, matrix bt709 / bt601 / bt2020nc; order says whether plane 0 of x is blue ('bgr', the
     video path's frames) or red.  Half the bytes of the interleaved image.  Returns a flat uint8 device tensor of pixfmt.frameBytes(fmt, outW, outH); out: one to write into."""
     pixfmt.check(fmt, matrix, order)
-    return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order))
+    return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order), reuse=reuse)
 
 
-def doCropPlanes(opt, x, depth, out=None):
+def doCropPlanes(opt, x, depth, out=None, reuse=None):
     """doCrop(opt, x) quantised plane by plane at `depth` bits (8, 10, 12, 16), as ONE call (moe_run_plan_planes): the final fold rounds each pixel as the canvas of x's
     dtype would have and writes C = 1 .. 4 planes of outH x outW samples (uint8 for depth 8, else little-endian uint16) -- the Y plane or the two chroma planes of a
     planar 4:2:0 frame (pixfmt.fromPlanes).  Returns a flat uint8 device tensor of those bytes; out: one to write into, e.g. a view into a frame at a plane's offset."""
-    return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth))
+    return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth), reuse=reuse)
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------
@@ -581,7 +606,7 @@ def _finite(s):
     return isinstance(s, (int, float)) and math.isfinite(s)
 
 
-def _RGBFilter(opt, img):
+def _RGBFilter(opt, img, reuse=None):
     """The DN wrapper (python/imageProcess.py:350-377): the denoiser sees the colour planes only, `strength` blends its result
     with the input, alpha rides around it.  With config.filterOnDevice the blend and the alpha plane are the final fold's own work (moe_run_plan_filter: one call, no
     temporaries, no concatenation) whenever there is something to blend or to carry; the torch expressions below are the other form of the same bits.  The image
@@ -590,11 +615,11 @@ def _RGBFilter(opt, img):
     rgb = opt.prepare(extractAlpha(alpha)(img))
     if (config.filterOnDevice and isinstance(opt.modelCached, EngineModule) and rgb.device.type == 'cuda' and rgb.dtype in _DT and rgb.dim() == 3
             and rgb.is_contiguous() and rgb.data_ptr() % 16 == 0 and _finite(opt.strength) and (opt.strength != 1 or 'im' in alpha)):
-        return _runPlan('RGBFilter', opt, rgb, mix=(opt.strength, alpha.get('im')))
-    return mergeAlpha(alpha)(strengthOp(doCrop(opt, rgb), rgb, opt.strength))
+        return _runPlan('RGBFilter', opt, rgb, mix=(opt.strength, alpha.get('im')), reuse=reuse)
+    return mergeAlpha(alpha)(strengthOp(doCrop(opt, rgb, reuse=reuse), rgb, opt.strength))
 
 
-def filterOut(opt, img, bitDepth, out=None):
+def filterOut(opt, img, bitDepth, out=None, reuse=None):
     """toOutput(bitDepth)(toFloat(_RGBFilter(opt, img))) without the download, as ONE call (moe_run_plan_filter), as doCropOut is to doCrop: the final fold blends each
     pixel with the input, rounds as the canvas of img's dtype would have and writes the quantised (H, W, C) image, alpha included; neither the canvas nor its fp32
     copy exists.  strength must be finite.  out: as doCropOut's."""
@@ -602,7 +627,7 @@ def filterOut(opt, img, bitDepth, out=None):
         raise ValueError('filterOut: strength must be finite, got {!r}'.format(opt.strength))
     alpha = {}
     rgb = opt.prepare(extractAlpha(alpha)(img))
-    return _runPlan('filterOut', opt, rgb, bitDepth, out, mix=(opt.strength, alpha.get('im')))
+    return _runPlan('filterOut', opt, rgb, bitDepth, out, mix=(opt.strength, alpha.get('im')), reuse=reuse)
 
 
 RGBFilter = lambda opt: lambda img: _RGBFilter(opt, img)

@@ -16,14 +16,16 @@ three queues, the last fold writing the encoder's samples itself (imageProcess.d
 
 With {'op': 'buffer', 'pixFmt': 'yuv420p' | 'yuv420p10le' | 'yuv420p12le' | 'yuv420p16le'} as the source step both builders take the decoder's planar Y'CbCr 4:2:0
 frames as they are and run the chain on Y' and on Cb / Cr as two images.
+
+`genFrameStream(.., reuse=True)` keeps each step's tile pool from the previous frame and runs only the tiles whose input changed, bit for bit.
 """
 import math
 import time
 from functools import reduce
 
-from . import _lib, pixfmt, runDN, runSR
+from . import _lib, pixfmt, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (RGBFilter, apply, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
+from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
                            toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -75,9 +77,11 @@ def _planeFormats(steps, width=None, height=None):
     return src, dst
 
 
-def _planeChain(steps, fuse):
+def _planeChain(steps, fuse, rsteps=None):
     """The compute steps of a planar chain -> (funcs, nodes, scale, last): funcs map a (C, H, W) image to the next; with fuse, a last step whose final fold can write
-    the samples itself (an SR without ensemble, a DN of strength 1) is left out of funcs and returned as last = (Option, its prepare)."""
+    the samples itself (an SR without ensemble, a DN of strength 1) is left out of funcs and returned as last = (Option, its prepare).  rsteps: a list that receives
+    the reuse form of every entry of funcs (_ReuseState)."""
+    rsteps = [] if rsteps is None else rsteps
     work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
     for opt in work:
         if opt['op'] not in stepOpts:
@@ -99,11 +103,13 @@ def _planeChain(steps, fuse):
                 last = (o, identity)
             else:
                 funcs.append(runSR.sr(o))
+                rsteps.append(_reuseSR(o, funcs[-1]))
             scale *= opt['scale']
         elif final and o.strength == 1:
             last = (o, o.prepare)
         else:
             funcs.append(RGBFilter(o))
+            rsteps.append(_reuseDN(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
     return funcs, nodes, scale, last
 
@@ -230,6 +236,88 @@ def _checkRing(depth, bitDepth):
         raise ValueError('frame stream: bitDepth must be 8 or 16, got {!r}'.format(bitDepth))
 
 
+# ---- reuse between frames ------------------------------------------------------------------------------------------------
+# With reuse the backend keeps the previous raw frame on the device; the upload stage compares the new one against it (moe_changed_blocks, which also retains it) and
+# sends the cell map(s) to pinned memory in front of the `uploaded` event; the compute stage waits for that event on the host, then walks the chain with the rules of
+# moephoto_amd/reuse.py: every tiled step runs the tiles whose support touches a changed cell into the pool it kept from the previous frame (moe_run_plan_subset) and
+# folds the whole pool as always.  A step is described to the walk as (kind, f, ..): 'tiles' -- f(x, reuse) takes _runPlan's reuse callback; 'resize' -- f(x) with the
+# step's dict behind it; 'opaque' -- f(x), no rule: it runs as it is and its output counts as wholly changed.
+def _reuseSR(o, f):
+    return ('tiles', lambda x, reuse, o=o: doCrop(o, x, reuse=reuse)) if o.ensemble == 0 else ('opaque', f)
+
+
+def _reuseDN(o):
+    return ('tiles', lambda x, reuse, o=o: _RGBFilter(o, x, reuse))
+
+
+def _checkReuse(reuse):
+    if not isinstance(reuse, bool):
+        raise ValueError('frame stream: reuse must be True or False, got {!r}'.format(reuse))
+
+
+class _ReuseState(object):
+    """What a reuse stream owns besides its slots: the tracker (which plan each step ran with), one pool per step and image, the counters (`stream.reuse`):
+    tiles[(step, image)] = [planned, run] over the stream, frames = the same per frame for the last 256 frames, pixels_planned / pixels_run = input pixels of the
+    planes of those tiles."""
+
+    def __init__(self, steps, tiledEdge):
+        from collections import deque
+        self.steps, self.tiledEdge = list(steps), tiledEdge
+        self.tracker, self.pools = _reuse.Tracker(), {}
+        self.stats = dict(frames=deque(maxlen=256), tiles={}, pixels_planned=0, pixels_run=0)
+        self.n = 0
+
+    def begin(self):
+        self.frame = {}
+        self.stats['frames'].append(self.frame)
+        self.n += 1
+        return self.n == 1          # the first frame: there is no frame before it, whatever the map says
+
+    def callback(self, key, changed):
+        """_runPlan's reuse callback for one step of one image; its .out is the region of the step's output once it has been called."""
+        import torch
+
+        def cb(plan, C):
+            mask, cb.out = self.tracker.step(key, plan, changed)
+            n, ent = plan.pool_elems(C), self.pools.get(key)
+            if ent is None or ent[0] is not plan or ent[1].numel() != n:          # no results of the previous frame under this plan: everything runs
+                ent = self.pools[key] = (plan, torch.empty((n,), dtype=torch.float32, device=torch.device(config.device())))
+                mask[:] = 1
+                cb.out = None
+            px = self.tracker.regions(plan).pixels
+            planned, run = len(mask), int(mask.sum())
+            self.frame[key] = (planned, run)
+            tot = self.stats['tiles'].setdefault(key, [0, 0])
+            tot[0] += planned
+            tot[1] += run
+            self.stats['pixels_planned'] += C * sum(px)
+            self.stats['pixels_run'] += C * sum(p for p, m in zip(px, mask) if m)
+            return mask, ent[1]
+        cb.out = None
+        return cb
+
+    def walk(self, image, x, changed):
+        """The chain's steps in front of the edge on one image: -> (the edge's input, its region; None = all of it)."""
+        for i, step in enumerate(self.steps):
+            kind, f = step[0], step[1]
+            if kind == 'tiles':
+                cb = self.callback((i, image), changed)
+                x, changed = f(x, cb), cb.out
+            elif kind == 'resize':
+                y = f(x)
+                changed = _reuse.resizeRegion(changed, tuple(x.shape[-2:]), tuple(y.shape[-2:]), step[2]['method']) if changed is not None else None
+                x = y
+            else:
+                x, changed = f(x), None
+        return x, changed
+
+    def edgeCallback(self, image, changed):
+        return self.callback((len(self.steps), image), changed) if self.tiledEdge else None
+
+    def close(self):
+        self.pools.clear()
+
+
 class FrameStream(object):
     def __init__(self, backend, width, height, bitDepth, depth=2, nodes=(), frameBytes=None):
         _checkRing(depth, bitDepth)
@@ -300,9 +388,9 @@ class _DeviceBackend(object):
     edge on torch's current stream; download = async D2H into the slot's pinned buffer on a third stream.  timing: the events take timestamps and `stats` sums the
     milliseconds per stage over the collected frames (tools/frame_stream_bench.py)."""
 
-    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None):
+    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None, reuse=None):
         import torch
-        self.torch, self.funcs, self.edge, self.bitDepth, self.timing = torch, funcs, edge, bitDepth, timing
+        self.torch, self.funcs, self.edge, self.bitDepth, self.timing, self.reuse = torch, funcs, edge, bitDepth, timing, reuse
         self.dev = torch.device(config.device())
         if self.dev.type != 'cuda':
             raise _lib.EngineError('frame stream: needs a HIP device (moephoto_amd has no CPU path)')
@@ -321,6 +409,31 @@ class _DeviceBackend(object):
                 s.update(t_up=self.event(), t_comp=self.event(), t_down=self.event())
             self.slots.append(s)
         self.stats = dict(frames=0, memcpy_ms=0.0, h2d_ms=0.0, compute_ms=0.0, d2h_ms=0.0, tobytes_ms=0.0)
+        if reuse is not None:          # the retained raw frame, the change map(s) on the device and one pinned copy per slot
+            self.prev = torch.empty_like(self.slots[0]['raw'])
+            self.maps = self._maps()
+            self.map_dev = torch.empty((sum(a * b for a, b in self.maps),), dtype=torch.uint8, device=self.dev)
+            for s in self.slots:
+                s['pin_map'] = torch.empty((self.map_dev.numel(),), dtype=torch.uint8, pin_memory=True)
+                s['map_np'] = s['pin_map'].numpy()
+
+    def _maps(self):
+        """The cell grids of the images the chain starts from, in the order of the map buffer."""
+        return [_reuse.cells(self.H, self.W)]
+
+    def _detect(self, s, stream):
+        """moe_changed_blocks on the slot's raw frame against the retained one: an interleaved frame is one matrix, a cell 16 pixels of 3 samples wide."""
+        es = 1 if self.bitDepth <= 8 else 2
+        _lib.check(_lib.lib().moe_changed_blocks(s['raw'].data_ptr(), self.prev.data_ptr(), 1, self.H, self.W * 3 * es, _reuse.CELL, _reuse.CELL * 3 * es,
+                                                 self.map_dev.data_ptr(), self.dev.index or 0, stream.cuda_stream))
+
+    def _changed(self, s, first):
+        """The regions of the chain's input images for the slot's frame, from its pinned map (None: the first frame)."""
+        out, at = [], 0
+        for a, b in self.maps:
+            out.append(None if first else s['map_np'][at:at + a * b].reshape(a, b) != 0)
+            at += a * b
+        return out
 
     def _slot(self, in_dt):
         """A slot's input side: the pinned and the device copy of the raw frame, and the image(s) the chain starts from."""
@@ -350,15 +463,35 @@ class _DeviceBackend(object):
         def work(stream):
             with self.torch.cuda.stream(stream):
                 s['raw'].copy_(s['pin_in'], non_blocking=True)
+                if self.reuse is not None:          # right behind the copy, in front of the `uploaded` event: the map is on the host once that event has passed
+                    self._detect(s, stream)
+                    s['pin_map'].copy_(self.map_dev, non_blocking=True)
+        if self.reuse is not None:
+            s['uploaded'] = record
         self._stage(self.up, s, 'up', wait, record, work)
+
+    def _regions(self, s):
+        """The compute stage's first act with reuse: wait on the host for the frame's own `uploaded` event -- recorded by an earlier statement of this thread, so the
+        wait cannot hang -- and read the regions the chain starts from."""
+        s['uploaded'].synchronize()
+        return self._changed(s, self.reuse.begin())
 
     def compute(self, slot, wait, record):
         s = self.slots[slot]
+        R = self.reuse
+        changed = self._regions(s)[0] if R is not None else None
 
         def work(stream):
             _lib.check(_lib.lib().moe_to_float(s['raw'].data_ptr(), self.src_dt, self.bitDepth, self.H, self.W, 3, s['x'].data_ptr(), _DT[s['x'].dtype],
                                                self.dev.index or 0, stream.cuda_stream))
-            self.edge(reduce(apply, self.funcs, s['x']), s['out'])
+            if R is None:
+                self.edge(reduce(apply, self.funcs, s['x']), s['out'])
+                return
+            x, region = R.walk('rgb', s['x'], changed)
+            if R.tiledEdge:
+                self.edge(x, s['out'], R.edgeCallback('rgb', region))
+            else:
+                self.edge(x, s['out'])
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
     def download(self, slot, wait, record):
@@ -387,15 +520,29 @@ class _DeviceBackend(object):
     def close(self):
         self.torch.cuda.synchronize(self.dev)
         self.slots = []
+        if self.reuse is not None:
+            self.reuse.close()
+            self.prev = self.map_dev = None
 
 
 class _PlanesBackend(_DeviceBackend):
     """The same three queues for a chain on the decoder's planes: a slot's input is the flat planar frame (pinned and on the device), its images are Y (1, H, W) and
     C (2, H / 2, W / 2), its output the flat planar frame of outBytes.  compute = moe_planes_to_float, the chain on Y and then on C, and edge(y, c, out)."""
 
-    def __init__(self, funcs, edge, fmt, width, height, depth, timing, outBytes):
+    def __init__(self, funcs, edge, fmt, width, height, depth, timing, outBytes, reuse=None):
         self.convert, self.inBytes = fromPlanes(fmt, width, height, config.dtype()), pixfmt.frameBytes(fmt, width, height)
-        super().__init__(funcs, edge, 8 if pixfmt.FORMATS[fmt] == 8 else 16, width, height, None, depth, timing, outBytes)
+        super().__init__(funcs, edge, 8 if pixfmt.FORMATS[fmt] == 8 else 16, width, height, None, depth, timing, outBytes, reuse)
+
+    def _maps(self):
+        return [_reuse.cells(self.H, self.W), _reuse.cells(self.H // 2, self.W // 2)]
+
+    def _detect(self, s, stream):
+        """The Y plane is one matrix, Cb and Cr are two matrices folded into one map: a cell is 16 x 16 pixels of the image the chain sees."""
+        es = 1 if self.bitDepth <= 8 else 2
+        L, raw, prev, m, ny = _lib.lib(), s['raw'].data_ptr(), self.prev.data_ptr(), self.map_dev.data_ptr(), self.H * self.W * es
+        _lib.check(L.moe_changed_blocks(raw, prev, 1, self.H, self.W * es, _reuse.CELL, _reuse.CELL * es, m, self.dev.index or 0, stream.cuda_stream))
+        _lib.check(L.moe_changed_blocks(raw + ny, prev + ny, 2, self.H // 2, self.W // 2 * es, _reuse.CELL, _reuse.CELL * es, m + self.maps[0][0] * self.maps[0][1],
+                                        self.dev.index or 0, stream.cuda_stream))
 
     def _slot(self, in_dt):
         torch = self.torch
@@ -406,31 +553,45 @@ class _PlanesBackend(_DeviceBackend):
     def compute(self, slot, wait, record):
         s = self.slots[slot]
 
+        R = self.reuse
+        changed = self._regions(s) if R is not None else None
+
         def work(stream):
             y, c = self.convert(s['raw'], s['y'], s['c'])
-            self.edge(reduce(apply, self.funcs, y), reduce(apply, self.funcs, c), s['out'])
+            if R is None:
+                self.edge(reduce(apply, self.funcs, y), reduce(apply, self.funcs, c), s['out'])
+                return
+            (y, ry), (c, rc) = R.walk('y', y, changed[0]), R.walk('c', c, changed[1])
+            if R.tiledEdge:
+                self.edge(y, c, s['out'], R.edgeCallback('y', ry), R.edgeCallback('c', rc))
+            else:
+                self.edge(y, c, s['out'])
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
 
-def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing):
+def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False):
     src, dst = fmts
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
-    funcs, nodes, scale, last = _planeChain(steps, True)
+    _checkReuse(reuse)
+    rsteps = []
+    funcs, nodes, scale, last = _planeChain(steps, True, rsteps)
     w, h = int(width) * scale, int(height) * scale
     D, cb = pixfmt.FORMATS[dst], pixfmt.planeOffsets(dst, w, h)[1]
     if last:          # the last step's two folds write straight into the slot's frame, at the Y and at the Cb offset: no canvas exists
         o, prepare = last
-        into, edgeName = (lambda x, out: doCropPlanes(o, prepare(x), D, out)), 'crop'
+        into, edgeName = (lambda x, out, reuse=None: doCropPlanes(o, prepare(x), D, out, reuse=reuse)), 'crop'
     else:
-        into, edgeName = toPlanes(D), 'quantise'
+        quantise = toPlanes(D)
+        into, edgeName = (lambda x, out, reuse=None: quantise(x, out)), 'quantise'
 
-    def edge(y, c, out):
-        into(y, out[:cb])
-        into(c, out[cb:])
-    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h))
+    def edge(y, c, out, reuseY=None, reuseC=None):
+        into(y, out[:cb], reuseY)
+        into(c, out[cb:], reuseC)
+    state = _ReuseState(rsteps, bool(last)) if reuse else None
+    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h), state)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
-    stream.edge = edgeName
+    stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
 
 
@@ -453,7 +614,7 @@ def _quantiseInto(bitDepth):
     return f
 
 
-def genFrameStream(steps, width, height, depth=2, timing=False):
+def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False):
     """genProcess for a video source as a stream: `steps` as genProcess takes them, steps[0] = {'op': 'buffer', 'bitDepth': 8 | 16}; frames are width x height x 3.
     Returns a FrameStream: push(raw) -> list of finished frames' bytes (input order; [] for an empty buffer), flush(), close(), nodes.  The last compute step decides
     the output edge, named by the stream's `edge`: 'crop' -- an SR without ensemble or a DN of strength 1 folds its tiles straight into the encoder's samples
@@ -463,22 +624,26 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
     tiles straight into them (doCropYuv); every other chain ends in toYuv on the step's result (a 'filter' chain blends in RGBFilter first).
     With steps[0] = {'op': 'buffer', 'pixFmt': ..} the frames pushed are the decoder's planar Y'CbCr 4:2:0 frames (pixfmt.frameBytes bytes, even width and height), the
     chain runs on Y' and on Cb / Cr as two images and the finished frames are planar again, at the source's format or the output step's: 'crop' -- two doCropPlanes
-    folds write straight into the frame -- or 'quantise' (toPlanes); no resize step, no matrix / order (ValueError before a model is loaded)."""
+    folds write straight into the frame -- or 'quantise' (toPlanes); no resize step, no matrix / order (ValueError before a model is loaded).
+    reuse=True (either source kind, every edge): the stream keeps each step's tile pool from the previous frame and runs only the tiles whose input changed bit for
+    bit -- frames shown twice, static shots, slides; the finished frames are the same bytes.  `stream.reuse` then holds the counters (tiles
+    planned / run per step and image, plane-tile pixels planned / run over the stream; None without reuse)."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
     planar = _planeFormats(steps, width, height)
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
-        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing)
+        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse)
     bitDepth = int(steps[0].get('bitDepth', 16))
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
+    _checkReuse(reuse)                   # (likewise)
     yuvOf = toYuv(*yuv) if yuv else None
     work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
     for opt in work:
         if opt['op'] not in stepOpts:
             raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(opt['op']))
-    funcs, nodes, edge, edgeName = [], [], None, 'quantise'
+    funcs, nodes, edge, edgeName, rsteps = [], [], None, 'quantise', []
     h, w = int(height), int(width)
     for k, opt in enumerate(work):
         op, last = opt['op'], k == len(work) - 1
@@ -487,6 +652,7 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
         convertValues(float, opt, so.get('toFloat', []))
         if op == 'resize':
             funcs.append(resize(opt, dict(source=True)))
+            rsteps.append(('resize', funcs[-1], opt))
             h = round(h * opt['scaleH']) if 'scaleH' in opt else opt['height']
             w = round(w * opt['scaleW']) if 'scaleW' in opt else opt['width']
             nodes.append(dict(op='resize', mode=opt['method']))
@@ -499,22 +665,28 @@ def genFrameStream(steps, width, height, depth=2, timing=False):
             if not opt['scale'] > 1:
                 raise TypeError('Invalid scale setting for SR.')
             if last and o.ensemble == 0:
-                edge, edgeName = (lambda x, out, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:]) if yuv else doCropOut(o, x, bitDepth, out)), 'crop'
+                edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:], reuse=reuse) if yuv
+                                  else doCropOut(o, x, bitDepth, out, reuse=reuse)), 'crop'
             else:
                 funcs.append(runSR.sr(o))
+                rsteps.append(_reuseSR(o, funcs[-1]))
             h, w = h * opt['scale'], w * opt['scale']
         elif last and o.strength == 1:         # RGBFilter on three planes with nothing to blend: prepare, doCrop
-            edge, edgeName = (lambda x, out, o=o: doCropYuv(o, o.prepare(x), yuv[0], out, *yuv[1:]) if yuv else doCropOut(o, o.prepare(x), bitDepth, out)), 'crop'
+            edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, o.prepare(x), yuv[0], out, *yuv[1:], reuse=reuse) if yuv
+                              else doCropOut(o, o.prepare(x), bitDepth, out, reuse=reuse)), 'crop'
         elif last and config.filterOnDevice and isinstance(o.strength, (int, float)) and math.isfinite(o.strength):      # the blend with the frame inside the fold
-            edge, edgeName = (lambda x, out, o=o: yuvOf(RGBFilter(o)(x), out) if yuv else filterOut(o, x, bitDepth, out)), 'filter'
+            edge, edgeName = (lambda x, out, reuse=None, o=o: yuvOf(_RGBFilter(o, x, reuse), out) if yuv else filterOut(o, x, bitDepth, out, reuse=reuse)), 'filter'
         else:
             funcs.append(RGBFilter(o))
+            rsteps.append(_reuseDN(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
+    tiledEdge = edge is not None
     if edge is None:
         edge = yuvOf or _quantiseInto(bitDepth)
-    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None)
+    state = _ReuseState(rsteps, tiledEdge) if reuse else None
+    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
-    stream.edge = edgeName
+    stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
 
 
