@@ -334,6 +334,18 @@ int moe_stitch_planes(const moe_plan* plan, int device, const float* tiles_dev, 
 int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                         int canvas_dtype, int depth, void* dst, int max_tiles_per_batch, void* stream);
 
+/* The chroma planes of a LUMA-ONLY chain: the net runs on Y' alone and Cb / Cr are brought to the new size by a fixed resampling filter, in integers -- the definition
+ * is moephoto_amd/pixfmt.py (chromaTable, resampleChroma) and the device matches it byte for byte.  src = two planes of h x w codes, one after the other (uint8 at
+ * depth 8, little-endian uint16 at 10, 12, 16; high bits are not masked); dst = two planes of h * scale x w * scale at dst_depth, likewise.  Any 2-byte aligned
+ * address (any address at depth 8): the Cb plane of a frame starts wherever its Y plane ends.  cx / ox and cy / oy are HOST tables, per axis scale x taps 14-bit
+ * coefficients and scale offsets: output index o = q * scale + p reads the source samples clamp(q + off[p] + j, 0, n - 1), j < taps (1, 2 or 4).  Row pass in int32,
+ * column pass in int64, sample = clamp((v + 2^27) >> 28, 0, 2^src_depth - 1), then << (dst_depth - src_depth) or >> (src_depth - dst_depth).  Refused (MOE_EINVAL,
+ * before any device call): a NULL pointer, a depth outside {8, 10, 12, 16}, h, w or scale below 1, scale above 16, taps outside {1, 2, 4}, a misaligned pointer, a
+ * coefficient row that does not sum to 2^14 or whose sum of magnitudes exceeds 32767 (so the int32 row pass holds for any uint16 code), an offset outside [-2, 1].
+ * Asynchronous on `stream`. */
+int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
+                        const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream);
+
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
  * alpha, strength, bits, dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */

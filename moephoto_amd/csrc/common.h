@@ -511,6 +511,10 @@ void launch_to_float(const void* src, int src_dtype, float inv_or_div, bool divi
 void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s);
 // a planar 4:2:0 frame of H x W (u8 for depth 8, else u16) -> dst_y (1, H, W) and dst_c (2, H / 2, W / 2), code * 2^-depth (moephoto_amd/pixfmt.py: toPlanes)
 void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, hipStream_t s);
+// chroma.hip: one axis of moe_chroma_resample's polyphase filter, by value in the kernel's arguments: output phase p reads TAPS source samples from off[p] on
+// (relative to q = o / scale) with the 14-bit coefficients coef[p][0 .. TAPS) (moephoto_amd/pixfmt.py: chromaTable)
+struct ChromaTab { short coef[16][4]; signed char off[16]; };
+void launch_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps, const ChromaTab& tx, const ChromaTab& ty, hipStream_t s);
 // (C, H, W) -> (C, h, w); mode 0 nearest, 1 bilinear, 2 bicubic (torch F.interpolate semantics, align_corners = False)
 void launch_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, hipStream_t s);
 // max |a - b| over n floats, atomically folded into *out as the bits of a non-negative float (zero it first)

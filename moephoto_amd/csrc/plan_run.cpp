@@ -913,6 +913,39 @@ int moe_planes_to_float(const void* src, int depth, int H, int W, void* dst_y, v
     return launched("to_float_planes");
 }
 
+int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
+                        const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream)
+{
+    if (!src || !dst || !cx || !ox || !cy || !oy) return fail(MOE_EINVAL, "moe_chroma_resample: NULL argument");
+    if (!plane_depth(src_depth) || !plane_depth(dst_depth)) return fail(MOE_EINVAL, "moe_chroma_resample: depth %d -> %d (8, 10, 12 or 16)", src_depth, dst_depth);
+    if (h < 1 || w < 1) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d must be positive", w, h);
+    if (scale < 1 || scale > 16) return fail(MOE_EINVAL, "moe_chroma_resample: scale %d (1 to 16)", scale);
+    if ((long long)h * scale > 0x7fffffffll || (long long)w * scale > 0x7fffffffll) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d times %d does not fit an int", w, h, scale);
+    if (taps != 1 && taps != 2 && taps != 4) return fail(MOE_EINVAL, "moe_chroma_resample: %d taps (1, 2 or 4)", taps);
+    if (src_depth > 8 && ((uintptr_t)src & 1)) return fail(MOE_EINVAL, "moe_chroma_resample: src is not 2-byte aligned (depth %d: uint16 samples)", src_depth);
+    if (dst_depth > 8 && ((uintptr_t)dst & 1)) return fail(MOE_EINVAL, "moe_chroma_resample: dst is not 2-byte aligned (depth %d: uint16 samples)", dst_depth);
+    ChromaTab t[2] = {};
+    const int16_t* const coef[2] = {cx, cy};
+    const int8_t* const off[2] = {ox, oy};
+    for (int a = 0; a < 2; ++a)
+        for (int p = 0; p < scale; ++p) {
+            int sum = 0, mag = 0;
+            for (int j = 0; j < taps; ++j) {
+                const int c = coef[a][p * taps + j];
+                t[a].coef[p][j] = (short)c;
+                sum += c; mag += c < 0 ? -c : c;
+            }
+            // sum |c| <= 32767: the row pass's int32 sum holds for any uint16 code (32767 * 65535 < 2^31) -- part of the contract, the kernel does not check it
+            if (sum != 16384 || mag > 32767)
+                return fail(MOE_EINVAL, "moe_chroma_resample: %s coefficients of phase %d sum to %d (must be 16384) with magnitudes %d (32767 at most)", a ? "vertical" : "horizontal", p, sum, mag);
+            if (off[a][p] < -2 || off[a][p] > 1) return fail(MOE_EINVAL, "moe_chroma_resample: %s offset %d of phase %d (-2 to 1)", a ? "vertical" : "horizontal", (int)off[a][p], p);
+            t[a].off[p] = off[a][p];
+        }
+    HIP_TRY(hipSetDevice(device));
+    launch_chroma_resample(src, src_depth, h, w, dst, dst_depth, scale, taps, t[0], t[1], (hipStream_t)stream);
+    return launched("resize_kernel_codes");
+}
+
 int moe_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, int device, void* stream)
 {
     if (!src || !dst || C < 1 || H < 1 || W < 1 || h < 1 || w < 1) return fail(MOE_EINVAL, "moe_resize: bad argument");

@@ -15,6 +15,7 @@
 // The fold itself (stitch_classify, stitch_fold_row, stitch_pixel) exists once, so the bit equalities the tests demand between the edges (moe_stitch_out == moe_stitch ->
 // float -> quantise, moe_stitch_mix == stitch + torch) hold by construction.  This file is compiled without extra flags: the fold's cur + w (q - cur) contracts to one FMA.
 #include "common.h"
+#include "run_store.h"
 #include <type_traits>
 #include "../../include/moephoto_amd.h"
 
@@ -96,28 +97,6 @@ __device__ __forceinline__ StitchFold<NP> stitch_fold_row(const StitchArgs& a, c
         }
     }
     return f;
-}
-
-// A run of N elements a thread writes at once: aligned vector stores where the address allows it, element by element elsewhere (a canvas whose width is not a
-// multiple of 8, a base in the middle of a buffer).  The vector path stores words, not the struct: a struct copy is taken apart into element stores, the ones that
-// equal the fallback's are then sunk behind the branch, and the "vector" path keeps 16-byte stores for part of the run only (samples of the 8K canvas: 257 us for 211).
-// (a run of four bytes -- four u8 chroma samples -- is one word)
-template <typename T, int N> struct alignas((sizeof(T) * N) % 16 == 0 ? 16 : (sizeof(T) * N) % 8 == 0 ? 8 : 4) StitchRun { T e[N]; };
-
-template <typename T, int N>
-__device__ __forceinline__ void stitch_store(T* p, const StitchRun<T, N>& v)
-{
-    constexpr int A = alignof(StitchRun<T, N>), NV = sizeof(StitchRun<T, N>) / A;
-    typedef unsigned vec_t __attribute__((ext_vector_type(A / 4)));
-    if (((uintptr_t)p & (A - 1)) == 0) {
-        vec_t q[NV];
-        __builtin_memcpy(q, &v, sizeof(v));
-#pragma unroll
-        for (int k = 0; k < NV; ++k) ((vec_t*)p)[k] = q[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) p[k] = v.e[k];
-    }
 }
 
 // The skeleton: a block of 256 threads takes the canvas rows [Y0, Y0 + R) of [a.y0, a.y0 + a.rows) (a band: moe_stitch_band; the whole canvas: y0 = 0, rows = out_h)

@@ -12,6 +12,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   doCropYuv, toYuv                     (python/video.py:24,219,230 fix the pipe to bgr24 / bgr48le) -> moe_run_plan_yuv / moe_to_yuv: the encoder's 4:2:0 planes
   fromPlanes, doCropPlanes, toPlanes   (python/video.py:24,219 ask the decoder for bgr24 / bgr48le) -> moe_planes_to_float / moe_run_plan_planes / moe_to_output: chains on
                                        the decoder's own 4:2:0 planes, Y' as a (1, H, W) image and Cb / Cr as a (2, H / 2, W / 2) image (pixfmt.toPlanes / fromPlanes)
+  resampleChroma                       (no counterpart: the reference's pipe is RGB) -> moe_chroma_resample: the chroma planes of a luma-only chain, by the integer
+                                       polyphase filter of pixfmt.resampleChroma
   readFile / writeFile                 :265-302         (PIL, host)
 
 There is no CPU path: models must be moephoto_amd.models.EngineModule instances on a HIP device.
@@ -763,6 +765,36 @@ def toPlanes(depth):
         _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], C * H, W, 1, int(depth), out.data_ptr(), _lib.U8 if depth == 8 else _lib.U16,
                                             y.device.index or 0, cur.cuda_stream))
         y.record_stream(cur)
+        return out
+    return f
+
+
+def resampleChroma(srcFmt, dstFmt, w, h, scale, method, loc='center'):
+    """The chroma planes of a luma-only chain (moe_chroma_resample; the definition: pixfmt.resampleChroma): f(raw_dev, out) reads the Cb and Cr planes of the planar
+    4:2:0 frame of w x h in raw_dev (a flat uint8 device tensor of pixfmt.frameBytes(srcFmt, w, h)) and writes them, `scale` times as large and at dstFmt's depth,
+    into the chroma planes of the frame of w * scale x h * scale in out (flat uint8, pixfmt.frameBytes(dstFmt, w * scale, h * scale)); out's Y plane is not touched.
+    The tables are pixfmt.chromaTable's: `loc` sites the horizontal axis, the vertical one is always 'center'."""
+    (_, _), (ch, cw) = pixfmt.planeShapes(srcFmt, w, h)
+    if dstFmt not in pixfmt.FORMATS:
+        raise ValueError('pixFmt "{}" is not supported ({})'.format(dstFmt, ', '.join(pixfmt.FORMATS)))
+    (ox, cx), (oy, cy) = pixfmt.chromaTable(method, scale, loc), pixfmt.chromaTable(method, scale, 'center')
+    taps = pixfmt.CHROMA_METHODS[method]
+    flat = lambda rows: [c for row in rows for c in row]
+    tabs = ((ctypes.c_int16 * (scale * taps))(*flat(cx)), (ctypes.c_int8 * scale)(*ox), (ctypes.c_int16 * (scale * taps))(*flat(cy)), (ctypes.c_int8 * scale)(*oy))
+    n_in, n_out = pixfmt.frameBytes(srcFmt, w, h), pixfmt.frameBytes(dstFmt, w * scale, h * scale)
+    at_in, at_out = pixfmt.planeOffsets(srcFmt, w, h)[1], pixfmt.planeOffsets(dstFmt, w * scale, h * scale)[1]
+    Ds, Dd = pixfmt.FORMATS[srcFmt], pixfmt.FORMATS[dstFmt]
+
+    def f(raw_dev, out):
+        if raw_dev.device.type != 'cuda' or out.device != raw_dev.device:
+            raise _lib.EngineError('resampleChroma: both frames must live on one HIP device (moephoto_amd has no CPU path)')
+        for t, n in ((raw_dev, n_in), (out, n_out)):
+            if tuple(t.shape) != (n,) or t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError('resampleChroma: a flat contiguous uint8 tensor of {} bytes expected, got {} {}'.format(n, t.dtype, tuple(t.shape)))
+        cur = torch.cuda.current_stream(raw_dev.device)
+        _lib.check(_lib.lib().moe_chroma_resample(raw_dev.data_ptr() + at_in, Ds, ch, cw, out.data_ptr() + at_out, Dd, scale, taps, *tabs,
+                                                  raw_dev.device.index or 0, cur.cuda_stream))
+        raw_dev.record_stream(cur)
         return out
     return f
 

@@ -1,5 +1,6 @@
 """The encoder's planar Y'CbCr 4:2:0 frames: the definition the device kernels (stitch_yuv_kernel, to_output_yuv_kernel) are held to, in numpy.  (Below it, the
-definition of chains that run on such planes as they come from the decoder, with no conversion at all: planeShapes, toPlanes, fromPlanes.)
+definition of chains that run on such planes as they come from the decoder, with no conversion at all: planeShapes, toPlanes, fromPlanes; and below that the
+integer resampling filter that writes the chroma planes of a luma-only chain: chromaTable, resampleChroma.)
 
 The reference fixes the pipe's pixel format to bgr24 / bgr48le (python/video.py:24,219,230) and leaves the conversion to the encoder's side; here the last pass over a
 frame can write the encoder's own planes.  This module is the written specification and the comparator of the tests; it is on no hot path.
@@ -138,3 +139,83 @@ def fromSamples16(hwc, fmt, matrix='bt709', order='bgr'):
     chroma = lambda k: (128 << (D - 8)) + (((k[0] * sr + k[1] * sg + k[2] * sb) * 224 + (1 << (39 - D))) >> (40 - D))
     dt = np.uint8 if D == 8 else np.dtype('<u2')
     return b''.join(np.ascontiguousarray(p).astype(dt).tobytes() for p in (Y, chroma(urow), chroma(vrow)))
+
+
+# ---- luma-only chains: the chroma planes by a fixed integer polyphase filter -------------------------------------------------------------------
+# The other form of a chain on 4:2:0 planes: the net runs on Y' alone and Cb / Cr are brought to the output's size by a resampling filter -- what the device kernel
+# (resize_kernel_codes, moe_chroma_resample) is held to, byte for byte.  The library builds no table of its own: chromaTable is the only definition.
+#
+# Output index o = q * scale + p reads around the source coordinate q + r(p):
+#     'center'   r = (2 p + 1 - scale) / (2 scale)      align_corners = False, moe_resize's and the net path's convention
+#     'left'     r = p / scale                          chroma co-sited with the even luma columns (MPEG-2, H.264, HEVC); the horizontal axis only
+# nearest: off = floor(r + 1/2), one coefficient 2^14.  Otherwise f = r - floor(r), the weights (1 - f, f) for bilinear (off = floor(r)) or torch's cubic convolution
+# with A = -0.75 (off = floor(r) - 1), each rounded as floor(w 2^14 + 1/2), the deficit to exactly 2^14 added to the tap of largest magnitude (the first of equals).
+# Tap j reads source index clamp(q + off[p] + j, 0, n - 1): the edge sample repeats.  The weights are evaluated in exact fractions, so no float rounding takes part.
+CHROMA_METHODS = {'nearest': 1, 'bilinear': 2, 'bicubic': 4}          # method -> taps
+CHROMA_LOCS = ('center', 'left')
+CHROMA_ONE = 1 << 14
+
+
+def chromaTable(method, scale, loc='center'):
+    """(off[scale], coef[scale][taps]) of one axis, as lists of Python ints; ValueError names what is unknown."""
+    from fractions import Fraction as Fr
+    from math import floor
+    if method not in CHROMA_METHODS:
+        raise ValueError('chroma "{}" is not supported ({})'.format(method, ', '.join(CHROMA_METHODS)))
+    if loc not in CHROMA_LOCS:
+        raise ValueError('chromaLoc "{}" is not supported ({})'.format(loc, ', '.join(CHROMA_LOCS)))
+    if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 16:
+        raise ValueError('chroma: scale must be 1..16, got {!r}'.format(scale))
+    A = Fr(-3, 4)
+    inner = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1                  # |x| <= 1   (cubic1 of misc_kernels.hip)
+    outer = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A           # 1 < |x| < 2   (cubic2)
+    off, coef = [], []
+    for p in range(scale):
+        r = Fr(p, scale) if loc == 'left' else Fr(2 * p + 1 - scale, 2 * scale)
+        if method == 'nearest':
+            off.append(floor(r + Fr(1, 2)))
+            coef.append([CHROMA_ONE])
+            continue
+        f = r - floor(r)
+        wts = [1 - f, f] if method == 'bilinear' else [outer(f + 1), inner(f), inner(1 - f), outer(2 - f)]
+        c = [floor(x * CHROMA_ONE + Fr(1, 2)) for x in wts]
+        c[max(range(len(c)), key=lambda j: (abs(c[j]), -j))] += CHROMA_ONE - sum(c)
+        off.append(floor(r) - (1 if method == 'bicubic' else 0))
+        coef.append(c)
+    return off, coef
+
+
+def _chromaAxis(x, off, coef, scale, axis):
+    """One pass over `axis` of an int64 array: out[o] = sum_j coef[p][j] * x[clamp(q + off[p] + j)]."""
+    n = x.shape[axis]
+    o = np.arange(n * scale)
+    q, p = o // scale, o % scale
+    off, coef = np.asarray(off, np.int64), np.asarray(coef, np.int64)
+    shape = [1] * x.ndim
+    shape[axis] = n * scale
+    out = 0
+    for j in range(coef.shape[1]):
+        out = out + np.take(x, np.clip(q + off[p] + j, 0, n - 1), axis=axis) * coef[p, j].reshape(shape)
+    return out
+
+
+def resampleChroma(C, srcFmt, dstFmt, scale, method, loc='center'):
+    """C = the (2, h, w) codes of a frame's chroma planes at srcFmt's depth Ds (high bits are not masked) -> (2, h scale, w scale) codes at dstFmt's depth Dd, uint8
+    for Dd = 8, else little-endian uint16.  Horizontal pass t = sum_j cx[p][j] code (fits int32 for any uint16 code: sum |c| <= 32767), vertical pass
+    v = sum_i cy[p'][i] t_i, sample = clamp((v + 2^27) >> 28, 0, 2^Ds - 1), then << (Dd - Ds) or >> (Ds - Dd) -- what code 2^-Ds times 2^Dd, truncated, does to a code."""
+    for fmt in (srcFmt, dstFmt):
+        if fmt not in FORMATS:
+            raise ValueError('pixFmt "{}" is not supported ({})'.format(fmt, ', '.join(FORMATS)))
+    Ds, Dd = FORMATS[srcFmt], FORMATS[dstFmt]
+    x = np.asarray(C)
+    if x.ndim != 3 or x.shape[0] != 2 or x.dtype.kind not in 'ui':
+        raise ValueError('resampleChroma: the (2, h, w) integer codes of Cb and Cr expected, got {} {}'.format(x.dtype, x.shape))
+    x = x.astype(np.int64)
+    ox, cx = chromaTable(method, scale, loc)
+    oy, cy = chromaTable(method, scale, 'center')
+    t = _chromaAxis(x, ox, cx, scale, 2)
+    assert np.abs(t).max() < 1 << 31
+    v = _chromaAxis(t, oy, cy, scale, 1)
+    s = np.clip((v + (1 << 27)) >> 28, 0, (1 << Ds) - 1)
+    s = s << (Dd - Ds) if Dd >= Ds else s >> (Ds - Dd)
+    return s.astype(np.uint8 if Dd == 8 else np.dtype('<u2'))

@@ -18,6 +18,10 @@ With {'op': 'buffer', 'pixFmt': 'yuv420p' | 'yuv420p10le' | 'yuv420p12le' | 'yuv
 frames as they are and run the chain on Y' and on Cb / Cr as two images.
 
 `genFrameStream(.., reuse=True)` keeps each step's tile pool from the previous frame and runs only the tiles whose input changed, bit for bit.
+
+With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on such a source step the chain is luma-only: the net runs on Y' alone and Cb / Cr are brought to the output's size
+by a fixed integer resampling filter (pixfmt.resampleChroma, moe_chroma_resample); `genFrameStream(.., views=True)` hands the finished frames out as read-only views of
+the ring's pinned buffers instead of copies.
 """
 import math
 import time
@@ -25,7 +29,7 @@ from functools import reduce
 
 from . import _lib, pixfmt, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
+from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
                            toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -56,7 +60,8 @@ def _outputFormat(steps):
 # takes place anywhere.
 def _planeFormats(steps, width=None, height=None):
     """(source pixFmt, output pixFmt) of a step list whose source is planar, or None for every other list.  Everything such a chain refuses is refused here, as a
-    ValueError before any model is loaded: an unknown format, a resize step, matrix / order on the output step (there is no conversion they could steer), an odd size."""
+    ValueError before any model is loaded: an unknown format, a resize step, matrix / order on the output step (there is no conversion they could steer), an odd size,
+    and what _planeChroma refuses of the source step's 'chroma' / 'chromaLoc' keys."""
     if not steps or steps[0].get('op') != 'buffer' or steps[0].get('pixFmt') is None:
         return None
     src = dst = steps[0]['pixFmt']
@@ -74,7 +79,30 @@ def _planeFormats(steps, width=None, height=None):
                     raise ValueError('output: pixFmt "{}" is not supported ({})'.format(dst, ', '.join(pixfmt.FORMATS)))
     if width is not None:
         pixfmt.planeShapes(src, width, height)
+    _planeChroma(steps)
     return src, dst
+
+
+def _planeChroma(steps):
+    """(method, loc) of a luma-only chain -- the source step's 'chroma' is 'nearest', 'bilinear' or 'bicubic': the net runs on Y' alone and Cb / Cr are resampled by
+    pixfmt.resampleChroma -- or None for 'chroma': 'net' (the default: Cb / Cr go through the net as a second image).  ValueError for an unknown value of either key,
+    'chromaLoc' beside 'net' (the net path has no siting to choose) and a chain whose total scale exceeds the filter's 16."""
+    method, loc = steps[0].get('chroma', 'net'), steps[0].get('chromaLoc')
+    if method != 'net' and method not in pixfmt.CHROMA_METHODS:
+        raise ValueError('buffer: chroma "{}" is not supported (net, {})'.format(method, ', '.join(pixfmt.CHROMA_METHODS)))
+    if loc is not None and loc not in pixfmt.CHROMA_LOCS:
+        raise ValueError('buffer: chromaLoc "{}" is not supported ({})'.format(loc, ', '.join(pixfmt.CHROMA_LOCS)))
+    if method == 'net':
+        if loc is not None:
+            raise ValueError("buffer: 'chromaLoc' does not apply to 'chroma': 'net' (the planes go through the net, no filter is sited)")
+        return None
+    scale = 1
+    for s in steps[1:]:
+        if s.get('op') == 'SR':
+            scale *= int(s.get('scale', 1))
+    if scale > 16:
+        raise ValueError('buffer: chroma "{}" resamples by 16 at most, the chain scales by {}'.format(method, scale))
+    return method, loc or 'center'
 
 
 def _planeChain(steps, fuse, rsteps=None):
@@ -120,6 +148,7 @@ def _genProcessPlanes(steps, fmts):
     src, dst = fmts
     funcs, nodes, scale, _ = _planeChain(steps, False)
     quantise = toPlanes(pixfmt.FORMATS[dst])
+    chroma, resamplers = _planeChroma(steps), {}
 
     def run(frame):
         raw, height, width = frame
@@ -127,12 +156,18 @@ def _genProcessPlanes(steps, fmts):
         if len(raw) != pixfmt.frameBytes(src, width, height):
             raise ValueError('short frame: {} of {} bytes'.format(len(raw), pixfmt.frameBytes(src, width, height)))
         dev = torch.device(config.device())
-        y, c = fromPlanes(src, width, height, config.dtype())(torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev))
+        rawDev = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
+        y, c = fromPlanes(src, width, height, config.dtype())(rawDev)
         w, h = width * scale, height * scale
         cb = pixfmt.planeOffsets(dst, w, h)[1]
         out = torch.empty((pixfmt.frameBytes(dst, w, h),), dtype=torch.uint8, device=dev)
         quantise(reduce(apply, funcs, y), out[:cb])
-        quantise(reduce(apply, funcs, c), out[cb:])
+        if chroma:          # luma-only: Cb / Cr from the raw frame's codes, by the integer filter
+            if (width, height) not in resamplers:
+                resamplers[(width, height)] = resampleChroma(src, dst, width, height, scale, *chroma)
+            resamplers[(width, height)](rawDev, out)
+        else:
+            quantise(reduce(apply, funcs, c), out[cb:])
         return out.cpu().numpy().tobytes()
     return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
 
@@ -253,6 +288,11 @@ def _reuseDN(o):
 def _checkReuse(reuse):
     if not isinstance(reuse, bool):
         raise ValueError('frame stream: reuse must be True or False, got {!r}'.format(reuse))
+
+
+def _checkViews(views):
+    if not isinstance(views, bool):
+        raise ValueError('frame stream: views must be True or False, got {!r}'.format(views))
 
 
 class _ReuseState(object):
@@ -388,9 +428,9 @@ class _DeviceBackend(object):
     edge on torch's current stream; download = async D2H into the slot's pinned buffer on a third stream.  timing: the events take timestamps and `stats` sums the
     milliseconds per stage over the collected frames (tools/frame_stream_bench.py)."""
 
-    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None, reuse=None):
+    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None, reuse=None, views=False):
         import torch
-        self.torch, self.funcs, self.edge, self.bitDepth, self.timing, self.reuse = torch, funcs, edge, bitDepth, timing, reuse
+        self.torch, self.funcs, self.edge, self.bitDepth, self.timing, self.reuse, self.views = torch, funcs, edge, bitDepth, timing, reuse, views
         self.dev = torch.device(config.device())
         if self.dev.type != 'cuda':
             raise _lib.EngineError('frame stream: needs a HIP device (moephoto_amd has no CPU path)')
@@ -405,6 +445,8 @@ class _DeviceBackend(object):
             s.update(out=torch.empty(oshape, dtype=o_dt, device=self.dev), pin_out=torch.empty(oshape, dtype=o_dt, pin_memory=True))
             s['in_bytes'] = s['pin_in'].numpy().view('uint8').reshape(-1)
             s['out_np'] = s['pin_out'].numpy()
+            if views:          # the slot's pinned output as the caller sees it: flat bytes, read-only (the ring writes it through the tensor)
+                s['out_view'] = memoryview(s['out_np'].view('uint8').reshape(-1)).toreadonly()
             if timing:
                 s.update(t_up=self.event(), t_comp=self.event(), t_down=self.event())
             self.slots.append(s)
@@ -509,7 +551,7 @@ class _DeviceBackend(object):
             for name, key in (('up', 'h2d_ms'), ('comp', 'compute_ms'), ('down', 'd2h_ms')):      # (the download is over, so is everything before it)
                 self.stats[key] += s['t_' + name].elapsed_time(s['e_' + name])
         t0 = time.perf_counter()
-        buf = s['out_np'].tobytes()
+        buf = s['out_view'] if self.views else s['out_np'].tobytes()          # (a view: valid until the next push / flush / close, see genFrameStream)
         self.stats['tobytes_ms'] += (time.perf_counter() - t0) * 1e3
         self.stats['frames'] += 1
         return buf
@@ -527,28 +569,35 @@ class _DeviceBackend(object):
 
 class _PlanesBackend(_DeviceBackend):
     """The same three queues for a chain on the decoder's planes: a slot's input is the flat planar frame (pinned and on the device), its images are Y (1, H, W) and
-    C (2, H / 2, W / 2), its output the flat planar frame of outBytes.  compute = moe_planes_to_float, the chain on Y and then on C, and edge(y, c, out)."""
+    C (2, H / 2, W / 2), its output the flat planar frame of outBytes.  compute = moe_planes_to_float, the chain on Y and then on C, and edge(y, c, out).
+    lumaOnly: the chain runs on Y alone -- no C image is walked and the change map covers Y only; edge(y, raw, out) writes the chroma planes from the raw frame (every
+    frame, reuse or not: the output frame is the slot's).  moe_planes_to_float still fills one C image, shared by the slots and read by nobody (it refuses a NULL)."""
 
-    def __init__(self, funcs, edge, fmt, width, height, depth, timing, outBytes, reuse=None):
-        self.convert, self.inBytes = fromPlanes(fmt, width, height, config.dtype()), pixfmt.frameBytes(fmt, width, height)
-        super().__init__(funcs, edge, 8 if pixfmt.FORMATS[fmt] == 8 else 16, width, height, None, depth, timing, outBytes, reuse)
+    def __init__(self, funcs, edge, fmt, width, height, depth, timing, outBytes, reuse=None, views=False, lumaOnly=False):
+        self.convert, self.inBytes, self.lumaOnly = fromPlanes(fmt, width, height, config.dtype()), pixfmt.frameBytes(fmt, width, height), lumaOnly
+        self.unusedC = None
+        super().__init__(funcs, edge, 8 if pixfmt.FORMATS[fmt] == 8 else 16, width, height, None, depth, timing, outBytes, reuse, views)
 
     def _maps(self):
-        return [_reuse.cells(self.H, self.W), _reuse.cells(self.H // 2, self.W // 2)]
+        return [_reuse.cells(self.H, self.W)] + ([] if self.lumaOnly else [_reuse.cells(self.H // 2, self.W // 2)])
 
     def _detect(self, s, stream):
         """The Y plane is one matrix, Cb and Cr are two matrices folded into one map: a cell is 16 x 16 pixels of the image the chain sees."""
         es = 1 if self.bitDepth <= 8 else 2
         L, raw, prev, m, ny = _lib.lib(), s['raw'].data_ptr(), self.prev.data_ptr(), self.map_dev.data_ptr(), self.H * self.W * es
         _lib.check(L.moe_changed_blocks(raw, prev, 1, self.H, self.W * es, _reuse.CELL, _reuse.CELL * es, m, self.dev.index or 0, stream.cuda_stream))
+        if self.lumaOnly:
+            return
         _lib.check(L.moe_changed_blocks(raw + ny, prev + ny, 2, self.H // 2, self.W // 2 * es, _reuse.CELL, _reuse.CELL * es, m + self.maps[0][0] * self.maps[0][1],
                                         self.dev.index or 0, stream.cuda_stream))
 
     def _slot(self, in_dt):
         torch = self.torch
+        if self.lumaOnly and self.unusedC is None:
+            self.unusedC = torch.empty((2, self.H // 2, self.W // 2), dtype=config.dtype(), device=self.dev)
         return dict(pin_in=torch.empty((self.inBytes,), dtype=torch.uint8, pin_memory=True), raw=torch.empty((self.inBytes,), dtype=torch.uint8, device=self.dev),
                     y=torch.empty((1, self.H, self.W), dtype=config.dtype(), device=self.dev),
-                    c=torch.empty((2, self.H // 2, self.W // 2), dtype=config.dtype(), device=self.dev))
+                    c=self.unusedC if self.lumaOnly else torch.empty((2, self.H // 2, self.W // 2), dtype=config.dtype(), device=self.dev))
 
     def compute(self, slot, wait, record):
         s = self.slots[slot]
@@ -558,6 +607,13 @@ class _PlanesBackend(_DeviceBackend):
 
         def work(stream):
             y, c = self.convert(s['raw'], s['y'], s['c'])
+            if self.lumaOnly:
+                if R is None:
+                    self.edge(reduce(apply, self.funcs, y), s['raw'], s['out'])
+                    return
+                y, ry = R.walk('y', y, changed[0])
+                self.edge(y, s['raw'], s['out'], R.edgeCallback('y', ry))
+                return
             if R is None:
                 self.edge(reduce(apply, self.funcs, y), reduce(apply, self.funcs, c), s['out'])
                 return
@@ -569,11 +625,13 @@ class _PlanesBackend(_DeviceBackend):
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
 
-def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False):
+def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False):
     src, dst = fmts
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     _checkReuse(reuse)
+    _checkViews(views)
+    chroma = _planeChroma(steps)
     rsteps = []
     funcs, nodes, scale, last = _planeChain(steps, True, rsteps)
     w, h = int(width) * scale, int(height) * scale
@@ -588,8 +646,14 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
     def edge(y, c, out, reuseY=None, reuseC=None):
         into(y, out[:cb], reuseY)
         into(c, out[cb:], reuseC)
+    if chroma:          # luma-only: the Y edge as above, then one moe_chroma_resample from the raw frame's chroma codes into the frame's Cb / Cr planes, on the compute stream
+        resample = resampleChroma(src, dst, int(width), int(height), scale, *chroma)
+
+        def edge(y, raw, out, reuseY=None):
+            into(y, out[:cb], reuseY)
+            resample(raw, out)
     state = _ReuseState(rsteps, bool(last)) if reuse else None
-    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h), state)
+    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h), state, views, bool(chroma))
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
     stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
@@ -614,7 +678,7 @@ def _quantiseInto(bitDepth):
     return f
 
 
-def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False):
+def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, views=False):
     """genProcess for a video source as a stream: `steps` as genProcess takes them, steps[0] = {'op': 'buffer', 'bitDepth': 8 | 16}; frames are width x height x 3.
     Returns a FrameStream: push(raw) -> list of finished frames' bytes (input order; [] for an empty buffer), flush(), close(), nodes.  The last compute step decides
     the output edge, named by the stream's `edge`: 'crop' -- an SR without ensemble or a DN of strength 1 folds its tiles straight into the encoder's samples
@@ -627,17 +691,24 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False):
     folds write straight into the frame -- or 'quantise' (toPlanes); no resize step, no matrix / order (ValueError before a model is loaded).
     reuse=True (either source kind, every edge): the stream keeps each step's tile pool from the previous frame and runs only the tiles whose input changed bit for
     bit -- frames shown twice, static shots, slides; the finished frames are the same bytes.  `stream.reuse` then holds the counters (tiles
-    planned / run per step and image, plane-tile pixels planned / run over the stream; None without reuse)."""
+    planned / run per step and image, plane-tile pixels planned / run over the stream; None without reuse).
+    With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on a planar source step (and 'chromaLoc': 'center' | 'left', the horizontal siting) the chain is luma-only: it
+    runs on Y' exactly as above and the frame's Cb / Cr planes are written by one moe_chroma_resample from the source's chroma codes (pixfmt.resampleChroma: integers,
+    byte for byte); 'chroma': 'net', the default, is the two-image form.  With reuse the change map and `stream.reuse` cover Y only.
+    views=True: push / flush return read-only memoryviews (flat, format 'B') of the ring's pinned output buffers instead of bytes -- no copy is made.  A view is valid
+    until the NEXT push, flush or close on this stream: frame k's slot is next written by the download that push(k + depth) enqueues, and that push is the first call
+    after the one that returned frame k.  Whoever needs a frame for longer copies it (bytes(view)); stats['tobytes_ms'] then reads about 0."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
     planar = _planeFormats(steps, width, height)
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
-        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse)
+        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views)
     bitDepth = int(steps[0].get('bitDepth', 16))
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
     _checkReuse(reuse)                   # (likewise)
+    _checkViews(views)                   # (likewise)
     yuvOf = toYuv(*yuv) if yuv else None
     work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
     for opt in work:
@@ -684,7 +755,7 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False):
     if edge is None:
         edge = yuvOf or _quantiseInto(bitDepth)
     state = _ReuseState(rsteps, tiledEdge) if reuse else None
-    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state)
+    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state, views)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
     stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
@@ -692,7 +763,9 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False):
 
 def runFramesStreamed(stream, read, write, start=0, stop=-1):
     """runFrames over a FrameStream: the same frames reach `write` in the same order and the same count is returned; they arrive up to depth - 1 reads later.  A short
-    frame raises the same ValueError after every frame already pushed has been written."""
+    frame raises the same ValueError after every frame already pushed has been written.  A stream built with views=True hands `write` read-only memoryviews of the
+    ring's pinned buffers: each is valid only until the next push / flush on the stream, and every frame is written here before the next push -- a `write` that keeps a
+    frame beyond its own call must copy it."""
     i = n = 0
 
     def hand(bufs):
