@@ -346,6 +346,26 @@ int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int
 int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
                         const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream);
 
+/* Planes of codes brought to a FITTED size: a rational (any n -> m) integer polyphase filter per axis, antialiasing where the axis shrinks -- the definition is
+ * moephoto_amd/pixfmt.py (fitTable, fitPlanes) and the device matches it byte for byte.  A handle holds one geometry: `planes` (1 .. 4) planes of h x w codes at
+ * src_depth -> as many planes of oh x ow at dst_depth (uint8 at depth 8, little-endian uint16 at 10, 12, 16; high bits are not masked), planes one after the other.
+ * cx / ox and cy / oy are HOST tables, per axis m x taps 14-bit coefficients and m offsets (m = ow or oh): output index o reads the source samples
+ * clamp(off[o] + j, 0, n - 1), j < taps (1 .. 16).  Row pass in int32, column pass in int64, sample = clamp((v + 2^27) >> 28, 0, 2^src_depth - 1), then
+ * << (dst_depth - src_depth) or >> (src_depth - dst_depth).  Refused (MOE_EINVAL, before any device call): a NULL pointer, a depth outside {8, 10, 12, 16}, planes outside
+ * 1 .. 4, a size below 1 or beyond int, taps outside 1 .. 16, a coefficient row that does not sum to 2^14 or whose sum of magnitudes exceeds 32767 (so the int32 row pass
+ * holds for any uint16 code), an offset whose taps do not reach the plane (off + taps - 1 < 0 or off > n - 1), offsets that decrease along the axis, and offsets that
+ * step so far that the source window of the smallest output tile does not fit the kernel's LDS.  The tables are then uploaded to `device` (synchronously) and stay
+ * there until the handle is destroyed. */
+typedef struct moe_fit moe_fit;
+int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
+                   int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out);
+/* One resample with the handle's geometry, asynchronous on `stream`.  src / dst: any 2-byte aligned address (any address at depth 8) -- the Cb plane of a frame starts
+ * wherever its Y plane ends.  Refused: a NULL pointer, a misaligned one. */
+int moe_fit_run(const moe_fit* fit, const void* src, void* dst, void* stream);
+/* info[0 .. 4) = the kernel's output tile (width, height), the LDS bytes of a workgroup, the planes. */
+int moe_fit_info(const moe_fit* fit, int64_t info[4]);
+void moe_fit_destroy(moe_fit* fit);
+
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
  * alpha, strength, bits, dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */

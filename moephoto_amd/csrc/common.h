@@ -515,6 +515,12 @@ void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_
 // (relative to q = o / scale) with the 14-bit coefficients coef[p][0 .. TAPS) (moephoto_amd/pixfmt.py: chromaTable)
 struct ChromaTab { short coef[16][4]; signed char off[16]; };
 void launch_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps, const ChromaTab& tx, const ChromaTab& ty, hipStream_t s);
+// fit.hip: one axis of moe_fit_run's rational polyphase filter, in DEVICE memory: output index o reads `taps` source samples from off[o] on with the 14-bit coefficients
+// coef[o * FIT_TAPS + 0 .. taps) (rows of FIT_TAPS, 32 bytes, the base 16-byte aligned; moephoto_amd/pixfmt.py: fitTable).  A workgroup's output tile is FIT_TW x th.
+constexpr int FIT_TW = 128, FIT_TAPS = 16;
+constexpr size_t FIT_LDS_BUDGET = 80 * 1024;          // per workgroup: two of them share a CU's 160 KiB
+struct FitAxis { const int* off; const short* coef; int taps; };
+void launch_fit(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int oh, int ow, int planes, int th, size_t lds, const FitAxis& ax, const FitAxis& ay, hipStream_t s);
 // (C, H, W) -> (C, h, w); mode 0 nearest, 1 bilinear, 2 bicubic (torch F.interpolate semantics, align_corners = False)
 void launch_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, hipStream_t s);
 // max |a - b| over n floats, atomically folded into *out as the bits of a non-negative float (zero it first)

@@ -14,6 +14,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
                                        the decoder's own 4:2:0 planes, Y' as a (1, H, W) image and Cb / Cr as a (2, H / 2, W / 2) image (pixfmt.toPlanes / fromPlanes)
   resampleChroma                       (no counterpart: the reference's pipe is RGB) -> moe_chroma_resample: the chroma planes of a luma-only chain, by the integer
                                        polyphase filter of pixfmt.resampleChroma
+  fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
+                                       brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
   readFile / writeFile                 :265-302         (PIL, host)
 
 There is no CPU path: models must be moephoto_amd.models.EngineModule instances on a HIP device.
@@ -796,6 +798,77 @@ def resampleChroma(srcFmt, dstFmt, w, h, scale, method, loc='center'):
                                                   raw_dev.device.index or 0, cur.cuda_stream))
         raw_dev.record_stream(cur)
         return out
+    return f
+
+
+_fitTabs = {}          # (method, n, m, loc) -> (taps, coefficients as c_int16[m * taps], offsets as c_int32[m]): built once per size (exact fractions: seconds at 8K)
+
+
+def fitTables(method, n, m, loc='center'):
+    """pixfmt.fitTable(method, n, m, loc) as moe_fit_create takes one axis: (taps, c_int16[m * taps], c_int32[m]), cached per size.  One normalisation: an offset
+    beyond the plane's last sample -- 'nearest' with 'left' when the axis grows: floor(c + 1/2) = n for its last outputs -- is passed as n - 1, the sample the
+    definition's own clamp reads; moe_fit_create refuses a row that does not reach the plane."""
+    key = (method, n, m, loc)
+    if key not in _fitTabs:
+        off, coef = pixfmt.fitTable(method, n, m, loc)
+        taps = len(coef[0])
+        off = [min(o, n - 1) for o in off]
+        if len(_fitTabs) >= 32:
+            _fitTabs.clear()
+        _fitTabs[key] = (taps, (ctypes.c_int16 * (m * taps))(*[c for row in coef for c in row]), (ctypes.c_int32 * m)(*off))
+    return _fitTabs[key]
+
+
+class _FitHandle(object):
+    """A moe_fit handle: the geometry and the tables on the device, freed with the object."""
+
+    def __init__(self, planes, srcDepth, h, w, dstDepth, oh, ow, tx, ty, device):
+        self._h = ctypes.c_void_p()
+        _lib.check(_lib.lib().moe_fit_create(planes, srcDepth, h, w, dstDepth, oh, ow, tx[0], tx[1], tx[2], ty[0], ty[1], ty[2], device, ctypes.byref(self._h)))
+
+    def info(self):
+        """dict(tile=(width, height), lds=bytes per workgroup, planes=..) of the kernel's launch."""
+        v = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.lib().moe_fit_info(self._h, v))
+        return dict(tile=(int(v[0]), int(v[1])), lds=int(v[2]), planes=int(v[3]))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h and _lib._lib is not None:
+            _lib._lib.moe_fit_destroy(h)
+
+
+def fitPlanes(srcDepth, dstDepth, planes, h, w, oh, ow, method, loc='center'):
+    """Planes of codes brought to a fitted size (moe_fit_create / moe_fit_run; the definition: pixfmt.fitPlanes): f(src_dev, out) reads `planes` planes of h x w codes
+    at srcDepth from src_dev (a flat contiguous uint8 device tensor of exactly those bytes: a frame's Y plane, its two chroma planes, or a view of them) and writes as
+    many planes of oh x ow at dstDepth into out, likewise.  The tables are pixfmt.fitTable's, cached per size: `loc` sites the horizontal axis, the vertical one is
+    always 'center'.  The handle (tables on the device) is made at the first call, for that call's device, and lives as long as f; f.info() describes its launch."""
+    for d in (srcDepth, dstDepth):
+        if d not in pixfmt.FORMATS.values():
+            raise ValueError('fitPlanes: depth must be one of {}, got {!r}'.format(sorted(pixfmt.FORMATS.values()), d))
+    if not isinstance(planes, int) or isinstance(planes, bool) or not 1 <= planes <= 4:
+        raise ValueError('fitPlanes: planes must be 1..4, got {!r}'.format(planes))
+    h, w, oh, ow = int(h), int(w), int(oh), int(ow)
+    tx, ty = fitTables(method, w, ow, loc), fitTables(method, h, oh, 'center')          # (ValueError for what fitTable refuses)
+    n_in, n_out = planes * h * w * (1 if srcDepth == 8 else 2), planes * oh * ow * (1 if dstDepth == 8 else 2)
+    handles = {}
+
+    def handle(device):
+        if device not in handles:
+            handles[device] = _FitHandle(planes, srcDepth, h, w, dstDepth, oh, ow, tx, ty, device.index or 0)
+        return handles[device]
+
+    def f(src_dev, out):
+        if src_dev.device.type != 'cuda' or out.device != src_dev.device:
+            raise _lib.EngineError('fitPlanes: both buffers must live on one HIP device (moephoto_amd has no CPU path)')
+        for t, n in ((src_dev, n_in), (out, n_out)):
+            if tuple(t.shape) != (n,) or t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError('fitPlanes: a flat contiguous uint8 tensor of {} bytes expected, got {} {}'.format(n, t.dtype, tuple(t.shape)))
+        cur = torch.cuda.current_stream(src_dev.device)
+        _lib.check(_lib.lib().moe_fit_run(handle(src_dev.device)._h, src_dev.data_ptr(), out.data_ptr(), cur.cuda_stream))
+        src_dev.record_stream(cur)
+        return out
+    f.info = lambda device=None: handle(device if device is not None else torch.device(config.device())).info()
     return f
 
 

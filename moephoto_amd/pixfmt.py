@@ -219,3 +219,111 @@ def resampleChroma(C, srcFmt, dstFmt, scale, method, loc='center'):
     s = np.clip((v + (1 << 27)) >> 28, 0, (1 << Ds) - 1)
     s = s << (Dd - Ds) if Dd >= Ds else s >> (Ds - Dd)
     return s.astype(np.uint8 if Dd == 8 else np.dtype('<u2'))
+
+
+# ---- fitted sizes: a rational (any n -> m) integer polyphase filter -------------------------------------------------------------------------------
+# A planar chain whose output step names a size ({'op': 'output', 'width': W, 'height': H, 'fit': 'bicubic'}) brings each plane from the size the chain gives to the
+# size asked for -- what the device kernel (resize_kernel_fit, moe_fit_create / moe_fit_run) is held to, byte for byte.  The library builds no table of its own:
+# fitTable is the only definition.
+#
+# One axis from n to m samples, s = n / m, f = max(1, s): the filter is stretched only when the axis shrinks (then it is the antialiasing filter).  Output o is
+# centred on the source coordinate
+#     'center'   c = ((2 o + 1) s - 1) / 2
+#     'left'     c = o s                                 chroma co-sited with the even luma columns; the horizontal axis only
+# nearest: one tap, off = floor(c + 1/2), coefficient 2^14, no stretch.  Otherwise R = 1 (bilinear: the triangle) or R = 2 (bicubic: chromaTable's cubic convolution,
+# A = -3/4), taps i = floor(c - R f) + 1 .. ceil(c + R f) - 1 with w_i = k((i - c) / f) / sum_j w_j, coefficients floor(w_i 2^14 + 1/2), the deficit to exactly 2^14
+# added to the tap of largest magnitude (the first of equals).  off[o] is the first tap, T the longest row of the axis (shorter rows end in zeros); tap j reads source
+# index clamp(off[o] + j, 0, n - 1).  At n / m <= 4, T <= 8 (bilinear) and T <= 16 (bicubic) and sum |c| <= 22 522.  Everything in exact fractions.
+FIT_MAX_DOWN, FIT_MAX_UP = 4, 16
+
+_fitCache = {}
+
+
+def _fitKernel(method):
+    from fractions import Fraction as Fr
+    if method == 'bilinear':
+        return 1, lambda x: max(1 - abs(x), Fr(0))
+    A = Fr(-3, 4)
+    inner = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
+    outer = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+
+    def cubic(x):
+        x = abs(x)
+        return inner(x) if x <= 1 else outer(x) if x < 2 else Fr(0)
+    return 2, cubic
+
+
+def fitTable(method, n, m, loc='center'):
+    """(off[m], coef[m][T]) of one axis resampled from n to m samples, as lists of Python ints; ValueError names what is refused."""
+    from fractions import Fraction as Fr
+    from math import ceil, floor, gcd
+    if method not in CHROMA_METHODS:
+        raise ValueError('fit "{}" is not supported ({})'.format(method, ', '.join(CHROMA_METHODS)))
+    if loc not in CHROMA_LOCS:
+        raise ValueError('fit: loc "{}" is not supported ({})'.format(loc, ', '.join(CHROMA_LOCS)))
+    for v in (n, m):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+            raise ValueError('fit: sizes must be positive ints, got {!r} -> {!r}'.format(n, m))
+    if n > FIT_MAX_DOWN * m:
+        raise ValueError('fit: {} -> {} shrinks by more than {}'.format(n, m, FIT_MAX_DOWN))
+    if m > FIT_MAX_UP * n:
+        raise ValueError('fit: {} -> {} enlarges by more than {}'.format(n, m, FIT_MAX_UP))
+    key = (method, n, m, loc)
+    if key not in _fitCache:
+        s = Fr(n, m)
+        f = max(Fr(1), s)
+        g = gcd(n, m)
+        period, step = m // g, n // g          # c(o + period) = c(o) + step: only `period` rows differ
+        rows = []
+        for o in range(min(m, period)):
+            c = Fr(2 * o + 1) * s / 2 - Fr(1, 2) if loc == 'center' else o * s
+            if method == 'nearest':
+                rows.append((floor(c + Fr(1, 2)), [CHROMA_ONE]))
+                continue
+            R, k = _fitKernel(method)
+            first, last = floor(c - R * f) + 1, ceil(c + R * f) - 1
+            w = [k((i - c) / f) for i in range(first, last + 1)]
+            tot = sum(w)
+            q = [floor(x / tot * CHROMA_ONE + Fr(1, 2)) for x in w]
+            q[max(range(len(q)), key=lambda j: (abs(q[j]), -j))] += CHROMA_ONE - sum(q)
+            rows.append((first, q))
+        T = max(len(q) for _, q in rows)
+        off = tuple(rows[o % period][0] + (o // period) * step for o in range(m))
+        coef = tuple(tuple(rows[o % period][1]) + (0,) * (T - len(rows[o % period][1])) for o in range(m))
+        if len(_fitCache) >= 64:
+            _fitCache.clear()
+        _fitCache[key] = (off, coef)
+    off, coef = _fitCache[key]
+    return list(off), [list(r) for r in coef]
+
+
+def _fitAxis(x, off, coef, axis):
+    """One pass over `axis` of an integer array: out[o] = sum_j coef[o][j] * x[clamp(off[o] + j)]."""
+    n = x.shape[axis]
+    off, coef = np.asarray(off, np.int64), np.asarray(coef, np.int64)
+    shape = [1] * x.ndim
+    shape[axis] = len(off)
+    out = 0
+    for j in range(coef.shape[1]):
+        out = out + np.take(x, np.clip(off + j, 0, n - 1), axis=axis) * coef[:, j].reshape(shape)
+    return out
+
+
+def fitPlanes(P, srcDepth, dstDepth, oh, ow, method, loc='center'):
+    """P = the (C, h, w) integer codes of C planes at depth srcDepth (high bits are not masked) -> (C, oh, ow) codes at dstDepth, uint8 for 8, else little-endian
+    uint16.  resampleChroma's arithmetic to the letter: horizontal pass in int32 (`loc` sites this axis only), vertical pass in int64,
+    sample = clamp((v + 2^27) >> 28, 0, 2^Ds - 1), then << (Dd - Ds) or >> (Ds - Dd)."""
+    for d in (srcDepth, dstDepth):
+        if d not in FORMATS.values():
+            raise ValueError('fitPlanes: depth must be one of {}, got {!r}'.format(sorted(FORMATS.values()), d))
+    x = np.asarray(P)
+    if x.ndim != 3 or x.shape[0] < 1 or x.dtype.kind not in 'ui':
+        raise ValueError('fitPlanes: the (C, h, w) integer codes of C planes expected, got {} {}'.format(x.dtype, x.shape))
+    ox, cx = fitTable(method, int(x.shape[2]), ow, loc)
+    oy, cy = fitTable(method, int(x.shape[1]), oh, 'center')
+    t = _fitAxis(x.astype(np.int32), ox, cx, 2)
+    assert t.dtype == np.int64 and np.abs(t).max() < 1 << 31          # (summed in int64 here; the bound is what lets the device sum in int32)
+    v = _fitAxis(t, oy, cy, 1)
+    s = np.clip((v + (1 << 27)) >> 28, 0, (1 << srcDepth) - 1)
+    s = s << (dstDepth - srcDepth) if dstDepth >= srcDepth else s >> (srcDepth - dstDepth)
+    return s.astype(np.uint8 if dstDepth == 8 else np.dtype('<u2'))

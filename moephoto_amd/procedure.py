@@ -22,6 +22,9 @@ frames as they are and run the chain on Y' and on Cb / Cr as two images (DESIGN.
 With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on such a source step the chain is luma-only: the net runs on Y' alone and Cb / Cr are brought to the output's size
 by a fixed integer resampling filter (pixfmt.resampleChroma, moe_chroma_resample); `genFrameStream(.., views=True)` hands the finished frames out as read-only views of
 the ring's pinned buffers instead of copies.
+
+With {'op': 'output', 'width': W, 'height': H, 'fit': 'bicubic'} on such a chain both builders deliver W x H frames: the planes the chain gives are brought to the size
+asked for by a rational integer polyphase filter that antialiases where it shrinks (pixfmt.fitPlanes, moe_fit_create / moe_fit_run).
 """
 import math
 import time
@@ -29,7 +32,7 @@ from functools import reduce
 
 from . import _lib, pixfmt, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fromPlanes, identity, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
+from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fitPlanes, fromPlanes, identity, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
                            toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -61,7 +64,7 @@ def _outputFormat(steps):
 def _planeFormats(steps, width=None, height=None):
     """(source pixFmt, output pixFmt) of a step list whose source is planar, or None for every other list.  Everything such a chain refuses is refused here, as a
     ValueError before any model is loaded: an unknown format, a resize step, matrix / order on the output step (there is no conversion they could steer), an odd size,
-    and what _planeChroma refuses of the source step's 'chroma' / 'chromaLoc' keys."""
+    what _planeChroma refuses of the source step's 'chroma' / 'chromaLoc' keys and what _planeFit refuses of the output step's 'width' / 'height' / 'fit'."""
     if not steps or steps[0].get('op') != 'buffer' or steps[0].get('pixFmt') is None:
         return None
     src = dst = steps[0]['pixFmt']
@@ -80,7 +83,58 @@ def _planeFormats(steps, width=None, height=None):
     if width is not None:
         pixfmt.planeShapes(src, width, height)
     _planeChroma(steps)
+    _planeFit(steps, width, height)
     return src, dst
+
+
+FIT_KEYS = ('width', 'height', 'fit')
+
+
+def _planeFit(steps, width=None, height=None):
+    """(W, H, method) of a planar chain whose output step names a size -- {'op': 'output', 'width': W, 'height': H, 'fit': 'nearest' | 'bilinear' | 'bicubic'}, 'fit'
+    defaults to 'bicubic': every plane is brought from the size the chain gives to W x H (chroma to W / 2 x H / 2) by pixfmt.fitPlanes -- or None.  ValueError naming
+    the key for a width or height that is not a positive even int, one without the other, an unknown 'fit', 'fit' without a size and, where the source's size is
+    known (width, height), a ratio beyond pixfmt.FIT_MAX_DOWN down or pixfmt.FIT_MAX_UP up on either axis against the chain's own output size (and, for a luma-only
+    chain, of its one pass from the source's chroma planes)."""
+    req = None
+    for s in steps[1:]:
+        if s.get('op') != 'output' or not any(k in s for k in FIT_KEYS):
+            continue
+        fit = s.get('fit', 'bicubic')
+        if fit not in pixfmt.CHROMA_METHODS:
+            raise ValueError('output: fit "{}" is not supported ({})'.format(fit, ', '.join(pixfmt.CHROMA_METHODS)))
+        if 'width' not in s and 'height' not in s:
+            raise ValueError("output: 'fit' needs a size ('width' and 'height')")
+        for k, other in (('width', 'height'), ('height', 'width')):
+            if k not in s:
+                raise ValueError("output: '{}' is missing beside '{}'".format(k, other))
+            v = s[k]
+            if not isinstance(v, int) or isinstance(v, bool) or v < 2 or v % 2:
+                raise ValueError("output: '{}' must be a positive even int (a 4:2:0 frame), got {!r}".format(k, v))
+        req = (s['width'], s['height'], fit)
+    if req is None or width is None:
+        return req
+    scale = 1
+    for s in steps[1:]:
+        if s.get('op') == 'SR':
+            scale *= int(s.get('scale', 1))
+    lumaOnly = steps[0].get('chroma', 'net') != 'net'
+    for k, have, want in (('width', int(width), req[0]), ('height', int(height), req[1])):
+        for n, what in ((have * scale, "the chain's"),) + (((have, "the source's chroma (one pass)"),) if lumaOnly else ()):
+            if n > pixfmt.FIT_MAX_DOWN * want:
+                raise ValueError("output: '{}' {} shrinks {} {} by more than {}".format(k, want, what, n, pixfmt.FIT_MAX_DOWN))
+            if want > pixfmt.FIT_MAX_UP * n:
+                raise ValueError("output: '{}' {} enlarges {} {} by more than {}".format(k, want, what, n, pixfmt.FIT_MAX_UP))
+    return req
+
+
+def _refuseFit(steps):
+    """A chain whose source is not planar has a resize step for this: the output step's size keys are refused, by name."""
+    for s in steps:
+        if s.get('op') == 'output':
+            for k in FIT_KEYS:
+                if k in s:
+                    raise ValueError("output: '{}' applies to a chain on planar Y'CbCr 4:2:0 frames only ({{'op': 'buffer', 'pixFmt': ..}}); an RGB chain takes a resize step".format(k))
 
 
 def _planeChroma(steps):
@@ -149,6 +203,27 @@ def _genProcessPlanes(steps, fmts):
     funcs, nodes, scale, _ = _planeChain(steps, False)
     quantise = toPlanes(pixfmt.FORMATS[dst])
     chroma, resamplers = _planeChroma(steps), {}
+    fit, quantise16, fitters = _planeFit(steps), toPlanes(16), {}
+
+    def runFit(rawDev, y, c, width, height, dev):
+        """The frame at the size the output step names: the chain's planes at 16 bits (the existing edge), then pixfmt.fitPlanes' kernel per image."""
+        W, H, method = fit
+        _planeFit(steps, width, height)          # (the ratios, now that the source's size is known)
+        w, h = width * scale, height * scale
+        Ds, Dd = pixfmt.FORMATS[src], pixfmt.FORMATS[dst]
+        if (width, height) not in fitters:
+            fitters[(width, height)] = (fitPlanes(16, Dd, 1, h, w, H, W, method),
+                                        fitPlanes(Ds, Dd, 2, height // 2, width // 2, H // 2, W // 2, *chroma) if chroma
+                                        else fitPlanes(16, Dd, 2, h // 2, w // 2, H // 2, W // 2, method))
+        fitY, fitC = fitters[(width, height)]
+        cb = pixfmt.planeOffsets(dst, W, H)[1]
+        out = torch.empty((pixfmt.frameBytes(dst, W, H),), dtype=torch.uint8, device=dev)
+        fitY(quantise16(reduce(apply, funcs, y)), out[:cb])
+        if chroma:
+            fitC(rawDev[pixfmt.planeOffsets(src, width, height)[1]:], out[cb:])
+        else:
+            fitC(quantise16(reduce(apply, funcs, c)), out[cb:])
+        return out.cpu().numpy().tobytes()
 
     def run(frame):
         raw, height, width = frame
@@ -158,6 +233,8 @@ def _genProcessPlanes(steps, fmts):
         dev = torch.device(config.device())
         rawDev = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
         y, c = fromPlanes(src, width, height, config.dtype())(rawDev)
+        if fit:
+            return runFit(rawDev, y, c, width, height, dev)
         w, h = width * scale, height * scale
         cb = pixfmt.planeOffsets(dst, w, h)[1]
         out = torch.empty((pixfmt.frameBytes(dst, w, h),), dtype=torch.uint8, device=dev)
@@ -182,6 +259,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
     planar = _planeFormats(steps)
     if planar:          # the decoder's own Y'CbCr 4:2:0 planes in, planar frames out
         return _genProcessPlanes(steps, planar)
+    _refuseFit(steps)
     ctx = Context()
     funcs, nodes = [], []
     has_file = bool(steps) and steps[0]['op'] == 'file'
@@ -652,8 +730,46 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
         def edge(y, raw, out, reuseY=None):
             into(y, out[:cb], reuseY)
             resample(raw, out)
+    outBytes = pixfmt.frameBytes(dst, w, h)
+    fit = _planeFit(steps, width, height)
+    if fit:          # a size on the output step: the edge above runs at 16 bits into one intermediate (compute queue only), then one fitPlanes per image into the slot's frame
+        import torch
+        W, H, method = fit
+        Dd, cb16, cbOut, cbIn = pixfmt.FORMATS[dst], w * h * 2, pixfmt.planeOffsets(dst, W, H)[1], pixfmt.planeOffsets(src, int(width), int(height))[1]
+        if last:
+            o, prepare = last
+            into = lambda x, out, reuse=None: doCropPlanes(o, prepare(x), 16, out, reuse=reuse)
+        else:
+            quantise16 = toPlanes(16)
+            into = lambda x, out, reuse=None: quantise16(x, out)
+        edgeName += '+fit'
+        outBytes = pixfmt.frameBytes(dst, W, H)
+        inter = {}          # the 16-bit planes of the chain's own size: allocated once, at the first frame
+
+        def intermediate(dev):
+            if 'buf' not in inter:
+                inter['buf'] = torch.empty((cb16 if chroma else pixfmt.frameBytes('yuv420p16le', w, h),), dtype=torch.uint8, device=dev)
+            return inter['buf']
+        fitY = fitPlanes(16, Dd, 1, h, w, H, W, method)
+        if chroma:          # luma-only: one pass from the source's chroma codes to the fitted size; no intermediate, no moe_chroma_resample
+            fitC = fitPlanes(pixfmt.FORMATS[src], Dd, 2, int(height) // 2, int(width) // 2, H // 2, W // 2, *chroma)
+
+            def edge(y, raw, out, reuseY=None):
+                mid = intermediate(out.device)
+                into(y, mid, reuseY)
+                fitY(mid, out[:cbOut])
+                fitC(raw[cbIn:], out[cbOut:])
+        else:
+            fitC = fitPlanes(16, Dd, 2, h // 2, w // 2, H // 2, W // 2, method)
+
+            def edge(y, c, out, reuseY=None, reuseC=None):
+                mid = intermediate(out.device)
+                into(y, mid[:cb16], reuseY)
+                into(c, mid[cb16:], reuseC)
+                fitY(mid[:cb16], out[:cbOut])
+                fitC(mid[cb16:], out[cbOut:])
     state = _ReuseState(rsteps, bool(last)) if reuse else None
-    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, pixfmt.frameBytes(dst, w, h), state, views, bool(chroma))
+    backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, outBytes, state, views, bool(chroma))
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
     stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
@@ -697,13 +813,19 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     byte for byte); 'chroma': 'net', the default, is the two-image form.  With reuse the change map and `stream.reuse` cover Y only.
     views=True: push / flush return read-only memoryviews (flat, format 'B') of the ring's pinned output buffers instead of bytes -- no copy is made.  A view is valid
     until the NEXT push, flush or close on this stream: frame k's slot is next written by the download that push(k + depth) enqueues, and that push is the first call
-    after the one that returned frame k.  Whoever needs a frame for longer copies it (bytes(view)); stats['tobytes_ms'] then reads about 0."""
+    after the one that returned frame k.  Whoever needs a frame for longer copies it (bytes(view)); stats['tobytes_ms'] then reads about 0.
+    With {'op': 'output', 'width': W, 'height': H, 'fit': 'nearest' | 'bilinear' | 'bicubic'} on a planar chain ('fit' defaults to 'bicubic', 'pixFmt' stays optional)
+    the finished frames are W x H: the edge runs at 16 bits into one intermediate of the chain's own size and one moe_fit_run per image (Y'; Cb / Cr) writes the
+    slot's frame -- a rational integer polyphase filter that antialiases where it shrinks (pixfmt.fitPlanes: integers, byte for byte); `edge` reads 'crop+fit' or
+    'quantise+fit'.  A luma-only chain fits Cb / Cr in one pass from the source's codes instead.  W and H are positive even ints within 4 down and 16 up of the chain's
+    own size (ValueError before a model is loaded); on a chain whose source is not planar the three keys are refused -- it has a resize step."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
     planar = _planeFormats(steps, width, height)
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
         return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views)
+    _refuseFit(steps)
     bitDepth = int(steps[0].get('bitDepth', 16))
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
