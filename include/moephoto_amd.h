@@ -346,6 +346,36 @@ int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int
 int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
                         const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream);
 
+/* ---- luma-only steps on RGB images ------------------------------------------------------------------------
+ * The reference sends every plane of a colour image through the net (planes are the batch: python/runSR.py:37-40); none of these entry points has a counterpart in
+ * it.  None of the SR / DN nets convolves planes jointly, so a step may run on Y' alone while Cb / Cr go to the output's size through moe_resize: a third of the net's
+ * work.  The definition is moephoto_amd/luma.py (lumaCoefficients, lumaSplit, lumaMerge): full range, no offset, all arithmetic fp32 with every product and every sum
+ * rounded separately in the written order (no FMA); the device matches it bit for bit (NaN payloads aside).  matrix MOE_YUV_BT709 / BT601 / BT2020NC gives the constants
+ * kr, kg = 1 - kr - kb, kb, ib = 1 / (2 (1 - kb)), ir = 1 / (2 (1 - kr)), eb = 2 (1 - kb), er = 2 (1 - kr), gr = kr er / kg, gb = kb eb / kg, each computed in double and
+ * rounded once; order says whether plane 0 is blue (MOE_ORDER_BGR) or red.  T = dtype, MOE_F16 / MOE_F32.
+ *
+ * moe_luma_split replaces handing the whole image to the net: img = (C = 3 | 4, H, W) of T, element (c, i, j) at img + c sC + i sH + j sW (strides in elements) ->
+ * dst_y = (C - 2, H, W) dense of T: y = (kr r + kg g) + kb b rounded to T, and behind it the fourth plane (alpha) unchanged, as the reference's SR path sends it through
+ * the net; dst_c = (2, H, W) dense fp32: cb = (b - y) ib, cr = (r - y) ir from the unrounded y.  One launch.  Refused (MOE_EINVAL, before any device call): a NULL
+ * pointer, C outside {3, 4}, a dtype other than MOE_F16 / MOE_F32, a size below 1, an unknown matrix / order, a pointer not aligned to its elements. */
+int moe_luma_split(const void* img, int dtype, int C, int64_t sC, int64_t sH, int64_t sW, int H, int W, int matrix, int order, void* dst_y, void* dst_c,
+                   int device, void* stream);
+/* moe_luma_merge replaces nothing of the reference's (it has no merge): y = (C - 2, H, W) dense of T (Y', alpha), c = (2, H, W) dense fp32 (Cb, Cr), C = 3 | 4 the planes
+ * written.  y' = fp32(T(Y')), r' = y' + er cr, b' = y' + eb cb, g' = y' - (gr cr + gb cb), each rounded to T, planes in `order`, alpha behind them unchanged.
+ * bits = 0: dst = the canvas (C, H, W) of dst_dtype = dtype; bits = 8 | 16: dst = (H, W, C) interleaved MOE_U8 / MOE_U16 samples, each value through moe_to_output's
+ * quantiser.  Serves the chains whose Y' is a canvas (an ensemble, a blended DN, a step that is not last).  Refused as above, and: unknown bits, a dst_dtype that does
+ * not fit them. */
+int moe_luma_merge(const void* y, int dtype, const void* c, int C, int H, int W, int matrix, int order, int bits, void* dst, int dst_dtype, int device, void* stream);
+/* moe_stitch_luma replaces moe_stitch -> moe_luma_merge (same bytes): the fold of a pool of P = 1 (Y') or 2 (Y', alpha) planes with the merge as its edge, so the Y'
+ * canvas never exists.  c = (2, out_h, out_w) dense fp32; dst and bits as moe_luma_merge's with C = P + 2 and T = canvas_dtype.  tile_off_dev: on the DEVICE, NULL =
+ * the plan's own layout.  Refused as above, and: P outside {1, 2}.  Asynchronous on `stream`. */
+int moe_stitch_luma(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int P, int canvas_dtype, const void* c, int matrix, int order,
+                    int bits, void* dst, int dst_dtype, void* stream);
+/* moe_run_plan_luma replaces moe_run_plan (or moe_run_plan_out) on the three colour planes: moe_run_plan on img_y (the plan's 1 or 2 planes, padded where the plan
+ * pads) with its final fold replaced by moe_stitch_luma. */
+int moe_run_plan_luma(moe_net* net, const moe_plan* plan, const void* img_y, int dtype, int64_t sC, int64_t sH, int64_t sW, const void* c, int matrix, int order,
+                      int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
+
 /* Planes of codes brought to a FITTED size: a rational (any n -> m) integer polyphase filter per axis, antialiasing where the axis shrinks -- the definition is
  * moephoto_amd/pixfmt.py (fitTable, fitPlanes) and the device matches it byte for byte.  A handle holds one geometry: `planes` (1 .. 4) planes of h x w codes at
  * src_depth -> as many planes of oh x ow at dst_depth (uint8 at depth 8, little-endian uint16 at 10, 12, 16; high bits are not masked), planes one after the other.

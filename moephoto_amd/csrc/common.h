@@ -469,6 +469,16 @@ struct YuvEdge {
 };
 void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s);      // C = 3, the whole canvas; a.out = the frame
 void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s);
+// Luma-only steps on RGB images (the definition: moephoto_amd/luma.py; the arithmetic: luma.h): the net runs on Y' alone, Cb / Cr ride around it as two fp32 planes.
+// The constants of a matrix, each computed in double and rounded once to fp32.
+struct LumaCoef { float kr, kg, kb, ib, ir, eb, er, gr, gb; };
+// The merge behind the fold (stitch_luma_kernel): a.C = the pool's planes (Y', and alpha behind it when 2); c = Cb then Cr, dense fp32 planes of out_h x out_w;
+// rp = the plane red goes to (0: 'rgb', 2: 'bgr'); quant = 0: a.out = the canvas (a.C + 2, out_h, out_w) of the canvas dtype, else 2^bits: interleaved u8 / u16 samples.
+struct StitchLuma { const float* c; LumaCoef k; int rp; float quant; };
+bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s);
+// luma.hip: a strided (C = 3 | 4, H, W) image -> dense Y (C - 2 planes of its dtype: Y', alpha) and dense Cb, Cr (fp32); and the merge on dense planes (quant as above)
+void launch_luma_split(const void* img, int dtype, int C, long long sC, long long sH, long long sW, int H, int W, const LumaCoef& k, int rp, void* dst_y, float* dst_c, hipStream_t s);
+void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, int W, const LumaCoef& k, int rp, float quant, void* dst, int dst_dtype, hipStream_t s);
 
 // blend.hip: the two blend() calls + slice-assign of doCrop's loop body for ONE tile, in the canvas dtype (moe_blend_tile)
 struct BlendTileArgs {

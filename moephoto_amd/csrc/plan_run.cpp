@@ -207,7 +207,9 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // (moe_stitch_out: the whole canvas only); with mix the DN step's blend and alpha ride in the fold too (moe_stitch_mix: canvas or samples, mix->quant says which);
 // with yuv `out` is the planar Y'CbCr 4:2:0 frame (moe_stitch_yuv: three planes, the whole canvas); with planes_depth `out` is C planes of samples at that depth
 // (moe_stitch_planes: the whole canvas).
-struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; int planes_depth = 0; };
+// With luma the C planes are Y' (and alpha) and `out` receives the C + 2 colour planes of a luma-only step's merge
+// (moe_stitch_luma: canvas or samples, luma->quant says which).
+struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; int planes_depth = 0; const StitchLuma* luma = nullptr; };
 static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
                   const OutEdge* edge = nullptr)
 {
@@ -265,6 +267,10 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
     if (edge && edge->planes_depth) {
         launch_stitch_planes(a, edge->canvas_dtype, edge->planes_depth, s);
         return launched("stitch_planes");
+    }
+    if (edge && edge->luma) {
+        if (!launch_stitch_luma(a, *edge->luma, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_luma: %d pool planes (1 or 2 are supported)", C);
+        return launched("stitch_luma");
     }
     if (edge && edge->mix) {
         if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
@@ -343,6 +349,35 @@ static int mix_edge_args(const char* who, const Plan& p, int planes, const void*
     if (!std::isfinite(strength)) return fail(MOE_EINVAL, "%s: strength must be finite", who);
     // strengthOp (python/imageProcess.py:562): x itself for s == 1, else s * x + (1 - s) * inp with the two Python floats handed to the device as fp32
     *m = StitchMix{inp, sC, sH, sW, alpha, aH, aW, (float)strength, (float)(1.0 - strength), strength != 1.0, bits ? (float)(1 << bits) : 0.f, 0, 0, 0, 0};
+    return MOE_OK;
+}
+
+// The constants of a luma-only step (moephoto_amd/luma.py: lumaCoefficients): each computed in double, in the definition's order, and rounded once to fp32.
+static LumaCoef luma_coef(int matrix)
+{
+    static const double K[3][2] = {{0.2126, 0.0722}, {0.299, 0.114}, {0.2627, 0.0593}};      // (Kr, Kb) of MOE_YUV_BT709, MOE_YUV_BT601, MOE_YUV_BT2020NC (pixfmt.LUMA)
+    const double kr = K[matrix][0], kb = K[matrix][1], kg = 1 - kr - kb;
+    const double eb = 2 * (1 - kb), er = 2 * (1 - kr);
+    return LumaCoef{(float)kr, (float)kg, (float)kb, (float)(1 / eb), (float)(1 / er), (float)eb, (float)er, (float)(kr * er / kg), (float)(kb * eb / kg)};
+}
+
+// What moe_luma_merge, moe_stitch_luma and moe_run_plan_luma check of their edge before any device call, and the edge itself.  planes: the colour planes written
+// (3, or 4 with alpha); T = dtype: the canvas dtype.  bits: 0 = the canvas, 8 or 16 = the samples.
+static int luma_edge_args(const char* who, int planes, int dtype, const void* c, int matrix, int order, int bits, const void* dst, int dst_dtype, StitchLuma* m)
+{
+    if (!c || !dst) return fail(MOE_EINVAL, "%s: NULL argument", who);
+    if (planes != 3 && planes != 4) return fail(MOE_EINVAL, "%s: %d colour planes (3, or 4 with alpha)", who, planes);
+    if (dtype != MOE_F32 && dtype != MOE_F16) return fail(MOE_EINVAL, "%s: canvas dtype must be MOE_F32 or MOE_F16", who);
+    if (matrix < MOE_YUV_BT709 || matrix > MOE_YUV_BT2020NC) return fail(MOE_EINVAL, "%s: unknown matrix %d", who, matrix);
+    if (order != MOE_ORDER_BGR && order != MOE_ORDER_RGB) return fail(MOE_EINVAL, "%s: unknown order %d", who, order);
+    if (bits != 0 && bits != 8 && bits != 16) return fail(MOE_EINVAL, "%s: %d bits (0 = the canvas, 8 or 16)", who, bits);
+    if (bits == 0 && dst_dtype != dtype) return fail(MOE_EINVAL, "%s: dst dtype must be the canvas dtype for the canvas form (bits = 0)", who);
+    if (bits != 0 && dst_dtype != MOE_U8 && dst_dtype != MOE_U16) return fail(MOE_EINVAL, "%s: dst dtype must be MOE_U8 or MOE_U16 for %d bits", who, bits);
+    if (bits > 8 && dst_dtype == MOE_U8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
+    if ((uintptr_t)c & 3) return fail(MOE_EINVAL, "%s: c is not 4-byte aligned (fp32 planes)", who);
+    const uintptr_t es = dst_dtype == MOE_F32 ? 4 : dst_dtype == MOE_U8 ? 1 : 2;
+    if ((uintptr_t)dst & (es - 1)) return fail(MOE_EINVAL, "%s: dst is not aligned to its %d-byte elements", who, (int)es);
+    *m = StitchLuma{(const float*)c, luma_coef(matrix), order == MOE_ORDER_RGB ? 0 : 2, bits ? (float)(1 << bits) : 0.f};
     return MOE_OK;
 }
 
@@ -602,6 +637,20 @@ int moe_stitch_yuv(const moe_plan* p, int device, const float* tiles_dev, const 
     return stitch(*p, device, tiles_dev, tile_off_dev, false, 3, dst, depth == 8 ? MOE_U8 : MOE_U16, nullptr, (hipStream_t)stream, &edge);
 }
 
+int moe_stitch_luma(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int P, int canvas_dtype, const void* c, int matrix, int order,
+                    int bits, void* dst, int dst_dtype, void* stream)
+{
+    if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_luma: NULL argument");
+    if (P != 1 && P != 2) return fail(MOE_EINVAL, "moe_stitch_luma: %d pool planes (1: Y', or 2: Y' and alpha)", P);
+    StitchLuma m{};
+    const int rc = luma_edge_args("moe_stitch_luma", P + 2, canvas_dtype, c, matrix, order, bits, dst, dst_dtype, &m);
+    if (rc) return rc;
+    if ((uintptr_t)tiles_dev & 3) return fail(MOE_EINVAL, "moe_stitch_luma: tiles_dev is not 4-byte aligned (fp32 pool)");
+    OutEdge edge{canvas_dtype, m.quant};
+    edge.luma = &m;
+    return stitch(*p, device, tiles_dev, tile_off_dev, false, P, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
+}
+
 int moe_blend_tile(const void* r, int64_t r_sC, int64_t r_sH, void* canvas, int64_t c_sC, int64_t c_sH, int dtype, int C,
                    int top_sc, int left_sc, int bsc, int rsc, int topT, int leftT, int pad_sc, const void* ramp, void* stream)
 {
@@ -673,6 +722,20 @@ int moe_run_plan_filter(moe_net* n, const moe_plan* pl, const void* img, int img
     if (rc) return rc;
     const OutEdge edge{img_dtype, m.quant, &m};
     return run_plan("moe_run_plan_filter", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
+}
+
+int moe_run_plan_luma(moe_net* n, const moe_plan* pl, const void* img_y, int dtype, int64_t sC, int64_t sH, int64_t sW, const void* c, int matrix, int order,
+                      int bits, void* dst, int dst_dtype, int max_tiles, void* stream)
+{
+    if (!n || !pl || !img_y) return fail(MOE_EINVAL, "moe_run_plan_luma: NULL argument");
+    if (pl->p.C != 1 && pl->p.C != 2) return fail(MOE_EINVAL, "moe_run_plan_luma: the plan has %d planes (1: Y', or 2: Y' and alpha)", pl->p.C);
+    StitchLuma m{};
+    const int rc = luma_edge_args("moe_run_plan_luma", pl->p.C + 2, dtype, c, matrix, order, bits, dst, dst_dtype, &m);
+    if (rc) return rc;
+    if ((uintptr_t)img_y & (dtype == MOE_F16 ? 1 : 3)) return fail(MOE_EINVAL, "moe_run_plan_luma: img_y is not aligned to its %d-byte elements", dtype == MOE_F16 ? 2 : 4);
+    OutEdge edge{dtype, m.quant};
+    edge.luma = &m;
+    return run_plan("moe_run_plan_luma", n, pl, img_y, dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
 int moe_run_plan_tiles(moe_net* n, const moe_plan* pl, const void* imgs, int img_dtype, int64_t frame_stride,
@@ -911,6 +974,35 @@ int moe_planes_to_float(const void* src, int depth, int H, int W, void* dst_y, v
     HIP_TRY(hipSetDevice(device));
     launch_to_float_planes(src, depth, H, W, dst_y, dst_c, dst_dtype, (hipStream_t)stream);
     return launched("to_float_planes");
+}
+
+int moe_luma_split(const void* img, int dtype, int C, int64_t sC, int64_t sH, int64_t sW, int H, int W, int matrix, int order, void* dst_y, void* dst_c, int device, void* stream)
+{
+    if (!img || !dst_y || !dst_c) return fail(MOE_EINVAL, "moe_luma_split: NULL argument");
+    if (C != 3 && C != 4) return fail(MOE_EINVAL, "moe_luma_split: %d planes (3, or 4 with alpha)", C);
+    if (dtype != MOE_F32 && dtype != MOE_F16) return fail(MOE_EINVAL, "moe_luma_split: dtype must be MOE_F32 or MOE_F16");
+    if (H < 1 || W < 1) return fail(MOE_EINVAL, "moe_luma_split: size %d x %d must be positive", W, H);
+    if (matrix < MOE_YUV_BT709 || matrix > MOE_YUV_BT2020NC) return fail(MOE_EINVAL, "moe_luma_split: unknown matrix %d", matrix);
+    if (order != MOE_ORDER_BGR && order != MOE_ORDER_RGB) return fail(MOE_EINVAL, "moe_luma_split: unknown order %d", order);
+    const uintptr_t es = dtype == MOE_F16 ? 2 : 4;
+    if (((uintptr_t)img | (uintptr_t)dst_y) & (es - 1)) return fail(MOE_EINVAL, "moe_luma_split: img / dst_y are not aligned to their %d-byte elements", (int)es);
+    if ((uintptr_t)dst_c & 3) return fail(MOE_EINVAL, "moe_luma_split: dst_c is not 4-byte aligned (fp32 planes)");
+    HIP_TRY(hipSetDevice(device));
+    launch_luma_split(img, dtype, C, sC, sH, sW, H, W, luma_coef(matrix), order == MOE_ORDER_RGB ? 0 : 2, dst_y, (float*)dst_c, (hipStream_t)stream);
+    return launched("to_float_luma");
+}
+
+int moe_luma_merge(const void* y, int dtype, const void* c, int C, int H, int W, int matrix, int order, int bits, void* dst, int dst_dtype, int device, void* stream)
+{
+    if (!y) return fail(MOE_EINVAL, "moe_luma_merge: NULL argument");
+    if (H < 1 || W < 1) return fail(MOE_EINVAL, "moe_luma_merge: size %d x %d must be positive", W, H);
+    StitchLuma m{};
+    const int rc = luma_edge_args("moe_luma_merge", C, dtype, c, matrix, order, bits, dst, dst_dtype, &m);
+    if (rc) return rc;
+    if ((uintptr_t)y & (dtype == MOE_F16 ? 1 : 3)) return fail(MOE_EINVAL, "moe_luma_merge: y is not aligned to its %d-byte elements", dtype == MOE_F16 ? 2 : 4);
+    HIP_TRY(hipSetDevice(device));
+    launch_luma_merge(y, dtype, m.c, C, H, W, m.k, m.rp, m.quant, dst, dst_dtype, (hipStream_t)stream);
+    return launched("to_output_luma");
 }
 
 int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,

@@ -1,4 +1,4 @@
-// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_planes, moe_stitch_mix, moe_stitch_yuv): one skeleton, four edges on
+// stitch.hip -- the fold of the tile pool into the image (moe_stitch / moe_stitch_band, moe_stitch_out, moe_stitch_planes, moe_stitch_mix, moe_stitch_luma, moe_stitch_yuv): one skeleton, five edges on
 // it and the Y'CbCr 4:2:0 edge over the same fold with a body of its own (chroma needs row pairs).
 //
 // Stitch: per-pixel fold of doCrop's sequential blend (imageProcess.py:120-131,167-170).  Every HR pixel visits,
@@ -11,11 +11,13 @@
 //     SamplesEdge    the encoder's interleaved u8 / u16 samples: the canvas dtype's rounding and to_output_kernel's quantiser            stitch_out_kernel
 //     PlaneEdge      the same samples at depth 8 / 10 / 12 / 16 as planes, one per blockIdx.z: the planes of a planar 4:2:0 frame            stitch_planes_kernel
 //     MixEdge        the DN step: strengthOp's blend with the image the net saw and the alpha plane, in canvas or sample form            stitch_mix_kernel
+//     LumaEdge       the merge of a luma-only step: Y' from the fold, Cb / Cr from two fp32 planes, the colour planes in canvas or sample form         stitch_luma_kernel
 //     (YuvEdge)      the encoder's planar Y'CbCr 4:2:0 frame from SamplesEdge's 16-bit samples: half the bytes of the interleaved image      stitch_yuv_kernel
 // The fold itself (stitch_classify, stitch_fold_row, stitch_pixel) exists once, so the bit equalities the tests demand between the edges (moe_stitch_out == moe_stitch ->
 // float -> quantise, moe_stitch_mix == stitch + torch) hold by construction.  This file is compiled without extra flags: the fold's cur + w (q - cur) contracts to one FMA.
 #include "common.h"
 #include "run_store.h"
+#include "luma.h"
 #include <type_traits>
 #include "../../include/moephoto_amd.h"
 
@@ -395,6 +397,71 @@ __global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The merge of a luma-only step in the stitch (moe_stitch_luma; the definition: moephoto_amd/luma.py, the arithmetic: luma.h): the pool holds Y' alone (and alpha behind
+// it when CT = 4), Cb / Cr come as two dense fp32 planes of the output's size, and the fold's edge writes the CT colour planes -- the Y' canvas never exists.  Per pixel
+//     y = fp32(T(fold));   r = y + er cr;   b = y + eb cb;   g = y - (gr cr + gb cb);   each rounded to T;   alpha = T(fold of plane 1)
+// exactly what moe_stitch -> moe_luma_merge give (to_output_luma_kernel runs the same luma.h functions).  A thread folds CT - 2 planes and holds CT output planes.
+// TD == T: the canvas form, dst = (CT, out_h, out_w) planes; else the sample form, dst = (out_h, out_w, CT) interleaved through to_output_kernel's quantiser.
+// The chroma runs are read as 16-byte vectors where their address allows it (out_w % 4 != 0 shifts every other row).
+// ---------------------------------------------------------------------------------------------------
+template <typename T, typename TD, int CT>
+struct LumaEdge {
+    static constexpr bool SAMPLE = !std::is_same<T, TD>::value;
+    static constexpr int NP = CT - 2, NOUT = CT;
+    struct Planes { StitchRun<T, 8> p[CT]; };
+    typedef typename std::conditional<SAMPLE, StitchRun<TD, 8 * CT>, Planes>::type Row;      // sample form: e[pixel * CT + plane]; canvas form: p[plane].e[pixel]
+    const StitchLuma& m;
+    __device__ __forceinline__ int c0() const { return 0; }
+    __device__ __forceinline__ int np(const StitchArgs&) const { return NP; }
+    __device__ __forceinline__ void emit(const StitchArgs& a, int X0, int Y, const float (&cur)[NP][8], Row& o) const
+    {
+        const float* const pb = m.c + (long long)Y * a.out_w + X0;
+        const float* const pr = pb + (long long)a.out_h * a.out_w;
+        float cb[8], cr[8];
+        stitch_mix_load8(pb, 1, ((uintptr_t)pb & 15) == 0, cb);
+        stitch_mix_load8(pr, 1, ((uintptr_t)pr & 15) == 0, cr);
+        T y[CT][8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            luma_merge_planes<T>(m.k, (float)(T)cur[0][e], cb[e], cr[e], m.rp, y[0][e], y[1][e], y[2][e]);
+            if constexpr (CT == 4) y[3][e] = luma_canon((T)cur[1][e]);
+        }
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if constexpr (SAMPLE) o.e[e * CT + c] = luma_quant<TD>((float)y[c][e], m.quant);
+                else o.p[c].e[e] = y[c][e];
+            }
+    }
+    __device__ __forceinline__ void store(const StitchArgs& a, int X0, int Y, const Row& o) const
+    {
+        if constexpr (SAMPLE) stitch_store((TD*)a.out + ((long long)Y * a.out_w + X0) * CT, o);
+        else {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) stitch_store((T*)a.out + ((long long)c * a.out_h + Y) * a.out_w + X0, o.p[c]);
+        }
+    }
+    __device__ __forceinline__ void pixel(const StitchArgs& a, int X, int Y, int c) const
+    {
+        T y;
+        if (c == 3) y = luma_canon((T)stitch_pixel(a, X, Y, 1));
+        else {
+            const long long at = (long long)Y * a.out_w + X;
+            y = luma_canon((T)luma_merge_px(m.k, (float)(T)stitch_pixel(a, X, Y, 0), m.c[at], m.c[(long long)a.out_h * a.out_w + at], luma_colour(c, m.rp)));
+        }
+        if constexpr (SAMPLE) ((TD*)a.out)[((long long)Y * a.out_w + X) * CT + c] = luma_quant<TD>((float)y, m.quant);
+        else ((T*)a.out)[((long long)c * a.out_h + Y) * a.out_w + X] = y;
+    }
+};
+
+template <typename T, typename TD, int CT, int R>
+__global__ __launch_bounds__(256) void stitch_luma_kernel(StitchArgs a, StitchLuma m)
+{
+    stitch_fold<R>(a, LumaEdge<T, TD, CT>{m});
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The encoder's planar Y'CbCr 4:2:0 frame (moe_stitch_yuv, moe_to_yuv; the definition: moephoto_amd/pixfmt.py).  Per pixel the three planes are taken at 16 bits by
 // SamplesEdge's quantiser -- the samples moe_stitch_out / moe_to_output write with bits = 16 -- and the conversion behind them is integer: Y per pixel, Cb and Cr from
 // the sums of a 2 x 2 block.  The frame is 1.5 samples per pixel instead of 3: half the writes, half the download.
@@ -664,6 +731,33 @@ bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipSt
     if (m.quant == 0.f) return f16 ? launch_stitch_mix_t<half_t, half_t>(a, m, planes, s) : launch_stitch_mix_t<float, float>(a, m, planes, s);
     if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s);
     return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s);
+}
+
+template <typename T, typename TD, int R>
+static bool launch_stitch_luma_r(const StitchArgs& a, const StitchLuma& m, hipStream_t s)
+{
+    const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.rows + R - 1) / R);
+    if (a.C == 1) hipLaunchKernelGGL((stitch_luma_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m);
+    else if (a.C == 2) hipLaunchKernelGGL((stitch_luma_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m);
+    else return false;
+    return true;
+}
+
+template <typename T, typename TD>
+static bool launch_stitch_luma_t(const StitchArgs& a, const StitchLuma& m, hipStream_t s)      // (rows per thread: launch_stitch_mix_t's rule)
+{
+    const long long blocks4 = (long long)(((a.out_w + 7) / 8 + 255) / 256) * ((a.out_h + 3) / 4);
+    return blocks4 >= 1024 ? launch_stitch_luma_r<T, TD, 4>(a, m, s) : launch_stitch_luma_r<T, TD, 1>(a, m, s);
+}
+
+// a.C: the pool's planes, 1 (Y') or 2 (Y', alpha); a.C + 2 planes are written.  m.quant == 0: a.out = the canvas (a.C + 2, out_h, out_w) of canvas_dtype; else a.out =
+// interleaved (out_h, out_w, a.C + 2) of a.out_dtype MOE_U8 / MOE_U16.  The whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
+bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s)
+{
+    const bool f16 = canvas_dtype == MOE_F16;
+    if (m.quant == 0.f) return f16 ? launch_stitch_luma_t<half_t, half_t>(a, m, s) : launch_stitch_luma_t<float, float>(a, m, s);
+    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_luma_t<half_t, uint8_t>(a, m, s) : launch_stitch_luma_t<float, uint8_t>(a, m, s);
+    return f16 ? launch_stitch_luma_t<half_t, uint16_t>(a, m, s) : launch_stitch_luma_t<float, uint16_t>(a, m, s);
 }
 
 // a.out: the Y'CbCr 4:2:0 frame of a.out_h x a.out_w (uint8 for depth 8, else uint16); three planes, the whole canvas (y0 = 0, rows = out_h, row_lo = 0)

@@ -16,6 +16,9 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
                                        polyphase filter of pixfmt.resampleChroma
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
+  lumaSplit, lumaMerge, doCropLuma     (no counterpart: the reference sends every plane of an RGB image through the net, python/runSR.py:37-40) -> moe_luma_split /
+                                       moe_luma_merge / moe_run_plan_luma: a luma-only step -- the net on Y' alone, Cb / Cr resized, merged inside the last fold
+                                       (the definition: moephoto_amd/luma.py)
   readFile / writeFile                 :265-302         (PIL, host)
 
 There is no CPU path: models must be moephoto_amd.models.EngineModule instances on a HIP device.
@@ -287,11 +290,12 @@ def _planesOut(who, depth, C, h, w, out, device):
     return out
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None, reuse=None):
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None, reuse=None, luma=None):
     """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
     alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold, with yuv = (pixFmt, matrix, order) moe_run_plan_yuv: the
     encoder's planar frame from the final fold, with planes = depth moe_run_plan_planes: the image's own planes as samples of that depth) and its one retry after
-    a MemoryError.
+    a MemoryError.  With luma = (C', matrix, order) x is the Y image of a luma-only step (luma.lumaSplit: 1 plane, or 2 with alpha) and the call is moe_run_plan_luma:
+    the final fold merges Y' with the fp32 chroma planes C' (2, outH, outW) into the colour planes -- the canvas (x's planes + 2, outH, outW), or with bitDepth its samples.
     reuse (the frame stream's): a callable (plan, planes) -> (mask, pool) -- the plan's tiles that have to run for this image as n_tiles uint8 on
     the host, and the fp32 device tensor of plan.pool_elems(planes) that holds every other tile's result from the previous frame.  The call is then moe_run_plan_subset
     into that pool followed by the same edge's stitch-only entry point on it (moe_stitch, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv, moe_stitch_planes)."""
@@ -318,6 +322,13 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
             alpha = alpha.to(xp.dtype)
             C += 1
         aH, aW = alpha.stride() if alpha is not None else (0, 0)
+    if luma is not None:
+        chroma, matrix, order = luma[0], pixfmt.MATRICES[luma[1]], pixfmt.ORDERS[luma[2]]
+        if C not in (1, 2):
+            raise ValueError('{}: a Y image of 1 plane (2 with alpha) expected, got {} planes'.format(who, C))
+        if (tuple(chroma.shape) != (2, plan.outH, plan.outW) or chroma.dtype != torch.float32 or not chroma.is_contiguous() or chroma.device != x.device):
+            raise ValueError('{}: the chroma planes must be a contiguous fp32 tensor of shape {} on {}'.format(who, (2, plan.outH, plan.outW), x.device))
+        C += 2
     if yuv is not None:
         depth, matrix, order = pixfmt.check(*yuv)
         if C != 3:
@@ -344,7 +355,10 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
         dev, P, dt = x.device.index or 0, xp.shape[0], _DT[xp.dtype]
 
     def fold():        # the edge alone, on the stream's pool in the plan's own layout
-        if yuv is not None:
+        if luma is not None:
+            _lib.check(L.moe_stitch_luma(plan._h, dev, pool.data_ptr(), None, P, dt, chroma.data_ptr(), matrix, order, int(bitDepth or 0), out.data_ptr(),
+                                         _DT[out.dtype] if bitDepth is None else lib_dt, stream))
+        elif yuv is not None:
             _lib.check(L.moe_stitch_yuv(plan._h, dev, pool.data_ptr(), None, dt, depth, matrix, order, out.data_ptr(), stream))
         elif planes is not None:
             _lib.check(L.moe_stitch_planes(plan._h, dev, pool.data_ptr(), None, P, dt, int(planes), out.data_ptr(), stream))
@@ -360,6 +374,9 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
         if reuse is not None:
             _lib.check(L.moe_run_plan_subset(model._h, plan._h, xp.data_ptr(), dt, sC, sH, sW, mask.ctypes.data, pool.data_ptr(), int(config.tilesPerBatch), stream))
             fold()
+        elif luma is not None:       # the canvas doCrop would have returned for Y has xp's dtype: its rounding comes first, then the merge in that dtype
+            _lib.check(L.moe_run_plan_luma(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, chroma.data_ptr(), matrix, order, int(bitDepth or 0),
+                                           out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
         elif yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
             _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth, matrix, order,
                                           out.data_ptr(), int(config.tilesPerBatch), stream))
@@ -383,6 +400,8 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
     xp.record_stream(torch.cuda.current_stream(x.device))
     if mix is not None and alpha is not None:
         alpha.record_stream(torch.cuda.current_stream(x.device))
+    if luma is not None:
+        chroma.record_stream(torch.cuda.current_stream(x.device))
     return out
 
 
@@ -413,6 +432,119 @@ def doCropPlanes(opt, x, depth, out=None, reuse=None):
     dtype would have and writes C = 1 .. 4 planes of outH x outW samples (uint8 for depth 8, else little-endian uint16) -- the Y plane or the two chroma planes of a
     planar 4:2:0 frame (pixfmt.fromPlanes).  Returns a flat uint8 device tensor of those bytes; out: one to write into, e.g. a view into a frame at a plane's offset."""
     return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth), reuse=reuse)
+
+
+# ---- luma-only steps (no counterpart: the reference sends every plane through the net; the definition: moephoto_amd/luma.py) -------------------
+def _lumaIds(who, matrix, order):
+    if matrix not in pixfmt.MATRICES:
+        raise ValueError('{}: chromaMatrix "{}" is not supported ({})'.format(who, matrix, ', '.join(pixfmt.MATRICES)))
+    if order not in pixfmt.ORDERS:
+        raise ValueError('{}: order "{}" is not supported ({})'.format(who, order, ', '.join(pixfmt.ORDERS)))
+    return pixfmt.MATRICES[matrix], pixfmt.ORDERS[order]
+
+
+LUMA_KEYS = ('chroma', 'chromaMatrix', 'order')
+
+
+def lumaKeys(step, defaultOrder='rgb'):
+    """(chroma, chromaMatrix, order) of an SR / DN step dict, checked: 'chroma' is 'net' (the default: every plane goes through the net, today's path), 'nearest',
+    'bilinear' or 'bicubic' (the step is luma-only and Cb / Cr are resized by that method); 'chromaMatrix' defaults to 'bt709'; 'order' says whether plane 0 is red
+    ('rgb', behind a file source) or blue ('bgr', behind a buffer source).  ValueError naming the key for an unknown value and for 'chromaMatrix' / 'order' beside 'net'."""
+    op = step.get('op', 'step')
+    chroma = step.get('chroma', 'net')
+    if chroma != 'net' and chroma not in _lib.RESIZE_MODES:
+        raise ValueError("{}: 'chroma' \"{}\" is not supported (net, {})".format(op, chroma, ', '.join(_lib.RESIZE_MODES)))
+    if chroma == 'net':
+        for k in LUMA_KEYS[1:]:
+            if k in step:
+                raise ValueError("{}: '{}' does not apply to 'chroma': 'net' (every plane goes through the net, nothing is converted)".format(op, k))
+        return 'net', 'bt709', defaultOrder
+    matrix, order = step.get('chromaMatrix', 'bt709'), step.get('order', defaultOrder)
+    if matrix not in pixfmt.MATRICES:
+        raise ValueError("{}: 'chromaMatrix' \"{}\" is not supported ({})".format(op, matrix, ', '.join(pixfmt.MATRICES)))
+    if order not in pixfmt.ORDERS:
+        raise ValueError("{}: 'order' \"{}\" is not supported ({})".format(op, order, ', '.join(pixfmt.ORDERS)))
+    return chroma, matrix, order
+
+
+def lumaSplit(matrix='bt709', order='rgb'):
+    """luma.lumaSplit on the device (moe_luma_split, one launch): f(x) takes a (3 | 4, H, W) fp16 / fp32 device image, strided or dense, and returns Y (1 | 2, H, W) of
+    x's dtype -- Y', and alpha behind it -- and C (2, H, W) fp32 -- Cb, Cr."""
+    mat, ordr = _lumaIds('lumaSplit', matrix, order)
+
+    def f(x):
+        if x.device.type != 'cuda':
+            raise _lib.EngineError('lumaSplit: input must live on a HIP device (moephoto_amd has no CPU path)')
+        if x.dim() != 3 or x.shape[0] not in (3, 4):
+            raise ValueError('lumaSplit expects a (3 | 4, H, W) image, got {}'.format(tuple(x.shape)))
+        if x.dtype not in _DT:
+            x = x.to(config.dtype())
+        C, H, W = x.shape
+        Y = torch.empty((C - 2, H, W), dtype=x.dtype, device=x.device)
+        Cc = torch.empty((2, H, W), dtype=torch.float32, device=x.device)
+        cur = torch.cuda.current_stream(x.device)
+        _lib.check(_lib.lib().moe_luma_split(x.data_ptr(), _DT[x.dtype], C, x.stride(0), x.stride(1), x.stride(2), H, W, mat, ordr, Y.data_ptr(), Cc.data_ptr(),
+                                             x.device.index or 0, cur.cuda_stream))
+        x.record_stream(cur)
+        return Y, Cc
+    return f
+
+
+def lumaMerge(matrix='bt709', order='rgb'):
+    """luma.lumaMerge on the device (moe_luma_merge): f(Y, C, bitDepth=None, out=None) takes Y' (1 | 2, H, W) fp16 / fp32 and C' (2, H, W) fp32 and returns the canvas
+    (3 | 4, H, W) of Y's dtype, or with bitDepth 8 | 16 the quantised (H, W, 3 | 4) image as doCropOut gives it; out: a tensor of that shape and dtype to write into."""
+    mat, ordr = _lumaIds('lumaMerge', matrix, order)
+
+    def f(Y, Cc, bitDepth=None, out=None):
+        if Y.device.type != 'cuda' or Cc.device != Y.device:
+            raise _lib.EngineError('lumaMerge: both inputs must live on one HIP device (moephoto_amd has no CPU path)')
+        if Y.dim() != 3 or Y.shape[0] not in (1, 2):
+            raise ValueError('lumaMerge expects a (1 | 2, H, W) Y image, got {}'.format(tuple(Y.shape)))
+        if Y.dtype not in _DT:
+            Y = Y.to(config.dtype())
+        P, H, W = Y.shape
+        if tuple(Cc.shape) != (2, H, W) or Cc.dtype != torch.float32:
+            raise ValueError('lumaMerge: the chroma planes must be fp32 of shape {}, got {} {}'.format((2, H, W), Cc.dtype, tuple(Cc.shape)))
+        Y, Cc = Y.contiguous(), Cc.contiguous()
+        if bitDepth is None:
+            shape, o_dt, lib_dt = (P + 2, H, W), Y.dtype, _DT[Y.dtype]
+        else:
+            o_dt, _, lib_dt = _outStorage(bitDepth)
+            shape = (H, W, P + 2)
+        if out is None:
+            out = torch.empty(shape, dtype=o_dt, device=Y.device)
+        elif tuple(out.shape) != shape or out.dtype != o_dt or not out.is_contiguous() or out.device != Y.device:
+            raise ValueError('lumaMerge: out must be a contiguous {} tensor of shape {} on {}'.format(o_dt, shape, Y.device))
+        cur = torch.cuda.current_stream(Y.device)
+        _lib.check(_lib.lib().moe_luma_merge(Y.data_ptr(), _DT[Y.dtype], Cc.data_ptr(), P + 2, H, W, mat, ordr, int(bitDepth or 0), out.data_ptr(), lib_dt,
+                                             Y.device.index or 0, cur.cuda_stream))
+        Y.record_stream(cur)
+        Cc.record_stream(cur)
+        return out
+    return f
+
+
+def lumaChroma(Cc, height, width, method):
+    """The chroma planes of a luma-only step at the size of its Y': the existing resize on fp32 with the method the step's 'chroma' key names; the planes themselves
+    when the size does not change (a DN step)."""
+    if tuple(Cc.shape[-2:]) == (int(height), int(width)):
+        return Cc
+    return resizeByTorch(Cc, width, height, method)
+
+
+def doCropLuma(opt, x, method, matrix='bt709', order='rgb', bitDepth=None, out=None, reuse=None):
+    """A luma-only step with the merge inside the last fold (moe_run_plan_luma; with reuse moe_run_plan_subset + moe_stitch_luma): lumaSplit(x), the chroma planes
+    resized to the step's output size, doCrop on Y with the final fold writing the colour planes -- the Y' canvas never exists.  The bytes of
+    lumaMerge(doCrop(opt, Y), lumaChroma(C, ..)).  With bitDepth the fold writes the encoder's samples into `out`, as doCropOut does.  An image of fewer than three
+    planes has no chroma to set aside: it runs as doCrop / doCropOut."""
+    if method not in _lib.RESIZE_MODES:
+        raise ValueError('doCropLuma: chroma "{}" is not supported ({})'.format(method, ', '.join(_lib.RESIZE_MODES)))
+    _lumaIds('doCropLuma', matrix, order)
+    if x.dim() == 3 and x.shape[0] < 3:
+        return _runPlan('doCropLuma', opt, x, bitDepth, out, reuse=reuse)
+    Y, Cc = lumaSplit(matrix, order)(x)
+    plan = _plan_for(opt, Y.shape)
+    return _runPlan('doCropLuma', opt, Y, bitDepth, out, reuse=reuse, luma=(lumaChroma(Cc, plan.outH, plan.outW, method), matrix, order))
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------

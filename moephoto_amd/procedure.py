@@ -25,6 +25,10 @@ the ring's pinned buffers instead of copies.
 
 With {'op': 'output', 'width': W, 'height': H, 'fit': 'bicubic'} on such a chain both builders deliver W x H frames: the planes the chain gives are brought to the size
 asked for by a rational integer polyphase filter that antialiases where it shrinks (pixfmt.fitPlanes, moe_fit_create / moe_fit_run).
+
+With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on an SR or DN step of a chain on an RGB source (a file, an array, a bgr24 / bgr48le buffer) that step is luma-only:
+the net runs on Y' alone and Cb / Cr go to its output size through the existing resize; a last step whose fold writes the samples merges the planes inside that fold
+(moephoto_amd/luma.py, imageProcess.doCropLuma, moe_run_plan_luma).
 """
 import math
 import time
@@ -32,8 +36,8 @@ from functools import reduce
 
 from . import _lib, pixfmt, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (RGBFilter, _RGBFilter, apply, doCrop, doCropOut, doCropPlanes, doCropYuv, filterOut, fitPlanes, fromPlanes, identity, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes,
-                           toTorch, toYuv, writeFile, _DT, _outStorage)
+from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPlanes, fromPlanes, identity, lumaChroma, lumaKeys,
+                           lumaMerge, lumaSplit, mergeAlpha, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -54,6 +58,78 @@ def _outputFormat(steps):
             pixfmt.check(*req)
             return req
     return None
+
+
+# ---- luma-only steps on an RGB source --------------------------------------------------------------------------------------
+# {'op': 'SR', .., 'chroma': 'bicubic'}: the step runs on Y' alone and Cb / Cr go to its output size through the existing resize (moephoto_amd/luma.py is the definition).
+def _lumaCheck(steps, planar=False):
+    """Every SR / DN step's 'chroma' / 'chromaMatrix' / 'order' keys, checked before any model is loaded (ValueError naming the key: imageProcess.lumaKeys; and any of
+    the three on a step of a planar chain, which has its own 'chroma' key on the source step).  A luma-only step's defaults are written into its dict: 'order' is 'bgr'
+    behind a buffer source (the video path's frames), 'rgb' behind a file."""
+    default = 'bgr' if steps and steps[0].get('op') == 'buffer' else 'rgb'
+    for s in steps:
+        if s.get('op') not in ('SR', 'DN'):
+            continue
+        if planar:
+            for k in LUMA_KEYS:
+                if k in s:
+                    raise ValueError("{}: '{}' does not apply to a step of a chain on planar Y'CbCr 4:2:0 frames: its source step has its own 'chroma' key".format(s['op'], k))
+            continue
+        chroma, matrix, order = lumaKeys(s, default)
+        if chroma != 'net':
+            s['chromaMatrix'], s['order'] = matrix, order
+
+
+def _isLuma(o):
+    return getattr(o, 'chroma', 'net') != 'net'
+
+
+def _lumaStep(op, o):
+    """A luma-only SR / DN step in its unfused form -> (f, its reuse form): lumaSplit, the step on Y (runSR.sr: doCrop or the ensemble; RGBFilter's blend), the chroma
+    planes resized to Y' 's size, lumaMerge.  The DN step keeps RGBFilter's alpha handling: alpha is split off first and re-attached behind the merge; the SR step sends
+    alpha through the net as Y's second plane.  An image of fewer than three planes runs as without the key.  The reuse form is g(x, reuse, changed) -> (y, the
+    region of y): the tiles' rule on Y, joined with the resize rule on the same input region for the chroma planes."""
+    split, merge = lumaSplit(o.chromaMatrix, o.order), lumaMerge(o.chromaMatrix, o.order)
+    plain = runSR.sr(o) if op == 'SR' else RGBFilter(o)
+
+    def run(x, net):
+        if x.shape[0] < 3:
+            return net(x)
+        alpha = {}
+        if op == 'DN':
+            x = o.prepare(extractAlpha(alpha)(x))
+        Y, C = split(x)
+        Y = net(Y)
+        y = merge(Y, lumaChroma(C, Y.shape[-2], Y.shape[-1], o.chroma))
+        return mergeAlpha(alpha)(y) if op == 'DN' else y
+    f = lambda x: run(x, plain)
+    if op == 'SR' and o.ensemble != 0:
+        return f, ('opaque', f)
+
+    def g(x, reuse, changed):
+        y = run(x, (lambda Y: doCrop(o, Y, reuse=reuse)) if op == 'SR' else (lambda Y: _RGBFilter(o, Y, reuse)))
+        region = reuse.out
+        if region is not None and changed is not None:
+            inHW, outHW = tuple(x.shape[-2:]), tuple(y.shape[-2:])
+            region = region | (changed if inHW == outHW else _reuse.resizeRegion(changed, inHW, outHW, o.chroma))
+        else:
+            region = None
+        return y, region
+    return f, ('luma', g)
+
+
+def _lumaLast(op, o, unfused, bitDepth):
+    """genProcess' last step when it is a luma-only SR without ensemble or DN of strength 1: doCropLuma with the merge and the quantiser inside the last fold, downloaded
+    as toOutput returns its image.  A four-plane image through a DN step (alpha rides around the net) takes the unfused form: the same bytes."""
+    import numpy as np
+    quantise = toOutput(bitDepth)
+
+    def f(x):
+        if op == 'DN' and x.shape[0] == 4:
+            return quantise(toFloat(unfused(x)))
+        a = doCropLuma(o, o.prepare(x) if op == 'DN' else x, o.chroma, o.chromaMatrix, o.order, bitDepth).cpu().numpy()
+        return a.view(np.uint16) if bitDepth > 8 else a
+    return f
 
 
 # ---- chains on the decoder's own planes -----------------------------------------------------------------------------------------------------
@@ -257,6 +333,7 @@ class Context(object):
 def genProcess(steps, bitDepth=8, outFile=None):
     steps = [dict(s) for s in steps]
     planar = _planeFormats(steps)
+    _lumaCheck(steps, bool(planar))
     if planar:          # the decoder's own Y'CbCr 4:2:0 planes in, planar frames out
         return _genProcessPlanes(steps, planar)
     _refuseFit(steps)
@@ -273,6 +350,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         bitDepth = int(steps[0].get('bitDepth', 16))
         funcs.append(toNumPy(bitDepth))
     funcs.append(toTorch(bitDepth, config.dtype(), config.device()))
+    work, fused = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')], None
     for opt in steps:
         op = opt['op']
         if op in ('file', 'buffer', 'output'):
@@ -290,9 +368,15 @@ def genProcess(steps, bitDepth=8, outFile=None):
         if o is None:
             raise ValueError('unknown model for step {}'.format(opt))
         opt['opt'] = o
-        if op == 'SR':
-            if not opt['scale'] > 1:
-                raise TypeError('Invalid scale setting for SR.')
+        if op == 'SR' and not opt['scale'] > 1:
+            raise TypeError('Invalid scale setting for SR.')
+        if _isLuma(o):          # a luma-only step; the last one's fold writes the samples itself where it can (an SR without ensemble, a DN of strength 1)
+            f = _lumaStep(op, o)[0]
+            if opt is work[-1] and not yuv and bitDepth in (8, 16) and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
+                fused = _lumaLast(op, o, f, bitDepth)
+            else:
+                funcs.append(f)
+        elif op == 'SR':
             funcs.append(runSR.sr(o))
         else:
             funcs.append(RGBFilter(o))
@@ -301,7 +385,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         funcs += [toYuv(*yuv), lambda t: t.cpu().numpy().tobytes()]
         run = lambda im: reduce(apply, funcs, im)
         return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
-    funcs += [toFloat, toOutput(bitDepth)]
+    funcs += [fused] if fused else [toFloat, toOutput(bitDepth)]
     if has_file and outFile is not None:
         funcs.append(lambda im: writeFile(im, outFile, ctx))
     if has_buffer:
@@ -421,6 +505,8 @@ class _ReuseState(object):
             if kind == 'tiles':
                 cb = self.callback((i, image), changed)
                 x, changed = f(x, cb), cb.out
+            elif kind == 'luma':          # a luma-only step (_lumaStep): the tiles' rule on Y and the resize rule on the chroma planes, joined by the step itself
+                x, changed = f(x, self.callback((i, image), changed), changed)
             elif kind == 'resize':
                 y = f(x)
                 changed = _reuse.resizeRegion(changed, tuple(x.shape[-2:]), tuple(y.shape[-2:]), step[2]['method']) if changed is not None else None
@@ -818,11 +904,20 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     the finished frames are W x H: the edge runs at 16 bits into one intermediate of the chain's own size and one moe_fit_run per image (Y'; Cb / Cr) writes the
     slot's frame -- a rational integer polyphase filter that antialiases where it shrinks (pixfmt.fitPlanes: integers, byte for byte); `edge` reads 'crop+fit' or
     'quantise+fit'.  A luma-only chain fits Cb / Cr in one pass from the source's codes instead.  W and H are positive even ints within 4 down and 16 up of the chain's
-    own size (ValueError before a model is loaded); on a chain whose source is not planar the three keys are refused -- it has a resize step."""
+    own size (ValueError before a model is loaded); on a chain whose source is not planar the three keys are refused -- it has a resize step.
+    With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on an SR or DN step of a chain whose source is NOT planar (and 'chromaMatrix': 'bt709' | 'bt601' | 'bt2020nc',
+    'order': 'bgr' -- the default behind a buffer -- | 'rgb') that step is luma-only: it runs on Y' = (kr r + kg g) + kb b alone and the full-range Cb / Cr planes go to
+    its output size through moe_resize with the method named (moephoto_amd/luma.py is the definition).  A last step that is an SR without ensemble or a DN of strength 1
+    keeps edge 'crop': its fold merges Y' with the resized chroma planes and writes the encoder's samples (doCropLuma); every other position or form -- a step that is
+    not last, an ensemble, a blended DN, a chain with an {'op': 'output', 'pixFmt': ..} step -- merges unfused (lumaMerge) and the edge is what it is without the key
+    for that chain's tail ('quantise').  'chroma': 'net', the default, is today's path; 'chromaMatrix' / 'order' beside it, unknown values, and any of the three keys on
+    a step of a planar chain raise ValueError naming the key before a model is loaded.  reuse=True works unchanged: the change map applies to Y' as it is
+    (DESIGN.md section 17)."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
     planar = _planeFormats(steps, width, height)
+    _lumaCheck(steps, bool(planar))
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
         return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views)
     _refuseFit(steps)
@@ -854,9 +949,19 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
         if o is None:
             raise ValueError('unknown model for step {}'.format(opt))
         opt['opt'] = o
-        if op == 'SR':
-            if not opt['scale'] > 1:
-                raise TypeError('Invalid scale setting for SR.')
+        if op == 'SR' and not opt['scale'] > 1:
+            raise TypeError('Invalid scale setting for SR.')
+        if _isLuma(o):          # a luma-only step: the merge rides in the last fold where that fold writes the samples; every other position or form merges unfused
+            if last and not yuv and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
+                edge, edgeName = (lambda x, out, reuse=None, o=o, prepare=o.prepare if op == 'DN' else identity:
+                                  doCropLuma(o, prepare(x), o.chroma, o.chromaMatrix, o.order, bitDepth, out, reuse=reuse)), 'crop'
+            else:
+                f, r = _lumaStep(op, o)
+                funcs.append(f)
+                rsteps.append(r)
+            if op == 'SR':
+                h, w = h * opt['scale'], w * opt['scale']
+        elif op == 'SR':
             if last and o.ensemble == 0:
                 edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:], reuse=reuse) if yuv
                                   else doCropOut(o, x, bitDepth, out, reuse=reuse)), 'crop'

@@ -3,7 +3,7 @@ MPRNet / NAFNet / VSR_Cleaning rows are other model families, out of this engine
 import os
 
 from .config import config
-from .imageProcess import initModel, Option
+from .imageProcess import initModel, lumaKeys, Option
 from .models import NetDN, SEDN
 from .runSR import engineRamCoef
 
@@ -23,7 +23,9 @@ def getOpt(optDN):
     crop_dns for SEDN; planes become the batch along the table's squeeze dim."""
     name = optDN['model']
     rel_path, ctor, sq_dim, padding, align = mode_switch[name]
+    luma = lumaKeys(optDN)          # 'chroma', 'chromaMatrix', 'order': a luma-only step (ValueError before the model is loaded)
     opt = Option(os.path.join(config.modelRoot, rel_path))
+    opt.chroma, opt.chromaMatrix, opt.order = luma
     opt.modelDef, opt.padding, opt.align = ctor, padding, align
     opt.strength = optDN.get('strength', 1.0)
     crops = config.getConfig()

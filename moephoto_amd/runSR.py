@@ -6,7 +6,7 @@ import os
 
 from . import _lib
 from .config import config
-from .imageProcess import ensemble, initModel, Option
+from .imageProcess import ensemble, initModel, lumaKeys, Option
 from .models import Net2x, Net3x, Net4x
 from .MoeNet_lite2 import Net
 
@@ -39,13 +39,16 @@ sr = lambda opt: ensemble(opt, average=True)
 
 def getOpt(optSR):
     """python/runSR.py:30-48: step dict {'model': 'a', 'scale': 4, 'ensemble': 0} -> Option, or None for an unknown model/scale pair.
-    Colour planes become the batch (dim-1 squeeze / unsqueeze), padding 9 for the x3 nets and 5 otherwise, cropsize = config.crop_sr."""
+    Colour planes become the batch (dim-1 squeeze / unsqueeze), padding 9 for the x3 nets and 5 otherwise, cropsize = config.crop_sr.
+    The keys 'chroma', 'chromaMatrix' and 'order' (imageProcess.lumaKeys: a luma-only step, no counterpart in the reference) go onto the Option as they are."""
     key = '{}{}'.format(optSR['model'], optSR['scale'])
     entry = mode_switch.get(key)
     if entry is None:
         return None
     rel_path, ctor = entry
+    luma = lumaKeys(optSR)          # (ValueError before the model is loaded)
     opt = Option(os.path.join(config.modelRoot, rel_path))
+    opt.chroma, opt.chromaMatrix, opt.order = luma
     opt.mode, opt.scale, opt.modelDef = optSR['model'], optSR['scale'], ctor
     opt.fixChannel = 0
     opt.squeeze, opt.unsqueeze = (lambda t: t.squeeze(1)), (lambda t: t.unsqueeze(1))
