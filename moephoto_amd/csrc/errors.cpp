@@ -18,6 +18,12 @@ int moe::fail(int code, const char* fmt, ...)
     return code;
 }
 
+int moe::launched(const char* who)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MOE_EHIP, "%s launch failed: %s", who, hipGetErrorString(e));
+    return MOE_OK;
+}
 
 extern "C" {
 

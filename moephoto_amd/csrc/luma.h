@@ -84,20 +84,3 @@ __device__ __forceinline__ void luma_load8(const T* p, long long sW, bool vec, i
         for (int e = 0; e < 8; ++e) v[e] = p[min(e, n - 1) * sW];
     }
 }
-
-// The first n pixels of a run of eight, N / 8 elements each: whole runs through stitch_store, the ragged end element by element (constant indices in loops of eight
-// that unroll: a run indexed by a loop variable is moved to LDS)
-template <typename T, int N>
-__device__ __forceinline__ void luma_store(T* p, const StitchRun<T, N>& v, int n)
-{
-    constexpr int G = N / 8;
-    if (n == 8) stitch_store(p, v);
-    else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            if (e >= n) break;
-#pragma unroll
-            for (int c = 0; c < G; ++c) p[e * G + c] = v.e[e * G + c];
-        }
-    }
-}

@@ -35,15 +35,15 @@ __global__ __launch_bounds__(256) void to_float_luma_kernel(const T* __restrict_
             oy.e[e] = (T)y;
         }
         const long long at = (long long)Y * W + X0;
-        luma_store(dst_y + at, oy, n);
-        luma_store(dst_c + at, ob, n);
-        luma_store(dst_c + HW + at, orr, n);
+        stitch_store_n(dst_y + at, oy, n);
+        stitch_store_n(dst_c + at, ob, n);
+        stitch_store_n(dst_c + HW + at, orr, n);
         if (C == 4) {          // alpha rides as Y's second plane
             luma_load8(row + 3 * sC, sW, v16, n, r);
             StitchRun<T, 8> oa;
 #pragma unroll
             for (int e = 0; e < 8; ++e) oa.e[e] = r[e];
-            luma_store(dst_y + HW + at, oa, n);
+            stitch_store_n(dst_y + HW + at, oa, n);
         }
     }
 }
@@ -77,14 +77,14 @@ __global__ __launch_bounds__(256) void to_output_luma_kernel(const T* __restrict
         for (int p = 0; p < CT; ++p)
 #pragma unroll
             for (int e = 0; e < 8; ++e) s.e[e * CT + p] = luma_quant<TD>((float)o[p][e], quant);
-        luma_store(dst + i0 * CT, s, n);
+        stitch_store_n(dst + i0 * CT, s, n);
     } else {
 #pragma unroll
         for (int p = 0; p < CT; ++p) {
             StitchRun<T, 8> s;
 #pragma unroll
             for (int e = 0; e < 8; ++e) s.e[e] = o[p][e];
-            luma_store(dst + p * HW + i0, s, n);
+            stitch_store_n(dst + p * HW + i0, s, n);
         }
     }
 }

@@ -22,6 +22,9 @@ namespace moe {
 // errors (errors.cpp)
 // =====================================================================================================
 int fail(int code, const char* fmt, ...);      // the message moe_last_error returns (thread-local); returns `code`
+int launched(const char* who);                 // behind a kernel launch: MOE_OK, or MOE_EHIP with "<who> launch failed: <hipGetLastError's text>"
+
+inline bool plane_depth(int depth) { return depth == 8 || depth == 10 || depth == 12 || depth == 16; }      // the depths of planar samples
 
 #define HIP_TRY(expr)                                                                                    \
     do {                                                                                                 \

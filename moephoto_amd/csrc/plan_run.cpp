@@ -1,17 +1,11 @@
 // plan_run.cpp -- the device-resident doCrop (tile gather -> net -> stitch: python/imageProcess.py:157-172).  A plan handle owns the planner's result and, beside it,
 // its device state: TILE TABLES (which planes of which image go where: built by tile_table from an input layout and a (frame, tile) -> destination table, one bounded
 // cache), the stitch tables of a (device, C) and the internal tile pool.  Every moe_run_plan* runner is a destination table + run_sets, the one loop that cuts a
-// table's groups into launch sets; every stitch is stitch().  Also here: the planner's entry points, the inter-rank wire format, the self-ensemble and the image edges.
+// table's groups into launch sets; every stitch is stitch().  Also here: the planner's entry points, the inter-rank wire format, the self-ensemble and the image edges
+// between floats and samples (the integer resamplers of planar codes, moe_chroma_resample and moe_fit_*, are polyphase.cpp's).
 #include "net.h"
 
 using namespace moe;
-
-static int launched(const char* who)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MOE_EHIP, "%s launch failed: %s", who, hipGetErrorString(e));
-    return MOE_OK;
-}
 
 // =====================================================================================================
 // the plan handle's device state
@@ -295,8 +289,6 @@ static int out_edge_args(const char* who, int planes, int canvas_dtype, int bits
     if (dst_dtype == MOE_U8 && bits > 8) return fail(MOE_EINVAL, "%s: %d bits do not fit MOE_U8", who, bits);
     return MOE_OK;
 }
-
-static bool plane_depth(int depth) { return depth == 8 || depth == 10 || depth == 12 || depth == 16; }
 
 // What moe_stitch_planes and moe_run_plan_planes check of their edge before any device call, and the edge itself.  planes: the C the kernel is asked for.
 static int plane_edge_args(const char* who, int planes, int canvas_dtype, int depth, const void* dst, OutEdge* edge)
@@ -1003,154 +995,6 @@ int moe_luma_merge(const void* y, int dtype, const void* c, int C, int H, int W,
     HIP_TRY(hipSetDevice(device));
     launch_luma_merge(y, dtype, m.c, C, H, W, m.k, m.rp, m.quant, dst, dst_dtype, (hipStream_t)stream);
     return launched("to_output_luma");
-}
-
-int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
-                        const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream)
-{
-    if (!src || !dst || !cx || !ox || !cy || !oy) return fail(MOE_EINVAL, "moe_chroma_resample: NULL argument");
-    if (!plane_depth(src_depth) || !plane_depth(dst_depth)) return fail(MOE_EINVAL, "moe_chroma_resample: depth %d -> %d (8, 10, 12 or 16)", src_depth, dst_depth);
-    if (h < 1 || w < 1) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d must be positive", w, h);
-    if (scale < 1 || scale > 16) return fail(MOE_EINVAL, "moe_chroma_resample: scale %d (1 to 16)", scale);
-    if ((long long)h * scale > 0x7fffffffll || (long long)w * scale > 0x7fffffffll) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d times %d does not fit an int", w, h, scale);
-    if (taps != 1 && taps != 2 && taps != 4) return fail(MOE_EINVAL, "moe_chroma_resample: %d taps (1, 2 or 4)", taps);
-    if (src_depth > 8 && ((uintptr_t)src & 1)) return fail(MOE_EINVAL, "moe_chroma_resample: src is not 2-byte aligned (depth %d: uint16 samples)", src_depth);
-    if (dst_depth > 8 && ((uintptr_t)dst & 1)) return fail(MOE_EINVAL, "moe_chroma_resample: dst is not 2-byte aligned (depth %d: uint16 samples)", dst_depth);
-    ChromaTab t[2] = {};
-    const int16_t* const coef[2] = {cx, cy};
-    const int8_t* const off[2] = {ox, oy};
-    for (int a = 0; a < 2; ++a)
-        for (int p = 0; p < scale; ++p) {
-            int sum = 0, mag = 0;
-            for (int j = 0; j < taps; ++j) {
-                const int c = coef[a][p * taps + j];
-                t[a].coef[p][j] = (short)c;
-                sum += c; mag += c < 0 ? -c : c;
-            }
-            // sum |c| <= 32767: the row pass's int32 sum holds for any uint16 code (32767 * 65535 < 2^31) -- part of the contract, the kernel does not check it
-            if (sum != 16384 || mag > 32767)
-                return fail(MOE_EINVAL, "moe_chroma_resample: %s coefficients of phase %d sum to %d (must be 16384) with magnitudes %d (32767 at most)", a ? "vertical" : "horizontal", p, sum, mag);
-            if (off[a][p] < -2 || off[a][p] > 1) return fail(MOE_EINVAL, "moe_chroma_resample: %s offset %d of phase %d (-2 to 1)", a ? "vertical" : "horizontal", (int)off[a][p], p);
-            t[a].off[p] = off[a][p];
-        }
-    HIP_TRY(hipSetDevice(device));
-    launch_chroma_resample(src, src_depth, h, w, dst, dst_depth, scale, taps, t[0], t[1], (hipStream_t)stream);
-    return launched("resize_kernel_codes");
-}
-
-// ---- fitted sizes (fit.hip) ------------------------------------------------------------------------------
-struct moe_fit {
-    int planes, ds, dd, h, w, oh, ow, th, device;
-    size_t lds;
-    void* tab;          // one device block: ox[ow], oy[oh], then the coefficient rows of x and of y
-    FitAxis ax, ay;
-};
-
-// The largest source window (samples along the axis) of any tile of `tile` output indices: off[last] + taps - off[first]; off is non-decreasing.
-static long long fit_window(const int32_t* off, long long m, int taps, int tile)
-{
-    long long worst = 0;
-    for (long long o0 = 0; o0 < m; o0 += tile) {
-        const long long o1 = std::min<long long>(o0 + tile, m) - 1;
-        worst = std::max(worst, (long long)off[o1] + taps - off[o0]);
-    }
-    return worst;
-}
-
-int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
-                   int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
-{
-    if (!cx || !ox || !cy || !oy || !out) return fail(MOE_EINVAL, "moe_fit_create: NULL argument");
-    *out = nullptr;
-    if (!plane_depth(src_depth) || !plane_depth(dst_depth)) return fail(MOE_EINVAL, "moe_fit_create: depth %d -> %d (8, 10, 12 or 16)", src_depth, dst_depth);
-    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "moe_fit_create: %d planes (1 to 4)", planes);
-    if (h < 1 || w < 1 || oh < 1 || ow < 1) return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld must be positive", (long long)w, (long long)h, (long long)ow, (long long)oh);
-    if (h > 0x7fffffffll || w > 0x7fffffffll || oh > 0x7fffffffll || ow > 0x7fffffffll)
-        return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld does not fit an int", (long long)w, (long long)h, (long long)ow, (long long)oh);
-    if (taps_x < 1 || taps_x > FIT_TAPS || taps_y < 1 || taps_y > FIT_TAPS) return fail(MOE_EINVAL, "moe_fit_create: %d x %d taps (1 to %d)", taps_x, taps_y, FIT_TAPS);
-    const int16_t* const coef[2] = {cx, cy};
-    const int32_t* const off[2] = {ox, oy};
-    const long long n[2] = {w, h}, m[2] = {ow, oh};
-    const int taps[2] = {taps_x, taps_y};
-    for (int a = 0; a < 2; ++a) {
-        const char* const axis = a ? "vertical" : "horizontal";
-        for (long long o = 0; o < m[a]; ++o) {
-            int sum = 0, mag = 0;
-            for (int j = 0; j < taps[a]; ++j) {
-                const int c = coef[a][o * taps[a] + j];
-                sum += c; mag += c < 0 ? -c : c;
-            }
-            // sum |c| <= 32767: the row pass's int32 sum holds for any uint16 code (32767 * 65535 < 2^31) -- part of the contract, the kernel does not check it
-            if (sum != 16384 || mag > 32767)
-                return fail(MOE_EINVAL, "moe_fit_create: %s coefficients of output %lld sum to %d (must be 16384) with magnitudes %d (32767 at most)", axis, o, sum, mag);
-            const long long first = off[a][o];
-            if (first + taps[a] - 1 < 0 || first > n[a] - 1)
-                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld: its %d taps do not reach the %lld samples", axis, first, o, taps[a], n[a]);
-            if (o && first < off[a][o - 1])
-                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld is below its predecessor's %d (offsets must not decrease)", axis, first, o, (int)off[a][o - 1]);
-        }
-    }
-    // the tile: FIT_TW outputs wide and th high, the largest th whose window (the row pass's int32 sums and the source samples) fits the budget
-    const long long es = src_depth == 8 ? 1 : 2, sw = fit_window(ox, ow, taps_x, FIT_TW);
-    int th = 0;
-    long long lds = 0;
-    for (int t : {32, 16, 8}) {
-        const long long sh = fit_window(oy, oh, taps_y, t);
-        lds = sh * FIT_TW * 4 + ((sh * sw * es + 15) & ~15ll);
-        if (lds <= (long long)FIT_LDS_BUDGET) { th = t; break; }
-    }
-    if (!th) return fail(MOE_EINVAL, "moe_fit_create: the source window of a %d x 8 tile takes %lld bytes of LDS (%lld at most): the offsets step too far", FIT_TW, lds, (long long)FIT_LDS_BUDGET);
-    std::unique_ptr<moe_fit> f(new moe_fit{});
-    f->planes = planes; f->ds = src_depth; f->dd = dst_depth; f->h = (int)h; f->w = (int)w; f->oh = (int)oh; f->ow = (int)ow; f->th = th; f->device = device;
-    f->lds = (size_t)lds;
-    // the upload: offsets, then (16-byte aligned) the coefficient rows padded to FIT_TAPS with zeros
-    const size_t n_off = (((size_t)(ow + oh) * 4) + 15) & ~(size_t)15, n_cx = (size_t)ow * FIT_TAPS * 2, n_cy = (size_t)oh * FIT_TAPS * 2;
-    std::vector<unsigned char> host(n_off + n_cx + n_cy, 0);
-    memcpy(host.data(), ox, (size_t)ow * 4);
-    memcpy(host.data() + (size_t)ow * 4, oy, (size_t)oh * 4);
-    for (int a = 0; a < 2; ++a) {
-        int16_t* rows = (int16_t*)(host.data() + n_off + (a ? n_cx : 0));
-        for (long long o = 0; o < m[a]; ++o) memcpy(rows + o * FIT_TAPS, coef[a] + o * taps[a], (size_t)taps[a] * 2);
-    }
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&f->tab, host.size()));
-    const hipError_t e = hipMemcpy(f->tab, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(f->tab);
-        return fail(MOE_EHIP, "moe_fit_create: the tables' upload failed: %s", hipGetErrorString(e));
-    }
-    const unsigned char* d = (const unsigned char*)f->tab;
-    f->ax = FitAxis{(const int*)d, (const short*)(d + n_off), taps_x};
-    f->ay = FitAxis{(const int*)(d + (size_t)ow * 4), (const short*)(d + n_off + n_cx), taps_y};
-    *out = f.release();
-    return MOE_OK;
-}
-
-int moe_fit_run(const moe_fit* f, const void* src, void* dst, void* stream)
-{
-    if (!f || !src || !dst) return fail(MOE_EINVAL, "moe_fit_run: NULL argument");
-    if (f->ds > 8 && ((uintptr_t)src & 1)) return fail(MOE_EINVAL, "moe_fit_run: src is not 2-byte aligned (depth %d: uint16 samples)", f->ds);
-    if (f->dd > 8 && ((uintptr_t)dst & 1)) return fail(MOE_EINVAL, "moe_fit_run: dst is not 2-byte aligned (depth %d: uint16 samples)", f->dd);
-    HIP_TRY(hipSetDevice(f->device));
-    launch_fit(src, f->ds, f->h, f->w, dst, f->dd, f->oh, f->ow, f->planes, f->th, f->lds, f->ax, f->ay, (hipStream_t)stream);
-    return launched("resize_kernel_fit");
-}
-
-int moe_fit_info(const moe_fit* f, int64_t info[4])
-{
-    if (!f || !info) return fail(MOE_EINVAL, "moe_fit_info: NULL argument");
-    info[0] = FIT_TW; info[1] = f->th; info[2] = (int64_t)f->lds; info[3] = f->planes;
-    return MOE_OK;
-}
-
-void moe_fit_destroy(moe_fit* f)
-{
-    if (!f) return;
-    if (f->tab) {
-        (void)hipSetDevice(f->device);
-        (void)hipFree(f->tab);
-    }
-    delete f;
 }
 
 int moe_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, int device, void* stream)

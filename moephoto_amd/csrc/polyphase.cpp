@@ -1,0 +1,160 @@
+// polyphase.cpp -- the entry points of the two integer polyphase resamplers of planar codes: moe_chroma_resample (chroma.hip: the chroma planes of a luma-only
+// chain, integer scales) and moe_fit_create / _run / _info / _destroy (fit.hip: planes brought to a fitted size).  What they check of the caller's tables is the
+// contract the kernels rely on (polyphase.h): the kernels check nothing.
+#include "net.h"
+
+using namespace moe;
+
+// One row of an axis' coefficient table (`word`: what the entry point calls a row, "phase" or "output").  sum |c| <= 32767: the row pass's int32 sum holds for any
+// uint16 code (32767 * 65535 < 2^31), and the column pass's result fits an int behind its shift.
+static int poly_row_check(const char* who, const char* axis, const char* word, long long row, const int16_t* c, int taps)
+{
+    int sum = 0, mag = 0;
+    for (int j = 0; j < taps; ++j) { sum += c[j]; mag += c[j] < 0 ? -c[j] : c[j]; }
+    if (sum != 16384 || mag > 32767)
+        return fail(MOE_EINVAL, "%s: %s coefficients of %s %lld sum to %d (must be 16384) with magnitudes %d (32767 at most)", who, axis, word, row, sum, mag);
+    return MOE_OK;
+}
+
+static int poly_depths_check(const char* who, int ds, int dd) { return plane_depth(ds) && plane_depth(dd) ? MOE_OK : fail(MOE_EINVAL, "%s: depth %d -> %d (8, 10, 12 or 16)", who, ds, dd); }
+static int poly_aligned_check(const char* who, const void* src, int ds, const void* dst, int dd)
+{
+    if (ds > 8 && ((uintptr_t)src & 1)) return fail(MOE_EINVAL, "%s: src is not 2-byte aligned (depth %d: uint16 samples)", who, ds);
+    if (dd > 8 && ((uintptr_t)dst & 1)) return fail(MOE_EINVAL, "%s: dst is not 2-byte aligned (depth %d: uint16 samples)", who, dd);
+    return MOE_OK;
+}
+static const char* axis_name(int a) { return a ? "vertical" : "horizontal"; }
+
+extern "C" {
+
+int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
+                        const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream)
+{
+    if (!src || !dst || !cx || !ox || !cy || !oy) return fail(MOE_EINVAL, "moe_chroma_resample: NULL argument");
+    if (int rc = poly_depths_check("moe_chroma_resample", src_depth, dst_depth)) return rc;
+    if (h < 1 || w < 1) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d must be positive", w, h);
+    if (scale < 1 || scale > 16) return fail(MOE_EINVAL, "moe_chroma_resample: scale %d (1 to 16)", scale);
+    if ((long long)h * scale > 0x7fffffffll || (long long)w * scale > 0x7fffffffll) return fail(MOE_EINVAL, "moe_chroma_resample: size %d x %d times %d does not fit an int", w, h, scale);
+    if (taps != 1 && taps != 2 && taps != 4) return fail(MOE_EINVAL, "moe_chroma_resample: %d taps (1, 2 or 4)", taps);
+    if (int rc = poly_aligned_check("moe_chroma_resample", src, src_depth, dst, dst_depth)) return rc;
+    ChromaTab t[2] = {};
+    const int16_t* const coef[2] = {cx, cy};
+    const int8_t* const off[2] = {ox, oy};
+    for (int a = 0; a < 2; ++a)
+        for (int p = 0; p < scale; ++p) {
+            if (int rc = poly_row_check("moe_chroma_resample", axis_name(a), "phase", p, coef[a] + p * taps, taps)) return rc;
+            if (off[a][p] < -2 || off[a][p] > 1) return fail(MOE_EINVAL, "moe_chroma_resample: %s offset %d of phase %d (-2 to 1)", axis_name(a), (int)off[a][p], p);
+            std::copy(coef[a] + p * taps, coef[a] + (p + 1) * taps, t[a].coef[p]);
+            t[a].off[p] = off[a][p];
+        }
+    HIP_TRY(hipSetDevice(device));
+    launch_chroma_resample(src, src_depth, h, w, dst, dst_depth, scale, taps, t[0], t[1], (hipStream_t)stream);
+    return launched("resize_kernel_codes");
+}
+
+// ---- fitted sizes (fit.hip) ------------------------------------------------------------------------------
+struct moe_fit {
+    int planes, ds, dd, h, w, oh, ow, th, device;
+    size_t lds;
+    void* tab;          // one device block: ox[ow], oy[oh], then the coefficient rows of x and of y
+    FitAxis ax, ay;
+};
+
+// The largest source window (samples along the axis) of any tile of `tile` output indices: off[last] + taps - off[first]; off is non-decreasing.
+static long long fit_window(const int32_t* off, long long m, int taps, int tile)
+{
+    long long worst = 0;
+    for (long long o0 = 0; o0 < m; o0 += tile) {
+        const long long o1 = std::min<long long>(o0 + tile, m) - 1;
+        worst = std::max(worst, (long long)off[o1] + taps - off[o0]);
+    }
+    return worst;
+}
+
+int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
+                   int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
+{
+    if (!cx || !ox || !cy || !oy || !out) return fail(MOE_EINVAL, "moe_fit_create: NULL argument");
+    *out = nullptr;
+    if (int rc = poly_depths_check("moe_fit_create", src_depth, dst_depth)) return rc;
+    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "moe_fit_create: %d planes (1 to 4)", planes);
+    if (h < 1 || w < 1 || oh < 1 || ow < 1) return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld must be positive", (long long)w, (long long)h, (long long)ow, (long long)oh);
+    if (h > 0x7fffffffll || w > 0x7fffffffll || oh > 0x7fffffffll || ow > 0x7fffffffll)
+        return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld does not fit an int", (long long)w, (long long)h, (long long)ow, (long long)oh);
+    if (taps_x < 1 || taps_x > FIT_TAPS || taps_y < 1 || taps_y > FIT_TAPS) return fail(MOE_EINVAL, "moe_fit_create: %d x %d taps (1 to %d)", taps_x, taps_y, FIT_TAPS);
+    const int16_t* const coef[2] = {cx, cy};
+    const int32_t* const off[2] = {ox, oy};
+    const long long n[2] = {w, h}, m[2] = {ow, oh};
+    const int taps[2] = {taps_x, taps_y};
+    for (int a = 0; a < 2; ++a)
+        for (long long o = 0; o < m[a]; ++o) {
+            if (int rc = poly_row_check("moe_fit_create", axis_name(a), "output", o, coef[a] + o * taps[a], taps[a])) return rc;
+            const long long first = off[a][o];
+            if (first + taps[a] - 1 < 0 || first > n[a] - 1)
+                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld: its %d taps do not reach the %lld samples", axis_name(a), first, o, taps[a], n[a]);
+            if (o && first < off[a][o - 1])
+                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld is below its predecessor's %d (offsets must not decrease)", axis_name(a), first, o, (int)off[a][o - 1]);
+        }
+    // the tile: FIT_TW outputs wide and th high, the largest th whose window (the row pass's int32 sums and the source samples) fits the budget
+    const long long es = src_depth == 8 ? 1 : 2, sw = fit_window(ox, ow, taps_x, FIT_TW);
+    int th = 0;
+    long long lds = 0;
+    for (int t : {32, 16, 8}) {
+        const long long sh = fit_window(oy, oh, taps_y, t);
+        lds = sh * FIT_TW * 4 + ((sh * sw * es + 15) & ~15ll);
+        if (lds <= (long long)FIT_LDS_BUDGET) { th = t; break; }
+    }
+    if (!th) return fail(MOE_EINVAL, "moe_fit_create: the source window of a %d x 8 tile takes %lld bytes of LDS (%lld at most): the offsets step too far", FIT_TW, lds, (long long)FIT_LDS_BUDGET);
+    std::unique_ptr<moe_fit> f(new moe_fit{});
+    f->planes = planes; f->ds = src_depth; f->dd = dst_depth; f->h = (int)h; f->w = (int)w; f->oh = (int)oh; f->ow = (int)ow; f->th = th; f->device = device;
+    f->lds = (size_t)lds;
+    // the upload: offsets, then (16-byte aligned) the coefficient rows padded to FIT_TAPS with zeros
+    const size_t n_off = (((size_t)(ow + oh) * 4) + 15) & ~(size_t)15, n_cx = (size_t)ow * FIT_TAPS * 2, n_cy = (size_t)oh * FIT_TAPS * 2;
+    std::vector<unsigned char> host(n_off + n_cx + n_cy, 0);
+    memcpy(host.data(), ox, (size_t)ow * 4);
+    memcpy(host.data() + (size_t)ow * 4, oy, (size_t)oh * 4);
+    for (int a = 0; a < 2; ++a) {
+        int16_t* rows = (int16_t*)(host.data() + n_off + (a ? n_cx : 0));
+        for (long long o = 0; o < m[a]; ++o) memcpy(rows + o * FIT_TAPS, coef[a] + o * taps[a], (size_t)taps[a] * 2);
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMalloc(&f->tab, host.size()));
+    const hipError_t e = hipMemcpy(f->tab, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(f->tab);
+        return fail(MOE_EHIP, "moe_fit_create: the tables' upload failed: %s", hipGetErrorString(e));
+    }
+    const unsigned char* d = (const unsigned char*)f->tab;
+    f->ax = FitAxis{(const int*)d, (const short*)(d + n_off), taps_x};
+    f->ay = FitAxis{(const int*)(d + (size_t)ow * 4), (const short*)(d + n_off + n_cx), taps_y};
+    *out = f.release();
+    return MOE_OK;
+}
+
+int moe_fit_run(const moe_fit* f, const void* src, void* dst, void* stream)
+{
+    if (!f || !src || !dst) return fail(MOE_EINVAL, "moe_fit_run: NULL argument");
+    if (int rc = poly_aligned_check("moe_fit_run", src, f->ds, dst, f->dd)) return rc;
+    HIP_TRY(hipSetDevice(f->device));
+    launch_fit(src, f->ds, f->h, f->w, dst, f->dd, f->oh, f->ow, f->planes, f->th, f->lds, f->ax, f->ay, (hipStream_t)stream);
+    return launched("resize_kernel_fit");
+}
+
+int moe_fit_info(const moe_fit* f, int64_t info[4])
+{
+    if (!f || !info) return fail(MOE_EINVAL, "moe_fit_info: NULL argument");
+    info[0] = FIT_TW; info[1] = f->th; info[2] = (int64_t)f->lds; info[3] = f->planes;
+    return MOE_OK;
+}
+
+void moe_fit_destroy(moe_fit* f)
+{
+    if (!f) return;
+    if (f->tab) {
+        (void)hipSetDevice(f->device);
+        (void)hipFree(f->tab);
+    }
+    delete f;
+}
+
+}  // extern "C"

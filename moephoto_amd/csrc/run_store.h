@@ -1,4 +1,5 @@
-// run_store.h -- the run of elements a thread writes at once (the stitch fold's edges, resize_kernel_codes): whole 16-byte stores where the address allows them.
+// run_store.h -- the run of elements a thread writes at once (the stitch fold's edges, the luma-only steps' split and merge, the polyphase kernels): whole 16-byte stores
+// where the address allows them, and the one store of a row's ragged end.
 #pragma once
 #include "common.h"
 
@@ -21,5 +22,22 @@ __device__ __forceinline__ void stitch_store(T* p, const StitchRun<T, N>& v)
     } else {
 #pragma unroll
         for (int k = 0; k < N; ++k) p[k] = v.e[k];
+    }
+}
+
+// The first n pixels of a run of eight, N / 8 elements each: whole runs through stitch_store, the ragged end element by element (constant indices in loops of eight
+// that unroll: a run indexed by a loop variable is moved to LDS)
+template <typename T, int N>
+__device__ __forceinline__ void stitch_store_n(T* p, const StitchRun<T, N>& v, int n)
+{
+    constexpr int G = N / 8;
+    if (n == 8) stitch_store(p, v);
+    else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (e >= n) break;
+#pragma unroll
+            for (int c = 0; c < G; ++c) p[e * G + c] = v.e[e * G + c];
+        }
     }
 }

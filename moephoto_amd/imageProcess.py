@@ -903,6 +903,15 @@ def toPlanes(depth):
     return f
 
 
+def _flatPair(who, what, src, n_in, out, n_out):
+    """What resampleChroma's and fitPlanes' f check of their two buffers: one HIP device, flat contiguous uint8 tensors of exactly n_in and n_out bytes."""
+    if src.device.type != 'cuda' or out.device != src.device:
+        raise _lib.EngineError('{}: both {} must live on one HIP device (moephoto_amd has no CPU path)'.format(who, what))
+    for t, n in ((src, n_in), (out, n_out)):
+        if tuple(t.shape) != (n,) or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError('{}: a flat contiguous uint8 tensor of {} bytes expected, got {} {}'.format(who, n, t.dtype, tuple(t.shape)))
+
+
 def resampleChroma(srcFmt, dstFmt, w, h, scale, method, loc='center'):
     """The chroma planes of a luma-only chain (moe_chroma_resample; the definition: pixfmt.resampleChroma): f(raw_dev, out) reads the Cb and Cr planes of the planar
     4:2:0 frame of w x h in raw_dev (a flat uint8 device tensor of pixfmt.frameBytes(srcFmt, w, h)) and writes them, `scale` times as large and at dstFmt's depth,
@@ -913,18 +922,13 @@ def resampleChroma(srcFmt, dstFmt, w, h, scale, method, loc='center'):
         raise ValueError('pixFmt "{}" is not supported ({})'.format(dstFmt, ', '.join(pixfmt.FORMATS)))
     (ox, cx), (oy, cy) = pixfmt.chromaTable(method, scale, loc), pixfmt.chromaTable(method, scale, 'center')
     taps = pixfmt.CHROMA_METHODS[method]
-    flat = lambda rows: [c for row in rows for c in row]
-    tabs = ((ctypes.c_int16 * (scale * taps))(*flat(cx)), (ctypes.c_int8 * scale)(*ox), (ctypes.c_int16 * (scale * taps))(*flat(cy)), (ctypes.c_int8 * scale)(*oy))
+    tabs = ((ctypes.c_int16 * (scale * taps))(*sum(cx, [])), (ctypes.c_int8 * scale)(*ox), (ctypes.c_int16 * (scale * taps))(*sum(cy, [])), (ctypes.c_int8 * scale)(*oy))
     n_in, n_out = pixfmt.frameBytes(srcFmt, w, h), pixfmt.frameBytes(dstFmt, w * scale, h * scale)
     at_in, at_out = pixfmt.planeOffsets(srcFmt, w, h)[1], pixfmt.planeOffsets(dstFmt, w * scale, h * scale)[1]
     Ds, Dd = pixfmt.FORMATS[srcFmt], pixfmt.FORMATS[dstFmt]
 
     def f(raw_dev, out):
-        if raw_dev.device.type != 'cuda' or out.device != raw_dev.device:
-            raise _lib.EngineError('resampleChroma: both frames must live on one HIP device (moephoto_amd has no CPU path)')
-        for t, n in ((raw_dev, n_in), (out, n_out)):
-            if tuple(t.shape) != (n,) or t.dtype != torch.uint8 or not t.is_contiguous():
-                raise ValueError('resampleChroma: a flat contiguous uint8 tensor of {} bytes expected, got {} {}'.format(n, t.dtype, tuple(t.shape)))
+        _flatPair('resampleChroma', 'frames', raw_dev, n_in, out, n_out)
         cur = torch.cuda.current_stream(raw_dev.device)
         _lib.check(_lib.lib().moe_chroma_resample(raw_dev.data_ptr() + at_in, Ds, ch, cw, out.data_ptr() + at_out, Dd, scale, taps, *tabs,
                                                   raw_dev.device.index or 0, cur.cuda_stream))
@@ -991,11 +995,7 @@ def fitPlanes(srcDepth, dstDepth, planes, h, w, oh, ow, method, loc='center'):
         return handles[device]
 
     def f(src_dev, out):
-        if src_dev.device.type != 'cuda' or out.device != src_dev.device:
-            raise _lib.EngineError('fitPlanes: both buffers must live on one HIP device (moephoto_amd has no CPU path)')
-        for t, n in ((src_dev, n_in), (out, n_out)):
-            if tuple(t.shape) != (n,) or t.dtype != torch.uint8 or not t.is_contiguous():
-                raise ValueError('fitPlanes: a flat contiguous uint8 tensor of {} bytes expected, got {} {}'.format(n, t.dtype, tuple(t.shape)))
+        _flatPair('fitPlanes', 'buffers', src_dev, n_in, out, n_out)
         cur = torch.cuda.current_stream(src_dev.device)
         _lib.check(_lib.lib().moe_fit_run(handle(src_dev.device)._h, src_dev.data_ptr(), out.data_ptr(), cur.cuda_stream))
         src_dev.record_stream(cur)

@@ -156,6 +156,24 @@ CHROMA_LOCS = ('center', 'left')
 CHROMA_ONE = 1 << 14
 
 
+def _cubic(x):
+    """torch's cubic convolution with A = -3/4 at x, an exact fraction (cubic1 / cubic2 of misc_kernels.hip); 0 from |x| = 2 on."""
+    from fractions import Fraction as Fr
+    A, x = Fr(-3, 4), abs(x)
+    if x <= 1:
+        return ((A + 2) * x - (A + 3)) * x * x + 1
+    return ((A * x - 5 * A) * x + 8 * A) * x - 4 * A if x < 2 else Fr(0)
+
+
+def _quantRow(weights):
+    """Exact weights that sum to 1 -> 14-bit coefficients that sum to 2^14: floor(w 2^14 + 1/2) each, the deficit added to the tap of largest magnitude (the first of equals)."""
+    from fractions import Fraction as Fr
+    from math import floor
+    c = [floor(x * CHROMA_ONE + Fr(1, 2)) for x in weights]
+    c[max(range(len(c)), key=lambda j: (abs(c[j]), -j))] += CHROMA_ONE - sum(c)
+    return c
+
+
 def chromaTable(method, scale, loc='center'):
     """(off[scale], coef[scale][taps]) of one axis, as lists of Python ints; ValueError names what is unknown."""
     from fractions import Fraction as Fr
@@ -166,9 +184,6 @@ def chromaTable(method, scale, loc='center'):
         raise ValueError('chromaLoc "{}" is not supported ({})'.format(loc, ', '.join(CHROMA_LOCS)))
     if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 16:
         raise ValueError('chroma: scale must be 1..16, got {!r}'.format(scale))
-    A = Fr(-3, 4)
-    inner = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1                  # |x| <= 1   (cubic1 of misc_kernels.hip)
-    outer = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A           # 1 < |x| < 2   (cubic2)
     off, coef = [], []
     for p in range(scale):
         r = Fr(p, scale) if loc == 'left' else Fr(2 * p + 1 - scale, 2 * scale)
@@ -177,26 +192,31 @@ def chromaTable(method, scale, loc='center'):
             coef.append([CHROMA_ONE])
             continue
         f = r - floor(r)
-        wts = [1 - f, f] if method == 'bilinear' else [outer(f + 1), inner(f), inner(1 - f), outer(2 - f)]
-        c = [floor(x * CHROMA_ONE + Fr(1, 2)) for x in wts]
-        c[max(range(len(c)), key=lambda j: (abs(c[j]), -j))] += CHROMA_ONE - sum(c)
         off.append(floor(r) - (1 if method == 'bicubic' else 0))
-        coef.append(c)
+        coef.append(_quantRow([1 - f, f] if method == 'bilinear' else [_cubic(f + 1), _cubic(f), _cubic(1 - f), _cubic(2 - f)]))
     return off, coef
 
 
-def _chromaAxis(x, off, coef, scale, axis):
-    """One pass over `axis` of an int64 array: out[o] = sum_j coef[p][j] * x[clamp(q + off[p] + j)]."""
+def _polyAxis(x, off, coef, axis):
+    """One pass over `axis` of an int64 array, off and coef per output index: out[o] = sum_j coef[o][j] * x[clamp(off[o] + j, 0, n - 1)]."""
     n = x.shape[axis]
-    o = np.arange(n * scale)
-    q, p = o // scale, o % scale
     off, coef = np.asarray(off, np.int64), np.asarray(coef, np.int64)
     shape = [1] * x.ndim
-    shape[axis] = n * scale
+    shape[axis] = len(off)
     out = 0
     for j in range(coef.shape[1]):
-        out = out + np.take(x, np.clip(q + off[p] + j, 0, n - 1), axis=axis) * coef[p, j].reshape(shape)
+        out = out + np.take(x, np.clip(off + j, 0, n - 1), axis=axis) * coef[:, j].reshape(shape)
     return out
+
+
+def _polyPlanes(x, tabX, tabY, Ds, Dd):
+    """Both passes and the quantiser on (C, h, w) integer codes; tabX / tabY = (off, coef) per output index.  The arithmetic of csrc/polyphase.h."""
+    t = _polyAxis(x.astype(np.int64), tabX[0], tabX[1], 2)
+    assert np.abs(t).max() < 1 << 31          # (summed in int64 here; the bound is what lets the device sum in int32)
+    v = _polyAxis(t, tabY[0], tabY[1], 1)
+    s = np.clip((v + (1 << 27)) >> 28, 0, (1 << Ds) - 1)
+    s = s << (Dd - Ds) if Dd >= Ds else s >> (Ds - Dd)
+    return s.astype(np.uint8 if Dd == 8 else np.dtype('<u2'))
 
 
 def resampleChroma(C, srcFmt, dstFmt, scale, method, loc='center'):
@@ -210,15 +230,10 @@ def resampleChroma(C, srcFmt, dstFmt, scale, method, loc='center'):
     x = np.asarray(C)
     if x.ndim != 3 or x.shape[0] != 2 or x.dtype.kind not in 'ui':
         raise ValueError('resampleChroma: the (2, h, w) integer codes of Cb and Cr expected, got {} {}'.format(x.dtype, x.shape))
-    x = x.astype(np.int64)
-    ox, cx = chromaTable(method, scale, loc)
-    oy, cy = chromaTable(method, scale, 'center')
-    t = _chromaAxis(x, ox, cx, scale, 2)
-    assert np.abs(t).max() < 1 << 31
-    v = _chromaAxis(t, oy, cy, scale, 1)
-    s = np.clip((v + (1 << 27)) >> 28, 0, (1 << Ds) - 1)
-    s = s << (Dd - Ds) if Dd >= Ds else s >> (Ds - Dd)
-    return s.astype(np.uint8 if Dd == 8 else np.dtype('<u2'))
+
+    def perOutput(n, off, coef):          # the phase tables as _polyAxis takes them: output o = q * scale + p reads from q + off[p] with coef[p]
+        return [o // scale + off[o % scale] for o in range(n * scale)], [coef[o % scale] for o in range(n * scale)]
+    return _polyPlanes(x, perOutput(x.shape[2], *chromaTable(method, scale, loc)), perOutput(x.shape[1], *chromaTable(method, scale, 'center')), Ds, Dd)
 
 
 # ---- fitted sizes: a rational (any n -> m) integer polyphase filter -------------------------------------------------------------------------------
@@ -240,17 +255,9 @@ _fitCache = {}
 
 
 def _fitKernel(method):
+    """(R, k): the kernel's support [-R, R] and the kernel -- bilinear: the triangle; bicubic: chromaTable's cubic convolution."""
     from fractions import Fraction as Fr
-    if method == 'bilinear':
-        return 1, lambda x: max(1 - abs(x), Fr(0))
-    A = Fr(-3, 4)
-    inner = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
-    outer = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
-
-    def cubic(x):
-        x = abs(x)
-        return inner(x) if x <= 1 else outer(x) if x < 2 else Fr(0)
-    return 2, cubic
+    return (1, lambda x: max(1 - abs(x), Fr(0))) if method == 'bilinear' else (2, _cubic)
 
 
 def fitTable(method, n, m, loc='center'):
@@ -284,9 +291,7 @@ def fitTable(method, n, m, loc='center'):
             first, last = floor(c - R * f) + 1, ceil(c + R * f) - 1
             w = [k((i - c) / f) for i in range(first, last + 1)]
             tot = sum(w)
-            q = [floor(x / tot * CHROMA_ONE + Fr(1, 2)) for x in w]
-            q[max(range(len(q)), key=lambda j: (abs(q[j]), -j))] += CHROMA_ONE - sum(q)
-            rows.append((first, q))
+            rows.append((first, _quantRow([x / tot for x in w])))
         T = max(len(q) for _, q in rows)
         off = tuple(rows[o % period][0] + (o // period) * step for o in range(m))
         coef = tuple(tuple(rows[o % period][1]) + (0,) * (T - len(rows[o % period][1])) for o in range(m))
@@ -295,18 +300,6 @@ def fitTable(method, n, m, loc='center'):
         _fitCache[key] = (off, coef)
     off, coef = _fitCache[key]
     return list(off), [list(r) for r in coef]
-
-
-def _fitAxis(x, off, coef, axis):
-    """One pass over `axis` of an integer array: out[o] = sum_j coef[o][j] * x[clamp(off[o] + j)]."""
-    n = x.shape[axis]
-    off, coef = np.asarray(off, np.int64), np.asarray(coef, np.int64)
-    shape = [1] * x.ndim
-    shape[axis] = len(off)
-    out = 0
-    for j in range(coef.shape[1]):
-        out = out + np.take(x, np.clip(off + j, 0, n - 1), axis=axis) * coef[:, j].reshape(shape)
-    return out
 
 
 def fitPlanes(P, srcDepth, dstDepth, oh, ow, method, loc='center'):
@@ -321,9 +314,4 @@ def fitPlanes(P, srcDepth, dstDepth, oh, ow, method, loc='center'):
         raise ValueError('fitPlanes: the (C, h, w) integer codes of C planes expected, got {} {}'.format(x.dtype, x.shape))
     ox, cx = fitTable(method, int(x.shape[2]), ow, loc)
     oy, cy = fitTable(method, int(x.shape[1]), oh, 'center')
-    t = _fitAxis(x.astype(np.int32), ox, cx, 2)
-    assert t.dtype == np.int64 and np.abs(t).max() < 1 << 31          # (summed in int64 here; the bound is what lets the device sum in int32)
-    v = _fitAxis(t, oy, cy, 1)
-    s = np.clip((v + (1 << 27)) >> 28, 0, (1 << srcDepth) - 1)
-    s = s << (dstDepth - srcDepth) if dstDepth >= srcDepth else s >> (srcDepth - dstDepth)
-    return s.astype(np.uint8 if dstDepth == 8 else np.dtype('<u2'))
+    return _polyPlanes(x, (ox, cx), (oy, cy), srcDepth, dstDepth)

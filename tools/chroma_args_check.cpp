@@ -1,12 +1,12 @@
 // chroma_args_check.cpp -- every refusal of moe_chroma_resample (include/moephoto_amd.h), called from a stand-alone program so that the argument validation in
-// plan_run.cpp -- the walk over the caller's coefficient and offset tables included -- can run under the host sanitizers.  No device is touched: every call must
+// polyphase.cpp -- the walk over the caller's coefficient and offset tables included -- can run under the host sanitizers.  No device is touched: every call must
 // return before its first HIP call.  The tables are heap blocks of exactly scale x taps / scale elements, so a read past either end is an AddressSanitizer report.
 //
 //   cd moephoto_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -x hip -Xarch_host -fsanitize=address,undefined \
-//       plan_run.cpp planner.cpp errors.cpp ../../tools/chroma_args_check.cpp -L.. -lmoephoto_amd -Wl,-rpath,$PWD/.. -fsanitize=address,undefined -o /tmp/chroma_args_check
+//       polyphase.cpp errors.cpp ../../tools/chroma_args_check.cpp -L.. -lmoephoto_amd -Wl,-rpath,$PWD/.. -fsanitize=address,undefined -o /tmp/chroma_args_check
 //   /tmp/chroma_args_check          (exit status 0 and "chroma_args_check: N refusals, all as declared")
 //
-// plan_run.cpp, planner.cpp and errors.cpp are compiled into the program with the sanitizers (the program's definitions win over the library's); the library only
+// polyphase.cpp and errors.cpp are compiled into the program with the sanitizers (the program's definitions win over the library's); the library only
 // supplies the kernels' launchers those files refer to.
 #include <cstdint>
 #include <cstdio>
