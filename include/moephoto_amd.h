@@ -208,6 +208,22 @@ int moe_plan_ramp(const moe_plan* plan, float* ramp);
  * tiles' own row 0, height of the tiles' output extent -- what the stitch kernel folds with (python/imageProcess.py:120-131,167-170) */
 int moe_plan_rows(const moe_plan* plan, int32_t* rows);
 
+/* ---- rounding and ordered dither in the quantising edges (the definition: moephoto_amd/quant.py) -----------------
+ * Every edge that turns a float into a sample truncates by default, as the reference does (python/imageProcess.py:245-257: v * 2^bits, clamp, truncate).  These flags are
+ * OR-ed into the `bits` argument of moe_to_output, moe_stitch_out, moe_run_plan_out, moe_stitch_mix, moe_run_plan_filter, moe_luma_merge, moe_stitch_luma and
+ * moe_run_plan_luma, and into the `depth` argument of moe_stitch_planes, moe_run_plan_planes, moe_stitch_yuv, moe_run_plan_yuv and moe_to_yuv; the low byte keeps its
+ * meaning and its checks.  With a mode the sample is trunc(clamp(fl32(fl32(v * S) + T / 128), 0, 2^bits - 1)), NaN = 0, the product and the sum rounded separately:
+ *     MOE_Q_ROUND      T = 64: round to nearest (halves up)
+ *     MOE_Q_ORDERED    T = 2 * B8[y & 7][x & 7] + 1, B8 the 8 x 8 Bayer matrix, (x, y) the sample's coordinates in the plane or image written; the interleaved channels of
+ *                      a pixel share one threshold, a chroma sample uses its chroma-plane coordinates
+ *     MOE_Q_UNIT       S = 2^bits - 1 instead of 2^bits: the inverse of moe_to_float's MOE_U8 reader (v / 255), so that exact 8-bit codes come back as they went in
+ * In the three *yuv* calls the 16-bit samples stay the truncating quantiser's and the two rounding constants of the integer conversion become thresholds (1 << (37 - D) ->
+ * T << (31 - D), 1 << (39 - D) -> T << (33 - D)): MOE_Q_ROUND is then today's frame.  Refused with MOE_EINVAL before any device call: both modes, MOE_Q_UNIT without a
+ * mode, MOE_Q_UNIT on a *yuv* call, any flag beside bits = 0 (the canvas forms), any other high bit. */
+#define MOE_Q_ROUND 0x100
+#define MOE_Q_ORDERED 0x200
+#define MOE_Q_UNIT 0x400
+
 /* ---- device-side stitch / whole-image run ------------------------------------------------------ */
 /* Fold the per-tile results into the canvas exactly as doCrop's sequential blend does.
  * tiles_dev: device buffer holding every tile's result as C contiguous fp32 planes of
@@ -230,7 +246,8 @@ int moe_stitch_band(const moe_plan* plan, int device, const float* tiles_dev, co
 /* The fold of moe_stitch_dev, the rounding of a canvas of `canvas_dtype` (MOE_F16 | MOE_F32) and the quantiser of moe_to_output in ONE pass over the pool: replaces
  * python/imageProcess.py:120-131,167-170 (blend + slice-assign), :238-243 (toFloat) and :245-257 (toOutput) for a caller that only wants the encoder's samples.
  * dst: out_h x out_w x C interleaved, MOE_U8 (bits = 8) or MOE_U16 (bits = 8 | 16), the bytes moe_stitch -> fp32 -> moe_to_output give; tile_off_dev: n_tiles int64
- * on the DEVICE, NULL = the plan's own layout.  C = 1 .. 4, any out_w.  Asynchronous on `stream`; the canvas itself never exists. */
+ * on the DEVICE, NULL = the plan's own layout.  C = 1 .. 4, any out_w.  Asynchronous on `stream`; the canvas itself never exists.  bits may carry MOE_Q_ROUND /
+ * MOE_Q_ORDERED / MOE_Q_UNIT: the quantiser rounds or dithers at the pixel's coordinates, the bytes of moe_stitch -> moe_to_output with the same flags. */
 int moe_stitch_out(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int bits,
                    void* dst, int dst_dtype, void* stream);
 /* The DN step's edge inside that fold, for plans of scale 1: replaces RGBFilter's passes behind doCrop -- strengthOp's `s * x + (1 - s) * inp` (python/imageProcess.py:562,
@@ -242,7 +259,8 @@ int moe_stitch_out(const moe_plan* plan, int device, const float* tiles_dev, con
  * (c,i,j) at inp + c*sC + i*sH + j*sW (elements; may be a view), read at the output's coordinates; alpha (NULL: none): one more plane of dtype T, element (i,j) at
  * alpha + i*aH + j*aW, copied unchanged behind the C planes.  bits = 0: dst = the canvas (C [+ 1], out_h, out_w) contiguous, dst_dtype = inp_dtype; bits = 8 | 16:
  * dst = out_h x out_w x (C [+ 1]) interleaved samples, MOE_U8 (8) or MOE_U16, as moe_stitch_out writes them; no canvas exists.  C + alpha = 1 .. 4; strength finite;
- * tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+ * tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`.  bits = 8 | 16 may carry the MOE_Q_* flags (the sample form's quantiser; alpha is a
+ * channel of its pixel and shares the threshold); beside bits = 0 they are refused. */
 int moe_stitch_mix(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C,
                    const void* inp, int inp_dtype, int64_t sC, int64_t sH, int64_t sW, const void* alpha, int64_t aH, int64_t aW,
                    double strength, int bits, void* dst, int dst_dtype, void* stream);
@@ -291,7 +309,7 @@ int moe_run_plan_ex(moe_net* net, const moe_plan* plan, const void* img, int img
                     int do_stitch, void* stream);
 
 /* doCrop + toFloat + toOutput (python/imageProcess.py:157-172,238-257): moe_run_plan_ex without shard on the plan's internal pool, its final fold replaced by
- * moe_stitch_out.  dst, canvas_dtype, bits, dst_dtype as there; asynchronous on `stream`. */
+ * moe_stitch_out.  dst, canvas_dtype, bits (with its MOE_Q_* flags), dst_dtype as there; asynchronous on `stream`. */
 int moe_run_plan_out(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                      int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
 
@@ -307,10 +325,11 @@ int moe_run_plan_out(moe_net* net, const moe_plan* plan, const void* img, int im
 #define MOE_YUV_BT2020NC 2
 #define MOE_ORDER_BGR 0        /* plane 0 is blue: the video path's frames */
 #define MOE_ORDER_RGB 1
-/* moe_stitch_out's fold with that frame behind it, for a plan of three planes; tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+/* moe_stitch_out's fold with that frame behind it, for a plan of three planes; tile_off_dev: on the DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`.
+ * depth may carry MOE_Q_ROUND (today's bytes) or MOE_Q_ORDERED (the conversion's rounding constants become Bayer thresholds: quant.yuvFromSamples16); MOE_Q_UNIT is refused. */
 int moe_stitch_yuv(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int canvas_dtype, int depth, int matrix, int order,
                    void* dst, void* stream);
-/* moe_run_plan_out with its final fold replaced by moe_stitch_yuv. */
+/* moe_run_plan_out with its final fold replaced by moe_stitch_yuv (depth and its flags as there). */
 int moe_run_plan_yuv(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                      int canvas_dtype, int depth, int matrix, int order, void* dst, int max_tiles_per_batch, void* stream);
 
@@ -327,10 +346,11 @@ int moe_planes_to_float(const void* src, int depth, int H, int W, void* dst_y, v
 /* moe_stitch_out's fold with a planar result at `depth` 8, 10, 12 or 16: dst = C (1 .. 4) planes of out_h x out_w samples, plane c at dst + c * out_h * out_w elements,
  * uint8 for depth 8, else uint16 -- per sample the bytes moe_stitch -> moe_to_output(H = C * out_h, W = out_w, C = 1, bits = depth) give, and for C = 1 at depth 8 or 16
  * those of moe_stitch_out.  dst: any 2-byte aligned address (any address for depth 8) -- the Cb plane of a frame starts wherever its Y plane ends.  tile_off_dev: on the
- * DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`. */
+ * DEVICE, NULL = the plan's own layout.  Asynchronous on `stream`.  depth may carry MOE_Q_ROUND / MOE_Q_ORDERED / MOE_Q_UNIT: each sample is rounded or dithered at its
+ * coordinates in its OWN plane (the bytes of moe_stitch -> one flagged moe_to_output per plane). */
 int moe_stitch_planes(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int depth,
                       void* dst, void* stream);
-/* moe_run_plan_out with its final fold replaced by moe_stitch_planes (C = the plan's planes). */
+/* moe_run_plan_out with its final fold replaced by moe_stitch_planes (C = the plan's planes; depth and its flags as there). */
 int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                         int canvas_dtype, int depth, void* dst, int max_tiles_per_batch, void* stream);
 
@@ -364,15 +384,15 @@ int moe_luma_split(const void* img, int dtype, int C, int64_t sC, int64_t sH, in
  * written.  y' = fp32(T(Y')), r' = y' + er cr, b' = y' + eb cb, g' = y' - (gr cr + gb cb), each rounded to T, planes in `order`, alpha behind them unchanged.
  * bits = 0: dst = the canvas (C, H, W) of dst_dtype = dtype; bits = 8 | 16: dst = (H, W, C) interleaved MOE_U8 / MOE_U16 samples, each value through moe_to_output's
  * quantiser.  Serves the chains whose Y' is a canvas (an ensemble, a blended DN, a step that is not last).  Refused as above, and: unknown bits, a dst_dtype that does
- * not fit them. */
+ * not fit them.  bits = 8 | 16 may carry the MOE_Q_* flags (the sample form's quantiser at pixel (i % W, i / W)); beside bits = 0 they are refused. */
 int moe_luma_merge(const void* y, int dtype, const void* c, int C, int H, int W, int matrix, int order, int bits, void* dst, int dst_dtype, int device, void* stream);
 /* moe_stitch_luma replaces moe_stitch -> moe_luma_merge (same bytes): the fold of a pool of P = 1 (Y') or 2 (Y', alpha) planes with the merge as its edge, so the Y'
  * canvas never exists.  c = (2, out_h, out_w) dense fp32; dst and bits as moe_luma_merge's with C = P + 2 and T = canvas_dtype.  tile_off_dev: on the DEVICE, NULL =
- * the plan's own layout.  Refused as above, and: P outside {1, 2}.  Asynchronous on `stream`. */
+ * the plan's own layout.  Refused as above, and: P outside {1, 2}.  Asynchronous on `stream`.  bits and its MOE_Q_* flags as moe_luma_merge's. */
 int moe_stitch_luma(const moe_plan* plan, int device, const float* tiles_dev, const int64_t* tile_off_dev, int P, int canvas_dtype, const void* c, int matrix, int order,
                     int bits, void* dst, int dst_dtype, void* stream);
 /* moe_run_plan_luma replaces moe_run_plan (or moe_run_plan_out) on the three colour planes: moe_run_plan on img_y (the plan's 1 or 2 planes, padded where the plan
- * pads) with its final fold replaced by moe_stitch_luma. */
+ * pads) with its final fold replaced by moe_stitch_luma (bits and its MOE_Q_* flags as there). */
 int moe_run_plan_luma(moe_net* net, const moe_plan* plan, const void* img_y, int dtype, int64_t sC, int64_t sH, int64_t sW, const void* c, int matrix, int order,
                       int bits, void* dst, int dst_dtype, int max_tiles_per_batch, void* stream);
 
@@ -398,7 +418,7 @@ void moe_fit_destroy(moe_fit* fit);
 
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
- * alpha, strength, bits, dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */
+ * alpha, strength, bits (with its MOE_Q_* flags), dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */
 int moe_run_plan_filter(moe_net* net, const moe_plan* plan, const void* img, int img_dtype, int64_t sC, int64_t sH, int64_t sW,
                         const void* alpha, int64_t aH, int64_t aW, double strength, int bits, void* dst, int dst_dtype,
                         int max_tiles_per_batch, void* stream);
@@ -475,9 +495,11 @@ int moe_run_plan_ens(moe_net* net, const moe_plan* plan, const moe_plan* plan_t,
 /* ---- image I/O edges ---------------------------------------------------------------------------- */
 /* src: H x W x C interleaved MOE_U8 (v/255) or MOE_U16 (v/2^bits); dst: C planes H x W, MOE_F32/MOE_F16 */
 int moe_to_float(const void* src, int src_dtype, int bits, int H, int W, int C, void* dst, int dst_dtype, int device, void* stream);
-/* src: C planes H x W (MOE_F32/MOE_F16); dst: H x W x C interleaved, v*2^bits clamped to [0, 2^bits-1], truncated */
+/* src: C planes H x W (MOE_F32/MOE_F16); dst: H x W x C interleaved, v*2^bits clamped to [0, 2^bits-1], truncated.  bits may carry MOE_Q_ROUND / MOE_Q_ORDERED / MOE_Q_UNIT
+ * (above): the rounding or ordered-dither quantiser, the threshold of pixel (x, y) shared by its C channels. */
 int moe_to_output(const void* src, int src_dtype, int H, int W, int C, int bits, void* dst, int dst_dtype, int device, void* stream);
-/* src: three planes H x W (MOE_F32/MOE_F16); dst: the Y'CbCr 4:2:0 frame of moe_stitch_yuv, from the samples moe_to_output gives with bits = 16 */
+/* src: three planes H x W (MOE_F32/MOE_F16); dst: the Y'CbCr 4:2:0 frame of moe_stitch_yuv, from the samples moe_to_output gives with bits = 16; depth and its flags
+ * (MOE_Q_ROUND, MOE_Q_ORDERED) as moe_stitch_yuv's */
 int moe_to_yuv(const void* src, int src_dtype, int H, int W, int depth, int matrix, int order, void* dst, int device, void* stream);
 
 /* the pipeline's `resize` step: resizeByTorch = F.interpolate(x[None], size=(h, w), mode, align_corners=False)

@@ -447,8 +447,11 @@ struct StitchArgs {
     int y0, rows;                                    // the canvas rows [y0, y0 + rows) are folded into `out` = (C, rows, out_w): the whole canvas (0, out_h) or a band (moe_stitch_band)
 };
 void launch_stitch(const StitchArgs& a, hipStream_t s);
-bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s);      // the fold + the canvas dtype's rounding + to_output's quantiser: a.out = interleaved u8 / u16
-void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s);     // the same quantiser at `depth` bits, planar: a.out = a.C planes of out_h x out_w u8 (depth 8) / u16
+// The dithered form of every quantising edge (quant.h; the definition: moephoto_amd/quant.py): sample = trunc(clamp(fl32(fl32(v S) + T / 128), 0, top)), T = 64 ('round') or the
+// 8 x 8 Bayer numerator at the sample's coordinates (ordered != 0).  The launchers below take a pointer to one: NULL = today's truncating quantiser, today's kernels.
+struct QuantDither { float S, top; int ordered; };
+bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s, const QuantDither* dq = nullptr);      // the fold + the canvas dtype's rounding + to_output's quantiser: a.out = interleaved u8 / u16
+void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s, const QuantDither* dq = nullptr);     // the same quantiser at `depth` bits, planar: a.out = a.C planes of out_h x out_w u8 (depth 8) / u16
 // The DN step's edge inside the stitch (stitch_mix_kernel, plans of scale 1): what RGBFilter does behind doCrop.  T = the canvas dtype.
 struct StitchMix {
     const void* inp; long long sC, sH, sW;           // the image the net saw, dtype T: element (c, y, x) at inp + c sC + y sH + x sW (elements); its top-left out_h x out_w is read
@@ -458,7 +461,7 @@ struct StitchMix {
     int inp_vec, alpha_vec;                          // set by launch_stitch_mix: rows may be read as 16-byte vectors
     long long once_from; int q_once;                 // set by launch_stitch_mix, fp16: from this element of the (C, H, W) result on / for inp everywhere a product is rounded once, as torch's kernels do
 };
-bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s);
+bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s, const QuantDither* dq = nullptr);
 // The encoder's planar Y'CbCr 4:2:0 frame behind the fold (stitch_yuv_kernel) or behind three dense planes (to_output_yuv_kernel); the definition: moephoto_amd/pixfmt.py.
 // dst = the Y plane H x W, then Cb, then Cr of ceil(H / 2) x ceil(W / 2), uint8 (depth 8) or uint16.  The shifts of the definition are folded into the multipliers:
 // (L 219 + 2^(37 - D)) >> (38 - D) = (L (219 << (D - 6)) + 2^31) >> 32, the high word of one 32 x 32 + 64 bit multiply-add; chroma likewise with 224 << (D - 8).
@@ -467,18 +470,20 @@ struct YuvEdge {
     unsigned mul_y, base_y; int mul_c, base_c;       // 219 << (D - 6), 16 << (D - 8);  224 << (D - 8), 128 << (D - 8)
     int depth, f16;                                  // D;  the samples are taken from the value rounded to fp16 (what an fp16 canvas held)
 };
-void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s);      // C = 3, the whole canvas; a.out = the frame
-void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s);
+// dither: 0 = today's kernels; 1 = 'round', 2 = 'ordered': the 2^31 behind each folded multiply becomes T << 25 (T = 64: the same bytes), a chroma sample at its chroma-plane coordinates
+void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s, int dither = 0);      // C = 3, the whole canvas; a.out = the frame
+void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s, int dither = 0);
 // Luma-only steps on RGB images (the definition: moephoto_amd/luma.py; the arithmetic: luma.h): the net runs on Y' alone, Cb / Cr ride around it as two fp32 planes.
 // The constants of a matrix, each computed in double and rounded once to fp32.
 struct LumaCoef { float kr, kg, kb, ib, ir, eb, er, gr, gb; };
 // The merge behind the fold (stitch_luma_kernel): a.C = the pool's planes (Y', and alpha behind it when 2); c = Cb then Cr, dense fp32 planes of out_h x out_w;
 // rp = the plane red goes to (0: 'rgb', 2: 'bgr'); quant = 0: a.out = the canvas (a.C + 2, out_h, out_w) of the canvas dtype, else 2^bits: interleaved u8 / u16 samples.
 struct StitchLuma { const float* c; LumaCoef k; int rp; float quant; };
-bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s);
+bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s, const QuantDither* dq = nullptr);
 // luma.hip: a strided (C = 3 | 4, H, W) image -> dense Y (C - 2 planes of its dtype: Y', alpha) and dense Cb, Cr (fp32); and the merge on dense planes (quant as above)
 void launch_luma_split(const void* img, int dtype, int C, long long sC, long long sH, long long sW, int H, int W, const LumaCoef& k, int rp, void* dst_y, float* dst_c, hipStream_t s);
-void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, int W, const LumaCoef& k, int rp, float quant, void* dst, int dst_dtype, hipStream_t s);
+void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, int W, const LumaCoef& k, int rp, float quant, void* dst, int dst_dtype, hipStream_t s,
+                       const QuantDither* dq = nullptr);
 
 // blend.hip: the two blend() calls + slice-assign of doCrop's loop body for ONE tile, in the canvas dtype (moe_blend_tile)
 struct BlendTileArgs {
@@ -518,7 +523,7 @@ long long wire_rec_words(const WireRec& r);
 void launch_wire(bool pack, float* tiles, unsigned* wire, const WireRec* recs, int n, long long max_elems, hipStream_t s);
 
 void launch_to_float(const void* src, int src_dtype, float inv_or_div, bool divide, int H, int W, int C, void* dst, int dst_dtype, hipStream_t s);
-void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s);
+void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s, const QuantDither* dq = nullptr);
 // a planar 4:2:0 frame of H x W (u8 for depth 8, else u16) -> dst_y (1, H, W) and dst_c (2, H / 2, W / 2), code * 2^-depth (moephoto_amd/pixfmt.py: toPlanes)
 void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_y, void* dst_c, int dst_dtype, hipStream_t s);
 // chroma.hip: one axis of moe_chroma_resample's polyphase filter, by value in the kernel's arguments: output phase p reads TAPS source samples from off[p] on

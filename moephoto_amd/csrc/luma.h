@@ -56,15 +56,7 @@ __device__ __forceinline__ void luma_merge_planes(const LumaCoef& k, float y, fl
     p2 = rp == 0 ? b : r;
 }
 
-// to_output_kernel's quantiser: v * quant, clamp to [0, quant - 1], truncate, NaN = 0
-template <typename TD>
-__device__ __forceinline__ TD luma_quant(float v, float quant)
-{
-    v = v * quant;
-    v = fminf(fmaxf(v, 0.f), quant - 1.f);
-    if (!(v == v)) v = 0.f;
-    return (TD)(int)v;
-}
+// (the quantiser of the sample forms is quant.h's quant_sample)
 
 // Eight elements from p with element stride sW; vec: p is 16-byte aligned and sW == 1 (whole runs only).  n < 8: the ragged end of a row, the last element repeated.
 template <typename T>

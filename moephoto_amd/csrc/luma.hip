@@ -4,6 +4,7 @@
 // plane through the net (python/runSR.py:37-40).  The merge of a chain whose last fold can write the result itself is stitch.hip's LumaEdge; this file's merge serves the
 // chains whose Y' is a canvas (an ensemble, a blended DN, a step that is not last).
 #include "luma.h"
+#include "quant.h"
 #include <type_traits>
 #include "../../include/moephoto_amd.h"
 
@@ -50,8 +51,10 @@ __global__ __launch_bounds__(256) void to_float_luma_kernel(const T* __restrict_
 
 // The merge on dense planes: y = CT - 2 planes of H x W (T), c = Cb, Cr (fp32).  Dense, so the planes are flat arrays of HW elements: one thread = eight consecutive
 // elements.  TD == T: dst = the canvas (CT, H, W); else dst = (H, W, CT) interleaved samples through to_output_kernel's quantiser, each value rounded to T first.
-template <typename T, typename TD, int CT>
-__global__ __launch_bounds__(256) void to_output_luma_kernel(const T* __restrict__ y, const float* __restrict__ c, long long HW, int rp, LumaCoef k, float quant, TD* __restrict__ dst)
+// DITHER (to_output_luma_dither_kernel, the sample form only): quant.h's rounding / ordered-dither quantiser at the pixel's coordinates (i % W, i / W) -- the bytes of the fold's
+// dithered LumaEdge.
+template <typename T, typename TD, int CT, bool DITHER>
+__device__ __forceinline__ void to_output_luma_body(const T* __restrict__ y, const float* __restrict__ c, long long HW, int rp, const LumaCoef& k, const Quant<DITHER>& q, int W, TD* __restrict__ dst)
 {
     constexpr bool SAMPLE = !std::is_same<T, TD>::value;
     const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
@@ -73,10 +76,19 @@ __global__ __launch_bounds__(256) void to_output_luma_kernel(const T* __restrict
     }
     if constexpr (SAMPLE) {
         StitchRun<TD, 8 * CT> s;
+        int px[8], py[8];          // (DITHER only: the eight pixels' coordinates, one division per thread)
+        if constexpr (DITHER) {
+            px[0] = (int)(i0 % W); py[0] = (int)(i0 / W);
+#pragma unroll
+            for (int e = 1; e < 8; ++e) {
+                const bool wrap = px[e - 1] + 1 == W;
+                px[e] = wrap ? 0 : px[e - 1] + 1; py[e] = py[e - 1] + (wrap ? 1 : 0);
+            }
+        }
 #pragma unroll
         for (int p = 0; p < CT; ++p)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) s.e[e * CT + p] = luma_quant<TD>((float)o[p][e], quant);
+            for (int e = 0; e < 8; ++e) s.e[e * CT + p] = quant_sample<TD>((float)o[p][e], false, q, DITHER ? px[e] : 0, DITHER ? py[e] : 0);
         stitch_store_n(dst + i0 * CT, s, n);
     } else {
 #pragma unroll
@@ -89,10 +101,29 @@ __global__ __launch_bounds__(256) void to_output_luma_kernel(const T* __restrict
     }
 }
 
+template <typename T, typename TD, int CT>
+__global__ __launch_bounds__(256) void to_output_luma_kernel(const T* __restrict__ y, const float* __restrict__ c, long long HW, int rp, LumaCoef k, float quant, TD* __restrict__ dst)
+{
+    to_output_luma_body<T, TD, CT, false>(y, c, HW, rp, k, Quant<false>{quant}, 0, dst);
+}
+
+template <typename T, typename TD, int CT>
+__global__ __launch_bounds__(256) void to_output_luma_dither_kernel(const T* __restrict__ y, const float* __restrict__ c, long long HW, int rp, LumaCoef k, QuantDither d, int W, TD* __restrict__ dst)
+{
+    to_output_luma_body<T, TD, CT, true>(y, c, HW, rp, k, Quant<true>{d}, W, dst);
+}
+
 template <typename T, typename TD>
-void launch_luma_merge_t(const void* y, const float* c, int C, long long HW, const LumaCoef& k, int rp, float quant, void* dst, hipStream_t s)
+void launch_luma_merge_t(const void* y, const float* c, int C, long long HW, const LumaCoef& k, int rp, float quant, void* dst, hipStream_t s, const QuantDither* dq = nullptr, int W = 0)
 {
     const dim3 g((unsigned)(((HW + 7) / 8 + 255) / 256));
+    if constexpr (!std::is_same<T, TD>::value) {
+        if (dq) {
+            if (C == 3) hipLaunchKernelGGL((to_output_luma_dither_kernel<T, TD, 3>), g, dim3(256), 0, s, (const T*)y, c, HW, rp, k, *dq, W, (TD*)dst);
+            else hipLaunchKernelGGL((to_output_luma_dither_kernel<T, TD, 4>), g, dim3(256), 0, s, (const T*)y, c, HW, rp, k, *dq, W, (TD*)dst);
+            return;
+        }
+    }
     if (C == 3) hipLaunchKernelGGL((to_output_luma_kernel<T, TD, 3>), g, dim3(256), 0, s, (const T*)y, c, HW, rp, k, quant, (TD*)dst);
     else hipLaunchKernelGGL((to_output_luma_kernel<T, TD, 4>), g, dim3(256), 0, s, (const T*)y, c, HW, rp, k, quant, (TD*)dst);
 }
@@ -109,7 +140,7 @@ void launch_luma_split(const void* img, int dtype, int C, long long sC, long lon
 }
 
 // quant == 0: dst = the canvas (C, H, W) of `dtype`; else dst = (H, W, C) of dst_dtype MOE_U8 / MOE_U16
-void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, int W, const LumaCoef& k, int rp, float quant, void* dst, int dst_dtype, hipStream_t s)
+void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, int W, const LumaCoef& k, int rp, float quant, void* dst, int dst_dtype, hipStream_t s, const QuantDither* dq)
 {
     const long long HW = (long long)H * W;
     const bool f16 = dtype == MOE_F16;
@@ -117,10 +148,10 @@ void launch_luma_merge(const void* y, int dtype, const float* c, int C, int H, i
         if (f16) launch_luma_merge_t<half_t, half_t>(y, c, C, HW, k, rp, quant, dst, s);
         else launch_luma_merge_t<float, float>(y, c, C, HW, k, rp, quant, dst, s);
     } else if (dst_dtype == MOE_U8) {
-        if (f16) launch_luma_merge_t<half_t, uint8_t>(y, c, C, HW, k, rp, quant, dst, s);
-        else launch_luma_merge_t<float, uint8_t>(y, c, C, HW, k, rp, quant, dst, s);
+        if (f16) launch_luma_merge_t<half_t, uint8_t>(y, c, C, HW, k, rp, quant, dst, s, dq, W);
+        else launch_luma_merge_t<float, uint8_t>(y, c, C, HW, k, rp, quant, dst, s, dq, W);
     } else {
-        if (f16) launch_luma_merge_t<half_t, uint16_t>(y, c, C, HW, k, rp, quant, dst, s);
-        else launch_luma_merge_t<float, uint16_t>(y, c, C, HW, k, rp, quant, dst, s);
+        if (f16) launch_luma_merge_t<half_t, uint16_t>(y, c, C, HW, k, rp, quant, dst, s, dq, W);
+        else launch_luma_merge_t<float, uint16_t>(y, c, C, HW, k, rp, quant, dst, s, dq, W);
     }
 }

@@ -2,6 +2,7 @@
 // squeeze-excite pooling / gates, and the uint8/uint16 <-> float image edges.
 // All of them stream NHWC fp16 activations with 16-byte accesses (8 lanes = one 128-B pixel line).
 #include "common.h"
+#include "quant.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -1106,6 +1107,18 @@ __global__ void to_output_kernel(const TS* src, TD* dst, int H, int W, int C, fl
     dst[idx] = (TD)(int)v;
 }
 
+// The rounding / ordered-dither form (moe_to_output's MOE_Q_ROUND / MOE_Q_ORDERED; quant.h): the same element map, the threshold of pixel (p % W, p / W) for all its channels.
+template <typename TS, typename TD>
+__global__ void to_output_dither_kernel(const TS* src, TD* dst, int H, int W, int C, QuantDither d)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n = (long long)H * W * C;
+    if (idx >= n) return;
+    const int c = (int)(idx % C);
+    const long long p = idx / C;
+    dst[idx] = quant_sample<TD, true>((float)src[(long long)c * H * W + p], false, d.S, d.top, d.ordered != 0, (int)(p % W), (int)(p / W));
+}
+
 // Three-channel images, eight pixels per thread (H * W % 8 == 0, aligned bases): the per-element kernels above move one 1..4-byte element per thread with a
 // stride of C elements on the interleaved side (1.3 TB/s on the 8K canvas); here a thread moves 8 x 3 interleaved elements as one contiguous run and 8
 // consecutive elements of each plane as one vector.  Same arithmetic per element.
@@ -1145,6 +1158,28 @@ __global__ __launch_bounds__(256) void to_output3_kernel(const TS* __restrict__ 
             if (!(v == v)) v = 0.f;
             o.e[e * 3 + c] = (TD)(int)v;
         }
+    }
+    *(VecN<TD, 24>*)(dst + p0 * 3) = o;
+}
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void to_output3_dither_kernel(const TS* __restrict__ src, TD* __restrict__ dst, long long HW, int W, QuantDither d)
+{
+    const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (p0 >= HW) return;
+    int px[8], py[8];          // the eight pixels' coordinates: a run may cross a row end (W need not be a multiple of 8)
+    px[0] = (int)(p0 % W); py[0] = (int)(p0 / W);
+#pragma unroll
+    for (int e = 1; e < 8; ++e) {
+        const bool wrap = px[e - 1] + 1 == W;
+        px[e] = wrap ? 0 : px[e - 1] + 1; py[e] = py[e - 1] + (wrap ? 1 : 0);
+    }
+    VecN<TD, 24> o;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const VecN<TS, 8> in = *(const VecN<TS, 8>*)(src + c * HW + p0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.e[e * 3 + c] = quant_sample<TD, true>((float)in.e[e], false, d.S, d.top, d.ordered != 0, px[e], py[e]);
     }
     *(VecN<TD, 24>*)(dst + p0 * 3) = o;
 }
@@ -1384,10 +1419,27 @@ void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_
     }
 }
 
-void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s)
+void launch_to_output(const void* src, int src_dtype, int H, int W, int C, float quant, void* dst, int dst_dtype, hipStream_t s, const QuantDither* dq)
 {
     const long long n = (long long)H * W * C, HW = (long long)H * W;
     const dim3 blk(256);
+    if (dq) {          // the same choice between the two forms, their dithered twins
+        const bool f16 = src_dtype == MOE_F16, u8 = dst_dtype == MOE_U8;
+        if (C == 3 && HW % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+            const dim3 g3((unsigned)((HW / 8 + 255) / 256));
+            if (f16 && u8) hipLaunchKernelGGL((to_output3_dither_kernel<half_t, uint8_t>), g3, blk, 0, s, (const half_t*)src, (uint8_t*)dst, HW, W, *dq);
+            else if (f16) hipLaunchKernelGGL((to_output3_dither_kernel<half_t, uint16_t>), g3, blk, 0, s, (const half_t*)src, (uint16_t*)dst, HW, W, *dq);
+            else if (u8) hipLaunchKernelGGL((to_output3_dither_kernel<float, uint8_t>), g3, blk, 0, s, (const float*)src, (uint8_t*)dst, HW, W, *dq);
+            else hipLaunchKernelGGL((to_output3_dither_kernel<float, uint16_t>), g3, blk, 0, s, (const float*)src, (uint16_t*)dst, HW, W, *dq);
+            return;
+        }
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (f16 && u8) hipLaunchKernelGGL((to_output_dither_kernel<half_t, uint8_t>), grid, blk, 0, s, (const half_t*)src, (uint8_t*)dst, H, W, C, *dq);
+        else if (f16) hipLaunchKernelGGL((to_output_dither_kernel<half_t, uint16_t>), grid, blk, 0, s, (const half_t*)src, (uint16_t*)dst, H, W, C, *dq);
+        else if (u8) hipLaunchKernelGGL((to_output_dither_kernel<float, uint8_t>), grid, blk, 0, s, (const float*)src, (uint8_t*)dst, H, W, C, *dq);
+        else hipLaunchKernelGGL((to_output_dither_kernel<float, uint16_t>), grid, blk, 0, s, (const float*)src, (uint16_t*)dst, H, W, C, *dq);
+        return;
+    }
     if (C == 3 && HW % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
         const dim3 g3((unsigned)((HW / 8 + 255) / 256));
         if (src_dtype == MOE_F16) {

@@ -203,7 +203,33 @@ static int stitch_tables(const moe_plan& pl, int device, int C, StitchTables** o
 // (moe_stitch_planes: the whole canvas).
 // With luma the C planes are Y' (and alpha) and `out` receives the C + 2 colour planes of a luma-only step's merge
 // (moe_stitch_luma: canvas or samples, luma->quant says which).
-struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; int planes_depth = 0; const StitchLuma* luma = nullptr; };
+// dq: the rounding / ordered-dither quantiser of the sample forms (MOE_Q_*: quant_flags below), NULL = today's; yuv_dither: the same request for the Y'CbCr edge (0, 1 = round, 2 = ordered).
+struct OutEdge { int canvas_dtype; float quant; const StitchMix* mix = nullptr; const YuvEdge* yuv = nullptr; int planes_depth = 0; const StitchLuma* luma = nullptr;
+                 const QuantDither* dq = nullptr; int yuv_dither = 0; };
+
+// The MOE_Q_* flags OR-ed into a `bits` / `depth` argument, checked before any device call.  low: the argument's low byte, validated by the caller exactly as before; an
+// argument with any other high bit (or a negative one) is handed on whole, so that the caller's own check refuses it as the unknown bits / depth it always was.
+// dither: 0 = none, 1 = MOE_Q_ROUND, 2 = MOE_Q_ORDERED.  unit_ok: the edge has a unit scale (the three *yuv* calls quantise in integers: they have none).
+struct QuantReq {
+    int low = 0, dither = 0; bool unit = false; QuantDither d{};
+    const QuantDither* dq() { return dither ? &d : nullptr; }
+    void fill() { const float top = (float)((1 << low) - 1); d = QuantDither{unit ? top : top + 1.f, top, dither == 2}; }      // (after the caller has validated low)
+};
+static int quant_flags(const char* who, int arg, bool unit_ok, QuantReq* q)
+{
+    const int known = MOE_Q_ROUND | MOE_Q_ORDERED | MOE_Q_UNIT, flags = arg & ~0xff;
+    *q = QuantReq{};
+    q->low = arg;
+    if (arg < 0 || (flags & ~known)) return MOE_OK;
+    q->low = arg & 0xff;
+    if ((flags & MOE_Q_ROUND) && (flags & MOE_Q_ORDERED)) return fail(MOE_EINVAL, "%s: MOE_Q_ROUND and MOE_Q_ORDERED are both set (one mode at most)", who);
+    if ((flags & MOE_Q_UNIT) && !(flags & (MOE_Q_ROUND | MOE_Q_ORDERED))) return fail(MOE_EINVAL, "%s: MOE_Q_UNIT without MOE_Q_ROUND or MOE_Q_ORDERED (the truncating quantiser has no unit scale)", who);
+    if ((flags & MOE_Q_UNIT) && !unit_ok) return fail(MOE_EINVAL, "%s: MOE_Q_UNIT does not apply to the Y'CbCr edge (its samples are quantised in integers)", who);
+    if (flags && q->low == 0) return fail(MOE_EINVAL, "%s: MOE_Q_* flags beside bits = 0 (the canvas form quantises nothing)", who);
+    q->dither = flags & MOE_Q_ROUND ? 1 : flags & MOE_Q_ORDERED ? 2 : 0;
+    q->unit = (flags & MOE_Q_UNIT) != 0;
+    return MOE_OK;
+}
 static int stitch(const moe_plan& pl, int device, const float* tiles, const int64_t* tile_off, bool off_on_host, int C, void* out, int out_dtype, const int* band, hipStream_t s,
                   const OutEdge* edge = nullptr)
 {
@@ -255,23 +281,23 @@ static int stitch(const moe_plan& pl, int device, const float* tiles, const int6
         }
     }
     if (edge && edge->yuv) {
-        launch_stitch_yuv(a, *edge->yuv, s);
+        launch_stitch_yuv(a, *edge->yuv, s, edge->yuv_dither);
         return launched("stitch_yuv");
     }
     if (edge && edge->planes_depth) {
-        launch_stitch_planes(a, edge->canvas_dtype, edge->planes_depth, s);
+        launch_stitch_planes(a, edge->canvas_dtype, edge->planes_depth, s, edge->dq);
         return launched("stitch_planes");
     }
     if (edge && edge->luma) {
-        if (!launch_stitch_luma(a, *edge->luma, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_luma: %d pool planes (1 or 2 are supported)", C);
+        if (!launch_stitch_luma(a, *edge->luma, edge->canvas_dtype, s, edge->dq)) return fail(MOE_EINVAL, "moe_stitch_luma: %d pool planes (1 or 2 are supported)", C);
         return launched("stitch_luma");
     }
     if (edge && edge->mix) {
-        if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
+        if (!launch_stitch_mix(a, *edge->mix, edge->canvas_dtype, s, edge->dq)) return fail(MOE_EINVAL, "moe_stitch_mix: %d planes (1 to 4 are supported)", C + (edge->mix->alpha ? 1 : 0));
         return launched("stitch_mix");
     }
     if (edge) {
-        if (!launch_stitch_out(a, edge->canvas_dtype, edge->quant, s)) return fail(MOE_EINVAL, "moe_stitch_out: %d planes (1 to 4 are supported)", C);
+        if (!launch_stitch_out(a, edge->canvas_dtype, edge->quant, s, edge->dq)) return fail(MOE_EINVAL, "moe_stitch_out: %d planes (1 to 4 are supported)", C);
         return launched("stitch_out");
     }
     launch_stitch(a, s);
@@ -592,9 +618,14 @@ int moe_stitch_band(const moe_plan* p, int device, const float* tiles_dev, const
 int moe_stitch_out(const moe_plan* p, int device, const float* tiles_dev, const int64_t* tile_off_dev, int C, int canvas_dtype, int bits, void* dst, int dst_dtype, void* stream)
 {
     if (!p || !tiles_dev || C < 1) return fail(MOE_EINVAL, "moe_stitch_out: bad argument");
+    QuantReq q;
+    if (int rc = quant_flags("moe_stitch_out", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = out_edge_args("moe_stitch_out", C, canvas_dtype, bits, dst, dst_dtype);
     if (rc) return rc;
-    const OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    q.fill();
+    OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    edge.dq = q.dq();
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
@@ -602,8 +633,13 @@ int moe_stitch_planes(const moe_plan* p, int device, const float* tiles_dev, con
 {
     if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_planes: NULL argument");
     OutEdge edge{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_stitch_planes", depth, true, &q)) return rc;
+    depth = q.low;
     const int rc = plane_edge_args("moe_stitch_planes", C, canvas_dtype, depth, dst, &edge);
     if (rc) return rc;
+    q.fill();
+    edge.dq = q.dq();
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, depth == 8 ? MOE_U8 : MOE_U16, nullptr, (hipStream_t)stream, &edge);
 }
 
@@ -612,9 +648,14 @@ int moe_stitch_mix(const moe_plan* p, int device, const float* tiles_dev, const 
 {
     if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_mix: NULL argument");
     StitchMix m{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_stitch_mix", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = mix_edge_args("moe_stitch_mix", p->p, C, inp, inp_dtype, sC, sH, sW, alpha, aH, aW, strength, bits, dst, dst_dtype, &m);
     if (rc) return rc;
-    const OutEdge edge{inp_dtype, m.quant, &m};
+    q.fill();
+    OutEdge edge{inp_dtype, m.quant, &m};
+    edge.dq = q.dq();
     return stitch(*p, device, tiles_dev, tile_off_dev, false, C, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
@@ -622,10 +663,14 @@ int moe_stitch_yuv(const moe_plan* p, int device, const float* tiles_dev, const 
 {
     if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_yuv: NULL argument");
     YuvEdge y{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_stitch_yuv", depth, false, &q)) return rc;
+    depth = q.low;
     const int rc = yuv_edge_args("moe_stitch_yuv", p->p.C, canvas_dtype, depth, matrix, order, dst, &y);
     if (rc) return rc;
     OutEdge edge{canvas_dtype, 0.f};
     edge.yuv = &y;
+    edge.yuv_dither = q.dither;
     return stitch(*p, device, tiles_dev, tile_off_dev, false, 3, dst, depth == 8 ? MOE_U8 : MOE_U16, nullptr, (hipStream_t)stream, &edge);
 }
 
@@ -635,11 +680,16 @@ int moe_stitch_luma(const moe_plan* p, int device, const float* tiles_dev, const
     if (!p || !tiles_dev) return fail(MOE_EINVAL, "moe_stitch_luma: NULL argument");
     if (P != 1 && P != 2) return fail(MOE_EINVAL, "moe_stitch_luma: %d pool planes (1: Y', or 2: Y' and alpha)", P);
     StitchLuma m{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_stitch_luma", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = luma_edge_args("moe_stitch_luma", P + 2, canvas_dtype, c, matrix, order, bits, dst, dst_dtype, &m);
     if (rc) return rc;
+    q.fill();
     if ((uintptr_t)tiles_dev & 3) return fail(MOE_EINVAL, "moe_stitch_luma: tiles_dev is not 4-byte aligned (fp32 pool)");
     OutEdge edge{canvas_dtype, m.quant};
     edge.luma = &m;
+    edge.dq = q.dq();
     return stitch(*p, device, tiles_dev, tile_off_dev, false, P, dst, dst_dtype, nullptr, (hipStream_t)stream, &edge);
 }
 
@@ -677,9 +727,14 @@ int moe_run_plan_out(moe_net* n, const moe_plan* pl, const void* img, int img_dt
                      int canvas_dtype, int bits, void* dst, int dst_dtype, int max_tiles, void* stream)
 {
     if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_out: NULL argument");
+    QuantReq q;
+    if (int rc = quant_flags("moe_run_plan_out", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = out_edge_args("moe_run_plan_out", pl->p.C, canvas_dtype, bits, dst, dst_dtype);
     if (rc) return rc;
-    const OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    q.fill();
+    OutEdge edge{canvas_dtype, (float)(1 << bits)};
+    edge.dq = q.dq();
     return run_plan("moe_run_plan_out", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
@@ -688,8 +743,13 @@ int moe_run_plan_planes(moe_net* n, const moe_plan* pl, const void* img, int img
 {
     if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_planes: NULL argument");
     OutEdge edge{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_run_plan_planes", depth, true, &q)) return rc;
+    depth = q.low;
     const int rc = plane_edge_args("moe_run_plan_planes", pl->p.C, canvas_dtype, depth, dst, &edge);
     if (rc) return rc;
+    q.fill();
+    edge.dq = q.dq();
     return run_plan("moe_run_plan_planes", n, pl, img, img_dtype, sC, sH, sW, dst, depth == 8 ? MOE_U8 : MOE_U16, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
@@ -698,10 +758,14 @@ int moe_run_plan_yuv(moe_net* n, const moe_plan* pl, const void* img, int img_dt
 {
     if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_yuv: NULL argument");
     YuvEdge y{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_run_plan_yuv", depth, false, &q)) return rc;
+    depth = q.low;
     const int rc = yuv_edge_args("moe_run_plan_yuv", pl->p.C, canvas_dtype, depth, matrix, order, dst, &y);
     if (rc) return rc;
     OutEdge edge{canvas_dtype, 0.f};
     edge.yuv = &y;
+    edge.yuv_dither = q.dither;
     return run_plan("moe_run_plan_yuv", n, pl, img, img_dtype, sC, sH, sW, dst, depth == 8 ? MOE_U8 : MOE_U16, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
@@ -710,9 +774,14 @@ int moe_run_plan_filter(moe_net* n, const moe_plan* pl, const void* img, int img
 {
     if (!n || !pl || !img) return fail(MOE_EINVAL, "moe_run_plan_filter: NULL argument");
     StitchMix m{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_run_plan_filter", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = mix_edge_args("moe_run_plan_filter", pl->p, pl->p.C, img, img_dtype, sC, sH, sW, alpha, aH, aW, strength, bits, dst, dst_dtype, &m);
     if (rc) return rc;
-    const OutEdge edge{img_dtype, m.quant, &m};
+    q.fill();
+    OutEdge edge{img_dtype, m.quant, &m};
+    edge.dq = q.dq();
     return run_plan("moe_run_plan_filter", n, pl, img, img_dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
@@ -722,11 +791,16 @@ int moe_run_plan_luma(moe_net* n, const moe_plan* pl, const void* img_y, int dty
     if (!n || !pl || !img_y) return fail(MOE_EINVAL, "moe_run_plan_luma: NULL argument");
     if (pl->p.C != 1 && pl->p.C != 2) return fail(MOE_EINVAL, "moe_run_plan_luma: the plan has %d planes (1: Y', or 2: Y' and alpha)", pl->p.C);
     StitchLuma m{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_run_plan_luma", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = luma_edge_args("moe_run_plan_luma", pl->p.C + 2, dtype, c, matrix, order, bits, dst, dst_dtype, &m);
     if (rc) return rc;
+    q.fill();
     if ((uintptr_t)img_y & (dtype == MOE_F16 ? 1 : 3)) return fail(MOE_EINVAL, "moe_run_plan_luma: img_y is not aligned to its %d-byte elements", dtype == MOE_F16 ? 2 : 4);
     OutEdge edge{dtype, m.quant};
     edge.luma = &m;
+    edge.dq = q.dq();
     return run_plan("moe_run_plan_luma", n, pl, img_y, dtype, sC, sH, sW, dst, dst_dtype, max_tiles, nullptr, 0, 1, 1, stream, &edge);
 }
 
@@ -989,11 +1063,15 @@ int moe_luma_merge(const void* y, int dtype, const void* c, int C, int H, int W,
     if (!y) return fail(MOE_EINVAL, "moe_luma_merge: NULL argument");
     if (H < 1 || W < 1) return fail(MOE_EINVAL, "moe_luma_merge: size %d x %d must be positive", W, H);
     StitchLuma m{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_luma_merge", bits, true, &q)) return rc;
+    bits = q.low;
     const int rc = luma_edge_args("moe_luma_merge", C, dtype, c, matrix, order, bits, dst, dst_dtype, &m);
     if (rc) return rc;
+    q.fill();
     if ((uintptr_t)y & (dtype == MOE_F16 ? 1 : 3)) return fail(MOE_EINVAL, "moe_luma_merge: y is not aligned to its %d-byte elements", dtype == MOE_F16 ? 2 : 4);
     HIP_TRY(hipSetDevice(device));
-    launch_luma_merge(y, dtype, m.c, C, H, W, m.k, m.rp, m.quant, dst, dst_dtype, (hipStream_t)stream);
+    launch_luma_merge(y, dtype, m.c, C, H, W, m.k, m.rp, m.quant, dst, dst_dtype, (hipStream_t)stream, q.dq());
     return launched("to_output_luma");
 }
 
@@ -1009,11 +1087,15 @@ int moe_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h
 
 int moe_to_output(const void* src, int src_dtype, int H, int W, int C, int bits, void* dst, int dst_dtype, int device, void* stream)
 {
+    QuantReq q;
+    if (int rc = quant_flags("moe_to_output", bits, true, &q)) return rc;
+    bits = q.low;
     if (!src || !dst || H < 1 || W < 1 || C < 1 || bits < 1 || bits > 16) return fail(MOE_EINVAL, "moe_to_output: bad argument");
     if ((dst_dtype != MOE_U8 && dst_dtype != MOE_U16) || (src_dtype != MOE_F32 && src_dtype != MOE_F16)) return fail(MOE_EINVAL, "moe_to_output: bad dtype");
     if (dst_dtype == MOE_U8 && bits > 8) return fail(MOE_EINVAL, "moe_to_output: %d bits do not fit MOE_U8", bits);
     HIP_TRY(hipSetDevice(device));
-    launch_to_output(src, src_dtype, H, W, C, (float)(1 << bits), dst, dst_dtype, (hipStream_t)stream);
+    q.fill();
+    launch_to_output(src, src_dtype, H, W, C, (float)(1 << bits), dst, dst_dtype, (hipStream_t)stream, q.dq());
     return MOE_OK;
 }
 
@@ -1022,11 +1104,14 @@ int moe_to_yuv(const void* src, int src_dtype, int H, int W, int depth, int matr
     if (!src) return fail(MOE_EINVAL, "moe_to_yuv: NULL argument");
     if (H < 1 || W < 1) return fail(MOE_EINVAL, "moe_to_yuv: size %d x %d must be positive", H, W);
     YuvEdge y{};
+    QuantReq q;
+    if (int rc = quant_flags("moe_to_yuv", depth, false, &q)) return rc;
+    depth = q.low;
     const int rc = yuv_edge_args("moe_to_yuv", 3, src_dtype, depth, matrix, order, dst, &y);
     if (rc) return rc;
     y.f16 = 0;      // (the planes are the canvas: their values are converted as they are)
     HIP_TRY(hipSetDevice(device));
-    launch_to_output_yuv(src, src_dtype, H, W, y, dst, (hipStream_t)stream);
+    launch_to_output_yuv(src, src_dtype, H, W, y, dst, (hipStream_t)stream, q.dither);
     return launched("to_output_yuv");
 }
 

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "run_store.h"
 #include "luma.h"
+#include "quant.h"
 #include <type_traits>
 #include "../../include/moephoto_amd.h"
 
@@ -203,41 +204,39 @@ __global__ __launch_bounds__(256) void stitch8r_kernel(StitchArgs a)
 // their order, so the bytes are theirs.  (Times of this form and of the one-row-per-thread form before it, on the 8K frame beside the three passes:
 // profiles/frame_stream/summary.md.)
 // ---------------------------------------------------------------------------------------------------
-template <typename TD>
-__device__ __forceinline__ TD stitch_out_quant(float v, bool f16, float quant)
-{
-    if (f16) v = (float)(half_t)v;                       // what the fp16 canvas held
-    v = v * quant;                                       // to_output_kernel: image * quant, clamp_(0, quant - 1), truncate
-    v = fminf(fmaxf(v, 0.f), quant - 1.f);
-    if (!(v == v)) v = 0.f;
-    return (TD)(int)v;
-}
-
-template <typename TD, int C>
+// The quantiser is quant.h's quant_sample.  DITHER = true (the *_dither_kernel twins below, moe_stitch_out's MOE_Q_ROUND / MOE_Q_ORDERED): the rounding or ordered-dither
+// form, at the pixel's coordinates in the image -- the vector path, the seam pass (pixel()) and the ragged row end hand the same (X, Y) to it.
+template <typename TD, int C, bool DITHER = false>
 struct SamplesEdge {
     static constexpr int NP = C, NOUT = C;
     typedef StitchRun<TD, 8 * C> Row;
-    float quant; bool f16;
+    Quant<DITHER> q; bool f16;
     __device__ __forceinline__ int c0() const { return 0; }
     __device__ __forceinline__ int np(const StitchArgs&) const { return C; }
-    __device__ __forceinline__ void emit(const StitchArgs&, int, int, const float (&cur)[C][8], Row& o) const
+    __device__ __forceinline__ void emit(const StitchArgs&, int X0, int Y, const float (&cur)[C][8], Row& o) const
     {
 #pragma unroll
         for (int c = 0; c < C; ++c)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o.e[e * C + c] = stitch_out_quant<TD>(cur[c][e], f16, quant);
+            for (int e = 0; e < 8; ++e) o.e[e * C + c] = quant_sample<TD>(cur[c][e], f16, q, X0 + e, Y);
     }
     __device__ __forceinline__ void store(const StitchArgs& a, int X0, int Y, const Row& o) const { stitch_store((TD*)a.out + ((long long)Y * a.out_w + X0) * C, o); }
     __device__ __forceinline__ void pixel(const StitchArgs& a, int X, int Y, int c) const
     {
-        ((TD*)a.out)[((long long)Y * a.out_w + X) * C + c] = stitch_out_quant<TD>(stitch_pixel(a, X, Y, c), f16, quant);
+        ((TD*)a.out)[((long long)Y * a.out_w + X) * C + c] = quant_sample<TD>(stitch_pixel(a, X, Y, c), f16, q, X, Y);
     }
 };
 
 template <typename TD, int C, int R>
 __global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float quant, int f16)
 {
-    stitch_fold<R>(a, SamplesEdge<TD, C>{quant, f16 != 0});
+    stitch_fold<R>(a, SamplesEdge<TD, C>{{quant}, f16 != 0});
+}
+
+template <typename TD, int C, int R>
+__global__ __launch_bounds__(256) void stitch_out_dither_kernel(StitchArgs a, QuantDither d, int f16)
+{
+    stitch_fold<R>(a, SamplesEdge<TD, C, true>{{d}, f16 != 0});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -246,30 +245,36 @@ __global__ __launch_bounds__(256) void stitch_out_kernel(StitchArgs a, float qua
 // fromPlanes).  SamplesEdge's quantiser on CanvasEdge's layout: one plane per blockIdx.z, so a thread writes one run of eight samples per row.  The base is aligned
 // only by luck (the Cb plane starts wherever the Y plane ends, inside a frame): every run goes through stitch_store.
 // ---------------------------------------------------------------------------------------------------
-template <typename TD>
+template <typename TD, bool DITHER = false>
 struct PlaneEdge {
     static constexpr int NP = 1, NOUT = 1;
     typedef StitchRun<TD, 8> Row;
-    float quant; bool f16;
+    Quant<DITHER> q; bool f16;          // (DITHER: the thresholds at the sample's coordinates in its own plane)
     __device__ __forceinline__ int c0() const { return blockIdx.z; }
     __device__ __forceinline__ int np(const StitchArgs&) const { return 1; }
     __device__ __forceinline__ long long at(const StitchArgs& a, int X, int Y) const { return ((long long)blockIdx.z * a.out_h + Y) * a.out_w + X; }
-    __device__ __forceinline__ void emit(const StitchArgs&, int, int, const float (&cur)[1][8], Row& o) const
+    __device__ __forceinline__ void emit(const StitchArgs&, int X0, int Y, const float (&cur)[1][8], Row& o) const
     {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o.e[e] = stitch_out_quant<TD>(cur[0][e], f16, quant);
+        for (int e = 0; e < 8; ++e) o.e[e] = quant_sample<TD>(cur[0][e], f16, q, X0 + e, Y);
     }
     __device__ __forceinline__ void store(const StitchArgs& a, int X0, int Y, const Row& o) const { stitch_store((TD*)a.out + at(a, X0, Y), o); }
     __device__ __forceinline__ void pixel(const StitchArgs& a, int X, int Y, int) const
     {
-        ((TD*)a.out)[at(a, X, Y)] = stitch_out_quant<TD>(stitch_pixel(a, X, Y, blockIdx.z), f16, quant);
+        ((TD*)a.out)[at(a, X, Y)] = quant_sample<TD>(stitch_pixel(a, X, Y, blockIdx.z), f16, q, X, Y);
     }
 };
 
 template <typename TD, int R>
 __global__ __launch_bounds__(256) void stitch_planes_kernel(StitchArgs a, float quant, int f16)
 {
-    stitch_fold<R>(a, PlaneEdge<TD>{quant, f16 != 0});
+    stitch_fold<R>(a, PlaneEdge<TD>{{quant}, f16 != 0});
+}
+
+template <typename TD, int R>
+__global__ __launch_bounds__(256) void stitch_planes_dither_kernel(StitchArgs a, QuantDither d, int f16)
+{
+    stitch_fold<R>(a, PlaneEdge<TD, true>{{d}, f16 != 0});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -337,13 +342,19 @@ __device__ __forceinline__ void stitch_mix_load8(const T* p, long long sW, bool 
     }
 }
 
-template <typename T, typename TD, int CT>
+template <typename T, typename TD, int CT, bool DITHER = false>
 struct MixEdge {
     static constexpr bool SAMPLE = !std::is_same<T, TD>::value;
     static constexpr int NP = CT, NOUT = CT;
     struct Planes { StitchRun<T, 8> p[CT]; };
     typedef typename std::conditional<SAMPLE, StitchRun<TD, 8 * CT>, Planes>::type Row;      // sample form: e[pixel * CT + plane]; canvas form: p[plane].e[pixel]
     const StitchMix& m;
+    typename std::conditional<DITHER, QuantDither, QuantNone>::type d;          // the dithered sample form's quantiser (stitch_mix_dither_kernel); alpha is a channel of the pixel and shares its threshold
+    template <typename V> __device__ __forceinline__ TD quant(V v, int X, int Y) const
+    {
+        if constexpr (DITHER) return quant_sample<TD, true>((float)v, false, d.S, d.top, d.ordered != 0, X, Y);
+        else return quant_sample<TD, false>((float)v, false, m.quant, 0.f, false, X, Y);
+    }
     __device__ __forceinline__ int c0() const { return 0; }
     __device__ __forceinline__ int np(const StitchArgs& a) const { return a.C; }
     __device__ __forceinline__ void emit(const StitchArgs& a, int X0, int Y, const float (&cur)[CT][8], Row& o) const
@@ -363,7 +374,7 @@ struct MixEdge {
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                if constexpr (SAMPLE) o.e[e * CT + c] = stitch_out_quant<TD>((float)y[e], false, m.quant);
+                if constexpr (SAMPLE) o.e[e * CT + c] = quant(y[e], X0 + e, Y);
                 else o.p[c].e[e] = y[e];
             }
         }
@@ -385,7 +396,7 @@ struct MixEdge {
             const bool p_once = sizeof(T) == 2 && ((long long)c * a.out_h + Y) * a.out_w + X >= m.once_from;
             y = m.blend ? stitch_mix_value<T>(cur, ((const T*)m.inp)[c * m.sC + Y * m.sH + X * m.sW], m.sf, m.tf, p_once, p_once || m.q_once) : (T)cur;
         }
-        if constexpr (SAMPLE) ((TD*)a.out)[((long long)Y * a.out_w + X) * CT + c] = stitch_out_quant<TD>((float)y, false, m.quant);
+        if constexpr (SAMPLE) ((TD*)a.out)[((long long)Y * a.out_w + X) * CT + c] = quant(y, X, Y);
         else ((T*)a.out)[((long long)c * a.out_h + Y) * a.out_w + X] = y;
     }
 };
@@ -396,6 +407,12 @@ __global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix
     stitch_fold<R>(a, MixEdge<T, TD, CT>{m});
 }
 
+template <typename T, typename TD, int CT, int R>
+__global__ __launch_bounds__(256) void stitch_mix_dither_kernel(StitchArgs a, StitchMix m, QuantDither d)      // (the sample form only)
+{
+    stitch_fold<R>(a, MixEdge<T, TD, CT, true>{m, d});
+}
+
 // ---------------------------------------------------------------------------------------------------
 // The merge of a luma-only step in the stitch (moe_stitch_luma; the definition: moephoto_amd/luma.py, the arithmetic: luma.h): the pool holds Y' alone (and alpha behind
 // it when CT = 4), Cb / Cr come as two dense fp32 planes of the output's size, and the fold's edge writes the CT colour planes -- the Y' canvas never exists.  Per pixel
@@ -404,13 +421,19 @@ __global__ __launch_bounds__(256) void stitch_mix_kernel(StitchArgs a, StitchMix
 // TD == T: the canvas form, dst = (CT, out_h, out_w) planes; else the sample form, dst = (out_h, out_w, CT) interleaved through to_output_kernel's quantiser.
 // The chroma runs are read as 16-byte vectors where their address allows it (out_w % 4 != 0 shifts every other row).
 // ---------------------------------------------------------------------------------------------------
-template <typename T, typename TD, int CT>
+template <typename T, typename TD, int CT, bool DITHER = false>
 struct LumaEdge {
     static constexpr bool SAMPLE = !std::is_same<T, TD>::value;
     static constexpr int NP = CT - 2, NOUT = CT;
     struct Planes { StitchRun<T, 8> p[CT]; };
     typedef typename std::conditional<SAMPLE, StitchRun<TD, 8 * CT>, Planes>::type Row;      // sample form: e[pixel * CT + plane]; canvas form: p[plane].e[pixel]
     const StitchLuma& m;
+    typename std::conditional<DITHER, QuantDither, QuantNone>::type d;          // the dithered sample form's quantiser (stitch_luma_dither_kernel)
+    template <typename V> __device__ __forceinline__ TD quant(V v, int X, int Y) const
+    {
+        if constexpr (DITHER) return quant_sample<TD, true>((float)v, false, d.S, d.top, d.ordered != 0, X, Y);
+        else return quant_sample<TD, false>((float)v, false, m.quant, 0.f, false, X, Y);
+    }
     __device__ __forceinline__ int c0() const { return 0; }
     __device__ __forceinline__ int np(const StitchArgs&) const { return NP; }
     __device__ __forceinline__ void emit(const StitchArgs& a, int X0, int Y, const float (&cur)[NP][8], Row& o) const
@@ -430,7 +453,7 @@ struct LumaEdge {
         for (int c = 0; c < CT; ++c)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                if constexpr (SAMPLE) o.e[e * CT + c] = luma_quant<TD>((float)y[c][e], m.quant);
+                if constexpr (SAMPLE) o.e[e * CT + c] = quant(y[c][e], X0 + e, Y);
                 else o.p[c].e[e] = y[c][e];
             }
     }
@@ -450,7 +473,7 @@ struct LumaEdge {
             const long long at = (long long)Y * a.out_w + X;
             y = luma_canon((T)luma_merge_px(m.k, (float)(T)stitch_pixel(a, X, Y, 0), m.c[at], m.c[(long long)a.out_h * a.out_w + at], luma_colour(c, m.rp)));
         }
-        if constexpr (SAMPLE) ((TD*)a.out)[((long long)Y * a.out_w + X) * CT + c] = luma_quant<TD>((float)y, m.quant);
+        if constexpr (SAMPLE) ((TD*)a.out)[((long long)Y * a.out_w + X) * CT + c] = quant(y, X, Y);
         else ((T*)a.out)[((long long)c * a.out_h + Y) * a.out_w + X] = y;
     }
 };
@@ -459,6 +482,12 @@ template <typename T, typename TD, int CT, int R>
 __global__ __launch_bounds__(256) void stitch_luma_kernel(StitchArgs a, StitchLuma m)
 {
     stitch_fold<R>(a, LumaEdge<T, TD, CT>{m});
+}
+
+template <typename T, typename TD, int CT, int R>
+__global__ __launch_bounds__(256) void stitch_luma_dither_kernel(StitchArgs a, StitchLuma m, QuantDither d)      // (the sample form only)
+{
+    stitch_fold<R>(a, LumaEdge<T, TD, CT, true>{m, d});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -471,180 +500,69 @@ __global__ __launch_bounds__(256) void stitch_luma_kernel(StitchArgs a, StitchLu
 // per-pixel fold one sample per thread, then one 2 x 2 block per thread; the odd last column is replicated there.  The Cb / Cr bases are aligned only by luck: every
 // run goes through stitch_store.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned yuv_luma(const YuvEdge& y, unsigned p0, unsigned p1, unsigned p2)
+// The dithered forms (stitch_yuv_dither_kernel, to_output_yuv_dither_kernel; the definition: quant.yuvFromSamples16): the 16-bit samples stay the truncating quantiser's and
+// the two rounding constants become thresholds: 1 << (37 - D) -> T << (31 - D) and 1 << (39 - D) -> T << (33 - D).  Folded like the shifts: the luma numerator is scaled by
+// 2^(D - 6) to reach >> 32, so T << (31 - D) becomes T << 25; the chroma numerator by 2^(D - 8) ((40 - D) + (D - 8) = 32), so T << (33 - D) becomes T << 25 as well.  T = 64
+// ('round') is today's 2^31.  A chroma sample takes the threshold of its own coordinates in the chroma plane.
+template <bool DITHER>
+__device__ __forceinline__ unsigned yuv_round(bool ordered, int x, int y)
+{
+    if constexpr (DITHER) return quant_threshold(ordered, x, y) << 25;
+    else return 0x80000000u;
+}
+
+__device__ __forceinline__ unsigned yuv_luma(const YuvEdge& y, unsigned p0, unsigned p1, unsigned p2, unsigned rnd = 0x80000000u)
 {
     // < 2^30: the coefficients are positive and sum to 2^14.  24-bit multiplies (samples of 16 bits, coefficients of 14): v_mad_u32_u24 runs at the full rate, a
     // 32-bit v_mul_lo_u32 at a quarter of it -- with 32-bit products this edge was 216.9 us on the 8K canvas beside the sample edge's 203.1 (profiles/yuv/summary.md)
     const unsigned L = __umul24(y.ky[0], p0) + __umul24(y.ky[1], p1) + __umul24(y.ky[2], p2);
-    return y.base_y + (unsigned)(((unsigned long long)L * y.mul_y + 0x80000000ull) >> 32);             // one v_mad_u64_u32, its high word
+    return y.base_y + (unsigned)(((unsigned long long)L * y.mul_y + (unsigned long long)rnd) >> 32);             // one v_mad_u64_u32, its high word
 }
 
 // s0..s2: the planes' sums over the block, four samples each.  |M| <= 2^13 * 4 * 65535 < 2^31 whatever the order of the terms (the positive and the negative
 // coefficients of a chroma row each sum to 2^13 in magnitude).
-__device__ __forceinline__ unsigned yuv_chroma(const int (&k)[3], const YuvEdge& y, int s0, int s1, int s2)
+__device__ __forceinline__ unsigned yuv_chroma(const int (&k)[3], const YuvEdge& y, int s0, int s1, int s2, unsigned rnd = 0x80000000u)
 {
     const int M = __mul24(k[0], s0) + __mul24(k[1], s1) + __mul24(k[2], s2);                             // (|k| <= 2^13, sums < 2^18: signed 24-bit factors)
-    return (unsigned)(y.base_c + (int)(((long long)M * y.mul_c + 0x80000000ll) >> 32));                 // (>> 32 of the signed sum: the floor shift of the definition)
+    return (unsigned)(y.base_c + (int)(((long long)M * y.mul_c + (long long)rnd) >> 32));                 // (>> 32 of the signed sum: the floor shift of the definition)
 }
 
-__device__ __forceinline__ int yuv_sample16(float v, bool f16) { return stitch_out_quant<uint16_t>(v, f16, 65536.f); }
+__device__ __forceinline__ int yuv_sample16(float v, bool f16) { return quant_sample<uint16_t, false>(v, f16, 65536.f, 65536.f - 1.f, false, 0, 0); }
 
+// (The body is stitch_yuv_body.inc, included by both kernels: see there.)
 template <typename TD, int R>
 __global__ __launch_bounds__(256) void stitch_yuv_kernel(StitchArgs a, YuvEdge y)
 {
-    static_assert(R % 2 == 0, "a thread owns whole row pairs");
-    __shared__ int s_seam[256];
-    __shared__ int s_nseam;
-    if (threadIdx.x == 0) s_nseam = 0;
-    __syncthreads();
-    const int Y0 = blockIdx.y * R, X0 = (blockIdx.x * 256 + threadIdx.x) * 8;
-    const int cw = (a.out_w + 1) / 2, ch = (a.out_h + 1) / 2;
-    TD* const py = (TD*)a.out;
-    TD* const pu = py + (long long)a.out_h * a.out_w;
-    TD* const pv = pu + (long long)ch * cw;
-    const bool f16 = y.f16 != 0;
-    if (X0 < a.out_w) {
-        StitchCols k;
-        if (!stitch_classify(a, X0, k)) s_seam[atomicAdd(&s_nseam, 1)] = threadIdx.x;
-        else {
-            StitchRun<TD, 8> oy[R];
-            StitchRun<TD, 4> ou[R / 2], ov[R / 2];
-            int sum[3][4];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const StitchFold<3> f = stitch_fold_row<3>(a, k, X0, min(Y0 + r, a.out_h - 1), 0, 3);
-                int s[3][8];
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[c][e] = yuv_sample16(f.v[c][e], f16);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) oy[r].e[e] = (TD)yuv_luma(y, s[0][e], s[1][e], s[2][e]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) sum[c][e] = (r & 1 ? sum[c][e] : 0) + s[c][2 * e] + s[c][2 * e + 1];
-                if (r & 1) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        ou[r / 2].e[e] = (TD)yuv_chroma(y.ku, y, sum[0][e], sum[1][e], sum[2][e]);
-                        ov[r / 2].e[e] = (TD)yuv_chroma(y.kv, y, sum[0][e], sum[1][e], sum[2][e]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (Y0 + r >= a.out_h) break;
-                stitch_store(py + (long long)(Y0 + r) * a.out_w + X0, oy[r]);
-                if (!(r & 1)) {      // (the pair's second row may be the replicated one: the chroma row exists with the first)
-                    const long long at = (long long)((Y0 + r) / 2) * cw + X0 / 2;
-                    stitch_store(pu + at, ou[r / 2]);
-                    stitch_store(pv + at, ov[r / 2]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // The enlisted groups: 4 * (R / 2) blocks of 2 x 2 pixels each, 12 samples a block.  One thread folds ONE sample (as the other edges' seam pass does: a thread that
-    // walked its block's twelve folds one after the other held the whole workgroup for twelve chains of dependent loads -- 216 us on the 8K canvas for the sample
-    // edge's 203); the samples of 21 blocks meet in LDS and one thread per block converts and writes them.
-    constexpr int PER = 4 * (R / 2), NB = 21;      // blocks of one group: (row pair, block), the block innermost;  blocks per pass: 21 * 12 = 252 threads
-    __shared__ int s_smp[NB * 12];
-    const int nblk = s_nseam * PER, t = threadIdx.x;
-    auto origin = [&](int b, int& xa, int& ya) {
-        const int gidx = b / PER, rem = b - gidx * PER;
-        xa = (blockIdx.x * 256 + s_seam[gidx]) * 8 + (rem % 4) * 2; ya = Y0 + (rem / 4) * 2;
-        return b < nblk && xa < a.out_w && ya < a.out_h;
-    };
-    for (int b0 = 0; b0 < nblk; b0 += NB) {          // (block-uniform)
-        int xa, ya;
-        if (t < NB * 12 && origin(b0 + t / 12, xa, ya)) {
-            const int item = t % 12, c = item % 3, i = item / 6, j = (item / 3) & 1;          // sample (i, j, c) of the block: (row, column, plane), the plane innermost
-            const int X = j ? min(xa + 1, a.out_w - 1) : xa, Y = i ? min(ya + 1, a.out_h - 1) : ya;      // (the odd last column / row: the edge pixel again)
-            s_smp[t] = yuv_sample16(stitch_pixel(a, X, Y, c), f16);
-        }
-        __syncthreads();
-        if (t < NB && origin(b0 + t, xa, ya)) {
-            const int* q = s_smp + t * 12;
-            int sum[3] = {0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int* e = q + (i * 2 + j) * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) sum[c] += e[c];
-                    if ((i && ya + 1 >= a.out_h) || (j && xa + 1 >= a.out_w)) continue;
-                    py[(long long)(ya + i) * a.out_w + xa + j] = (TD)yuv_luma(y, e[0], e[1], e[2]);
-                }
-            const long long at = (long long)(ya / 2) * cw + xa / 2;
-            pu[at] = (TD)yuv_chroma(y.ku, y, sum[0], sum[1], sum[2]);
-            pv[at] = (TD)yuv_chroma(y.kv, y, sum[0], sum[1], sum[2]);
-        }
-        __syncthreads();
-    }
+    constexpr bool DITHER = false;
+    const bool ordered = false;
+#include "stitch_yuv_body.inc"
+}
+
+template <typename TD, int R>
+__global__ __launch_bounds__(256) void stitch_yuv_dither_kernel(StitchArgs a, YuvEdge y, int ordered_)
+{
+    constexpr bool DITHER = true;
+    const bool ordered = ordered_ != 0;
+#include "stitch_yuv_body.inc"
 }
 
 // The unfused form (moe_to_yuv): three dense planes of H x W -> the same frame, for chains whose last step is a resize, an ensemble or a blended DN.  One thread = one
 // row pair x 8 columns; the samples are to_output_kernel's with bits = 16 (no canvas rounding: the planes are the canvas).
+// (The body is to_output_yuv_body.inc, included by both kernels.)
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void to_output_yuv_kernel(const TS* __restrict__ src, TD* __restrict__ dst, int H, int W, YuvEdge y)
 {
-    const int X0 = (blockIdx.x * 256 + threadIdx.x) * 8, ya = blockIdx.y * 2;
-    if (X0 >= W) return;
-    const int cw = (W + 1) / 2, ch = (H + 1) / 2;
-    const long long HW = (long long)H * W;
-    TD* const pu = dst + HW;
-    TD* const pv = pu + (long long)ch * cw;
-    const bool whole = X0 + 8 <= W;
-    StitchRun<TD, 8> oy[2];
-    int sum[3][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int Y = min(ya + i, H - 1);
-        int s[3][8];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const TS* p = src + c * HW + (long long)Y * W;
-            TS v[8];
-            if (whole) stitch_mix_load8(p + X0, 1, ((uintptr_t)(p + X0) & 15) == 0, v);
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = p[min(X0 + e, W - 1)];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[c][e] = yuv_sample16((float)v[e], false);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum[c][e] = (i ? sum[c][e] : 0) + s[c][2 * e] + s[c][2 * e + 1];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) oy[i].e[e] = (TD)yuv_luma(y, s[0][e], s[1][e], s[2][e]);
-    }
-    StitchRun<TD, 4> ou, ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        ou.e[e] = (TD)yuv_chroma(y.ku, y, sum[0][e], sum[1][e], sum[2][e]);
-        ov.e[e] = (TD)yuv_chroma(y.kv, y, sum[0][e], sum[1][e], sum[2][e]);
-    }
-    const long long at = (long long)blockIdx.y * cw + X0 / 2;
-    if (whole) {
-        stitch_store(dst + (long long)ya * W + X0, oy[0]);
-        if (ya + 1 < H) stitch_store(dst + (long long)(ya + 1) * W + X0, oy[1]);
-        stitch_store(pu + at, ou);
-        stitch_store(pv + at, ov);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {      // (constant indices: a run indexed by a loop variable is moved to LDS)
-            if (X0 + e >= W) break;
-            dst[(long long)ya * W + X0 + e] = oy[0].e[e];
-            if (ya + 1 < H) dst[(long long)(ya + 1) * W + X0 + e] = oy[1].e[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (X0 + 2 * e >= W) break;
-            pu[at + e] = ou.e[e]; pv[at + e] = ov.e[e];
-        }
-    }
+    constexpr bool DITHER = false;
+    const bool ordered = false;
+#include "to_output_yuv_body.inc"
+}
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void to_output_yuv_dither_kernel(const TS* __restrict__ src, TD* __restrict__ dst, int H, int W, YuvEdge y, int ordered_)
+{
+    constexpr bool DITHER = true;
+    const bool ordered = ordered_ != 0;
+#include "to_output_yuv_body.inc"
 }
 
 }  // namespace
@@ -657,10 +575,18 @@ void launch_stitch(const StitchArgs& a, hipStream_t s)
 }
 
 template <typename TD>
-static bool launch_stitch_out_t(const StitchArgs& a, float quant, int f16, hipStream_t s)
+static bool launch_stitch_out_t(const StitchArgs& a, float quant, int f16, hipStream_t s, const QuantDither* dq)
 {
     constexpr int R = 4;          // rows per thread (the canvas edge's)
     const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.rows + R - 1) / R);
+    if (dq) {          // the rounding / ordered-dither quantiser: the same grid, the twin kernels
+        if (a.C == 1) hipLaunchKernelGGL((stitch_out_dither_kernel<TD, 1, R>), g, dim3(256), 0, s, a, *dq, f16);
+        else if (a.C == 2) hipLaunchKernelGGL((stitch_out_dither_kernel<TD, 2, R>), g, dim3(256), 0, s, a, *dq, f16);
+        else if (a.C == 3) hipLaunchKernelGGL((stitch_out_dither_kernel<TD, 3, R>), g, dim3(256), 0, s, a, *dq, f16);
+        else if (a.C == 4) hipLaunchKernelGGL((stitch_out_dither_kernel<TD, 4, R>), g, dim3(256), 0, s, a, *dq, f16);
+        else return false;
+        return true;
+    }
     if (a.C == 1) hipLaunchKernelGGL((stitch_out_kernel<TD, 1, R>), g, dim3(256), 0, s, a, quant, f16);
     else if (a.C == 2) hipLaunchKernelGGL((stitch_out_kernel<TD, 2, R>), g, dim3(256), 0, s, a, quant, f16);
     else if (a.C == 3) hipLaunchKernelGGL((stitch_out_kernel<TD, 3, R>), g, dim3(256), 0, s, a, quant, f16);
@@ -670,34 +596,48 @@ static bool launch_stitch_out_t(const StitchArgs& a, float quant, int f16, hipSt
 }
 
 // a.out: (out_h, out_w, C) interleaved, a.out_dtype MOE_U8 / MOE_U16; the whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
-bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s)
+bool launch_stitch_out(const StitchArgs& a, int canvas_dtype, float quant, hipStream_t s, const QuantDither* dq)
 {
     const int f16 = canvas_dtype == MOE_F16;
-    return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s) : launch_stitch_out_t<uint16_t>(a, quant, f16, s);
+    return a.out_dtype == MOE_U8 ? launch_stitch_out_t<uint8_t>(a, quant, f16, s, dq) : launch_stitch_out_t<uint16_t>(a, quant, f16, s, dq);
 }
 
 template <typename TD>
-static void launch_stitch_planes_t(const StitchArgs& a, float quant, int f16, hipStream_t s)
+static void launch_stitch_planes_t(const StitchArgs& a, float quant, int f16, hipStream_t s, const QuantDither* dq)
 {
     // rows per thread: the sample edge's four, or one where four leave fewer than launch_stitch_mix_t's 1024 workgroups (a.C planes of them: blockIdx.z) -- the
     // chroma planes of a small frame
     const unsigned gx = ((a.out_w + 7) / 8 + 255) / 256;
-    if ((long long)gx * ((a.out_h + 3) / 4) * a.C >= 1024) hipLaunchKernelGGL((stitch_planes_kernel<TD, 4>), dim3(gx, (a.out_h + 3) / 4, a.C), dim3(256), 0, s, a, quant, f16);
+    const bool four = (long long)gx * ((a.out_h + 3) / 4) * a.C >= 1024;
+    if (dq) {
+        if (four) hipLaunchKernelGGL((stitch_planes_dither_kernel<TD, 4>), dim3(gx, (a.out_h + 3) / 4, a.C), dim3(256), 0, s, a, *dq, f16);
+        else hipLaunchKernelGGL((stitch_planes_dither_kernel<TD, 1>), dim3(gx, a.out_h, a.C), dim3(256), 0, s, a, *dq, f16);
+    } else if (four) hipLaunchKernelGGL((stitch_planes_kernel<TD, 4>), dim3(gx, (a.out_h + 3) / 4, a.C), dim3(256), 0, s, a, quant, f16);
     else hipLaunchKernelGGL((stitch_planes_kernel<TD, 1>), dim3(gx, a.out_h, a.C), dim3(256), 0, s, a, quant, f16);
 }
 
 // a.out: a.C planes of out_h x out_w samples at `depth` bits, uint8 for depth 8, else uint16; the whole canvas (y0 = 0, rows = out_h, row_lo = 0)
-void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s)
+void launch_stitch_planes(const StitchArgs& a, int canvas_dtype, int depth, hipStream_t s, const QuantDither* dq)
 {
     const int f16 = canvas_dtype == MOE_F16;
-    if (depth == 8) launch_stitch_planes_t<uint8_t>(a, 256.f, f16, s);
-    else launch_stitch_planes_t<uint16_t>(a, (float)(1 << depth), f16, s);
+    if (depth == 8) launch_stitch_planes_t<uint8_t>(a, 256.f, f16, s, dq);
+    else launch_stitch_planes_t<uint16_t>(a, (float)(1 << depth), f16, s, dq);
 }
 
 template <typename T, typename TD, int R>
-static bool launch_stitch_mix_r(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
+static bool launch_stitch_mix_r(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s, const QuantDither* dq)
 {
     const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.rows + R - 1) / R);
+    if constexpr (!std::is_same<T, TD>::value) {
+        if (dq) {
+            if (planes == 1) hipLaunchKernelGGL((stitch_mix_dither_kernel<T, TD, 1, R>), g, dim3(256), 0, s, a, m, *dq);
+            else if (planes == 2) hipLaunchKernelGGL((stitch_mix_dither_kernel<T, TD, 2, R>), g, dim3(256), 0, s, a, m, *dq);
+            else if (planes == 3) hipLaunchKernelGGL((stitch_mix_dither_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m, *dq);
+            else if (planes == 4) hipLaunchKernelGGL((stitch_mix_dither_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m, *dq);
+            else return false;
+            return true;
+        }
+    }
     if (planes == 1) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 1, R>), g, dim3(256), 0, s, a, m);
     else if (planes == 2) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 2, R>), g, dim3(256), 0, s, a, m);
     else if (planes == 3) hipLaunchKernelGGL((stitch_mix_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m);
@@ -709,15 +649,15 @@ static bool launch_stitch_mix_r(const StitchArgs& a, const StitchMix& m, int pla
 // Rows per thread: four where that still gives the device a few waves per SIMD (a 4K canvas and larger); one row on smaller canvases -- a DN
 // step's 1080p frame is 270 workgroups of four rows on 256 CUs, one wave per SIMD waiting out its own loads (times of both: profiles/filter/summary.md).
 template <typename T, typename TD>
-static bool launch_stitch_mix_t(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s)
+static bool launch_stitch_mix_t(const StitchArgs& a, const StitchMix& m, int planes, hipStream_t s, const QuantDither* dq = nullptr)
 {
     const long long blocks4 = (long long)(((a.out_w + 7) / 8 + 255) / 256) * ((a.out_h + 3) / 4);
-    return blocks4 >= 1024 ? launch_stitch_mix_r<T, TD, 4>(a, m, planes, s) : launch_stitch_mix_r<T, TD, 1>(a, m, planes, s);
+    return blocks4 >= 1024 ? launch_stitch_mix_r<T, TD, 4>(a, m, planes, s, dq) : launch_stitch_mix_r<T, TD, 1>(a, m, planes, s, dq);
 }
 
 // a.C: the net's planes; with m.alpha one more plane is written.  m.quant == 0: a.out = the canvas (planes, out_h, out_w) of canvas_dtype; else a.out = interleaved
 // (out_h, out_w, planes) of a.out_dtype MOE_U8 / MOE_U16.  The whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
-bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s)
+bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipStream_t s, const QuantDither* dq)
 {
     const int planes = a.C + (m.alpha ? 1 : 0);
     const bool f16 = canvas_dtype == MOE_F16;
@@ -729,14 +669,22 @@ bool launch_stitch_mix(const StitchArgs& a, StitchMix m, int canvas_dtype, hipSt
     m.once_from = (long long)a.C * a.out_h * a.out_w / 2048 * 2048;
     m.q_once = f16 && !(m.sW == 1 && (uintptr_t)m.inp % 16 == 0);
     if (m.quant == 0.f) return f16 ? launch_stitch_mix_t<half_t, half_t>(a, m, planes, s) : launch_stitch_mix_t<float, float>(a, m, planes, s);
-    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s);
-    return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s);
+    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_mix_t<half_t, uint8_t>(a, m, planes, s, dq) : launch_stitch_mix_t<float, uint8_t>(a, m, planes, s, dq);
+    return f16 ? launch_stitch_mix_t<half_t, uint16_t>(a, m, planes, s, dq) : launch_stitch_mix_t<float, uint16_t>(a, m, planes, s, dq);
 }
 
 template <typename T, typename TD, int R>
-static bool launch_stitch_luma_r(const StitchArgs& a, const StitchLuma& m, hipStream_t s)
+static bool launch_stitch_luma_r(const StitchArgs& a, const StitchLuma& m, hipStream_t s, const QuantDither* dq)
 {
     const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.rows + R - 1) / R);
+    if constexpr (!std::is_same<T, TD>::value) {
+        if (dq) {
+            if (a.C == 1) hipLaunchKernelGGL((stitch_luma_dither_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m, *dq);
+            else if (a.C == 2) hipLaunchKernelGGL((stitch_luma_dither_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m, *dq);
+            else return false;
+            return true;
+        }
+    }
     if (a.C == 1) hipLaunchKernelGGL((stitch_luma_kernel<T, TD, 3, R>), g, dim3(256), 0, s, a, m);
     else if (a.C == 2) hipLaunchKernelGGL((stitch_luma_kernel<T, TD, 4, R>), g, dim3(256), 0, s, a, m);
     else return false;
@@ -744,35 +692,48 @@ static bool launch_stitch_luma_r(const StitchArgs& a, const StitchLuma& m, hipSt
 }
 
 template <typename T, typename TD>
-static bool launch_stitch_luma_t(const StitchArgs& a, const StitchLuma& m, hipStream_t s)      // (rows per thread: launch_stitch_mix_t's rule)
+static bool launch_stitch_luma_t(const StitchArgs& a, const StitchLuma& m, hipStream_t s, const QuantDither* dq = nullptr)      // (rows per thread: launch_stitch_mix_t's rule)
 {
     const long long blocks4 = (long long)(((a.out_w + 7) / 8 + 255) / 256) * ((a.out_h + 3) / 4);
-    return blocks4 >= 1024 ? launch_stitch_luma_r<T, TD, 4>(a, m, s) : launch_stitch_luma_r<T, TD, 1>(a, m, s);
+    return blocks4 >= 1024 ? launch_stitch_luma_r<T, TD, 4>(a, m, s, dq) : launch_stitch_luma_r<T, TD, 1>(a, m, s, dq);
 }
 
 // a.C: the pool's planes, 1 (Y') or 2 (Y', alpha); a.C + 2 planes are written.  m.quant == 0: a.out = the canvas (a.C + 2, out_h, out_w) of canvas_dtype; else a.out =
 // interleaved (out_h, out_w, a.C + 2) of a.out_dtype MOE_U8 / MOE_U16.  The whole canvas (y0 = 0, rows = out_h, row_lo = 0).  false: a plane count without a kernel
-bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s)
+bool launch_stitch_luma(const StitchArgs& a, const StitchLuma& m, int canvas_dtype, hipStream_t s, const QuantDither* dq)
 {
     const bool f16 = canvas_dtype == MOE_F16;
     if (m.quant == 0.f) return f16 ? launch_stitch_luma_t<half_t, half_t>(a, m, s) : launch_stitch_luma_t<float, float>(a, m, s);
-    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_luma_t<half_t, uint8_t>(a, m, s) : launch_stitch_luma_t<float, uint8_t>(a, m, s);
-    return f16 ? launch_stitch_luma_t<half_t, uint16_t>(a, m, s) : launch_stitch_luma_t<float, uint16_t>(a, m, s);
+    if (a.out_dtype == MOE_U8) return f16 ? launch_stitch_luma_t<half_t, uint8_t>(a, m, s, dq) : launch_stitch_luma_t<float, uint8_t>(a, m, s, dq);
+    return f16 ? launch_stitch_luma_t<half_t, uint16_t>(a, m, s, dq) : launch_stitch_luma_t<float, uint16_t>(a, m, s, dq);
 }
 
 // a.out: the Y'CbCr 4:2:0 frame of a.out_h x a.out_w (uint8 for depth 8, else uint16); three planes, the whole canvas (y0 = 0, rows = out_h, row_lo = 0)
-void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s)
+void launch_stitch_yuv(const StitchArgs& a, const YuvEdge& y, hipStream_t s, int dither)
 {
     constexpr int R = 4;          // rows per thread (the sample edge's): two chroma rows
     const dim3 g(((a.out_w + 7) / 8 + 255) / 256, (a.out_h + R - 1) / R);
-    if (y.depth == 8) hipLaunchKernelGGL((stitch_yuv_kernel<uint8_t, R>), g, dim3(256), 0, s, a, y);
+    if (dither) {
+        const int ordered = dither == 2;
+        if (y.depth == 8) hipLaunchKernelGGL((stitch_yuv_dither_kernel<uint8_t, R>), g, dim3(256), 0, s, a, y, ordered);
+        else hipLaunchKernelGGL((stitch_yuv_dither_kernel<uint16_t, R>), g, dim3(256), 0, s, a, y, ordered);
+    } else if (y.depth == 8) hipLaunchKernelGGL((stitch_yuv_kernel<uint8_t, R>), g, dim3(256), 0, s, a, y);
     else hipLaunchKernelGGL((stitch_yuv_kernel<uint16_t, R>), g, dim3(256), 0, s, a, y);
 }
 
-void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s)
+void launch_to_output_yuv(const void* src, int src_dtype, int H, int W, const YuvEdge& y, void* dst, hipStream_t s, int dither)
 {
     const dim3 g(((W + 7) / 8 + 255) / 256, (H + 1) / 2);
-    if (src_dtype == MOE_F16) {
+    if (dither) {
+        const int ordered = dither == 2;
+        if (src_dtype == MOE_F16) {
+            if (y.depth == 8) hipLaunchKernelGGL((to_output_yuv_dither_kernel<half_t, uint8_t>), g, dim3(256), 0, s, (const half_t*)src, (uint8_t*)dst, H, W, y, ordered);
+            else hipLaunchKernelGGL((to_output_yuv_dither_kernel<half_t, uint16_t>), g, dim3(256), 0, s, (const half_t*)src, (uint16_t*)dst, H, W, y, ordered);
+        } else {
+            if (y.depth == 8) hipLaunchKernelGGL((to_output_yuv_dither_kernel<float, uint8_t>), g, dim3(256), 0, s, (const float*)src, (uint8_t*)dst, H, W, y, ordered);
+            else hipLaunchKernelGGL((to_output_yuv_dither_kernel<float, uint16_t>), g, dim3(256), 0, s, (const float*)src, (uint16_t*)dst, H, W, y, ordered);
+        }
+    } else if (src_dtype == MOE_F16) {
         if (y.depth == 8) hipLaunchKernelGGL((to_output_yuv_kernel<half_t, uint8_t>), g, dim3(256), 0, s, (const half_t*)src, (uint8_t*)dst, H, W, y);
         else hipLaunchKernelGGL((to_output_yuv_kernel<half_t, uint16_t>), g, dim3(256), 0, s, (const half_t*)src, (uint16_t*)dst, H, W, y);
     } else {

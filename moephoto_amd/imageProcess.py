@@ -33,7 +33,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib, pixfmt
+from . import _lib, pixfmt, quant
 from .config import config
 from .models import EngineModule
 from .weights import load_state_dict_file
@@ -290,7 +290,15 @@ def _planesOut(who, depth, C, h, w, out, device):
     return out
 
 
-def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None, reuse=None, luma=None):
+def ditherFlags(who, dither, bits, kind):
+    """The MOE_Q_* flags of a `dither` keyword (None | 'none' | 'round' | 'ordered') for an edge of `kind` ('rgb', 'planes', 'yuv': quant.flags) -- RGB samples at 8 bits
+    take the unit scale (their reader is / 255), at 16 bits and planar samples do not.  ValueError naming the keyword for an unknown value."""
+    if dither is not None and dither not in quant.MODES:
+        raise ValueError("{}: 'dither' \"{}\" is not supported ({})".format(who, dither, ', '.join(quant.MODES)))
+    return quant.flags(dither, bits, kind)
+
+
+def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=None, reuse=None, luma=None, dither=None):
     """doCrop, doCropOut and the DN step's fused forms: the checks, the plan, the pad, the call (moe_run_plan, with bitDepth moe_run_plan_out, with mix = (strength,
     alpha plane or None) moe_run_plan_filter: the blend with x and the alpha plane inside the final fold, with yuv = (pixFmt, matrix, order) moe_run_plan_yuv: the
     encoder's planar frame from the final fold, with planes = depth moe_run_plan_planes: the image's own planes as samples of that depth) and its one retry after
@@ -298,7 +306,12 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
     the final fold merges Y' with the fp32 chroma planes C' (2, outH, outW) into the colour planes -- the canvas (x's planes + 2, outH, outW), or with bitDepth its samples.
     reuse (the frame stream's): a callable (plan, planes) -> (mask, pool) -- the plan's tiles that have to run for this image as n_tiles uint8 on
     the host, and the fp32 device tensor of plan.pool_elems(planes) that holds every other tile's result from the previous frame.  The call is then moe_run_plan_subset
-    into that pool followed by the same edge's stitch-only entry point on it (moe_stitch, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv, moe_stitch_planes)."""
+    into that pool followed by the same edge's stitch-only entry point on it (moe_stitch, moe_stitch_out, moe_stitch_mix, moe_stitch_yuv, moe_stitch_planes).
+    dither ('round' | 'ordered'; moephoto_amd/quant.py): the edge's quantiser rounds or dithers -- its MOE_Q_* flags ride in the bits / depth argument of whichever call is
+    made, the reuse path's stitch included; a canvas form quantises nothing and refuses the keyword."""
+    qf = ditherFlags(who, dither, bitDepth, 'yuv' if yuv is not None else 'planes' if planes is not None else 'rgb')
+    if qf and bitDepth is None and yuv is None and planes is None:
+        raise ValueError("{}: 'dither' applies to a quantising edge; the canvas form quantises nothing".format(who))
     model = opt.modelCached
     if not isinstance(model, EngineModule):
         raise TypeError('{} needs an engine-backed model (moephoto_amd.models.*), got {}'.format(who, type(model).__name__))
@@ -356,40 +369,40 @@ def _runPlan(who, opt, x, bitDepth=None, out=None, mix=None, yuv=None, planes=No
 
     def fold():        # the edge alone, on the stream's pool in the plan's own layout
         if luma is not None:
-            _lib.check(L.moe_stitch_luma(plan._h, dev, pool.data_ptr(), None, P, dt, chroma.data_ptr(), matrix, order, int(bitDepth or 0), out.data_ptr(),
+            _lib.check(L.moe_stitch_luma(plan._h, dev, pool.data_ptr(), None, P, dt, chroma.data_ptr(), matrix, order, int(bitDepth or 0) | qf, out.data_ptr(),
                                          _DT[out.dtype] if bitDepth is None else lib_dt, stream))
         elif yuv is not None:
-            _lib.check(L.moe_stitch_yuv(plan._h, dev, pool.data_ptr(), None, dt, depth, matrix, order, out.data_ptr(), stream))
+            _lib.check(L.moe_stitch_yuv(plan._h, dev, pool.data_ptr(), None, dt, depth | qf, matrix, order, out.data_ptr(), stream))
         elif planes is not None:
-            _lib.check(L.moe_stitch_planes(plan._h, dev, pool.data_ptr(), None, P, dt, int(planes), out.data_ptr(), stream))
+            _lib.check(L.moe_stitch_planes(plan._h, dev, pool.data_ptr(), None, P, dt, int(planes) | qf, out.data_ptr(), stream))
         elif mix is not None:
             _lib.check(L.moe_stitch_mix(plan._h, dev, pool.data_ptr(), None, P, xp.data_ptr(), dt, sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
-                                        strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, stream))
+                                        strength, int(bitDepth or 0) | qf, out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, stream))
         elif bitDepth is None:
             _lib.check(L.moe_stitch(plan._h, dev, pool.data_ptr(), None, P, out.data_ptr(), _DT[out.dtype], stream))
         else:
-            _lib.check(L.moe_stitch_out(plan._h, dev, pool.data_ptr(), None, P, dt, int(bitDepth), out.data_ptr(), lib_dt, stream))
+            _lib.check(L.moe_stitch_out(plan._h, dev, pool.data_ptr(), None, P, dt, int(bitDepth) | qf, out.data_ptr(), lib_dt, stream))
 
     def run():
         if reuse is not None:
             _lib.check(L.moe_run_plan_subset(model._h, plan._h, xp.data_ptr(), dt, sC, sH, sW, mask.ctypes.data, pool.data_ptr(), int(config.tilesPerBatch), stream))
             fold()
         elif luma is not None:       # the canvas doCrop would have returned for Y has xp's dtype: its rounding comes first, then the merge in that dtype
-            _lib.check(L.moe_run_plan_luma(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, chroma.data_ptr(), matrix, order, int(bitDepth or 0),
+            _lib.check(L.moe_run_plan_luma(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, chroma.data_ptr(), matrix, order, int(bitDepth or 0) | qf,
                                            out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
         elif yuv is not None:        # (as doCropOut: the rounding of the canvas doCrop would have returned comes first)
-            _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth, matrix, order,
+            _lib.check(L.moe_run_plan_yuv(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], depth | qf, matrix, order,
                                           out.data_ptr(), int(config.tilesPerBatch), stream))
         elif planes is not None:
-            _lib.check(L.moe_run_plan_planes(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(planes),
+            _lib.check(L.moe_run_plan_planes(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(planes) | qf,
                                              out.data_ptr(), int(config.tilesPerBatch), stream))
         elif mix is not None:     # the canvas RGBFilter would have returned has xp's dtype; bits = 0 asks for that canvas, else for its samples
             _lib.check(L.moe_run_plan_filter(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, alpha.data_ptr() if alpha is not None else None, aH, aW,
-                                             strength, int(bitDepth or 0), out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
+                                             strength, int(bitDepth or 0) | qf, out.data_ptr(), _DT[out.dtype] if bitDepth is None else lib_dt, int(config.tilesPerBatch), stream))
         elif bitDepth is None:
             _lib.check(L.moe_run_plan(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, out.data_ptr(), _DT[out.dtype], int(config.tilesPerBatch), stream))
         else:          # the canvas doCrop would have returned has xp's dtype: its rounding is applied before the quantiser
-            _lib.check(L.moe_run_plan_out(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(bitDepth),
+            _lib.check(L.moe_run_plan_out(model._h, plan._h, xp.data_ptr(), _DT[xp.dtype], sC, sH, sW, _DT[xp.dtype], int(bitDepth) | qf,
                                           out.data_ptr(), lib_dt, int(config.tilesPerBatch), stream))
     try:
         run()
@@ -412,26 +425,27 @@ def doCrop(opt, x, *args, reuse=None, **_):
     return _runPlan('doCrop', opt, x, reuse=reuse)
 
 
-def doCropOut(opt, x, bitDepth, out=None, reuse=None):
+def doCropOut(opt, x, bitDepth, out=None, reuse=None, dither=None):
     """toOutput(bitDepth)(toFloat(doCrop(opt, x))) without the download, as ONE call (moe_run_plan_out): doCrop up to the final fold, which rounds each pixel as the
     canvas of x's dtype would have and writes the quantised (H, W, C) image (uint8, or uint16 samples in int16 storage) -- the canvas and its fp32 copy never exist
-    (python/imageProcess.py:157-172,238-257).  out: a contiguous device tensor of that shape and dtype to write into (the frame stream's slot buffers), else a new one."""
-    return _runPlan('doCropOut', opt, x, bitDepth, out, reuse=reuse)
+    (python/imageProcess.py:157-172,238-257).  out: a contiguous device tensor of that shape and dtype to write into (the frame stream's slot buffers), else a new one.
+    dither: None | 'round' | 'ordered' -- the fold's quantiser rounds to nearest or adds the 8 x 8 ordered dither (moephoto_amd/quant.py; 8 bits at unit scale)."""
+    return _runPlan('doCropOut', opt, x, bitDepth, out, reuse=reuse, dither=dither)
 
 
-def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr', reuse=None):
+def doCropYuv(opt, x, fmt, out=None, matrix='bt709', order='bgr', reuse=None, dither=None):
     """doCropOut(opt, x, 16) followed by pixfmt.fromSamples16, as ONE call (moe_run_plan_yuv): the final fold writes the encoder's planar Y'CbCr 4:2:0 frame -- fmt one of
     pixfmt.FORMATS (yuv420p, yuv420p10le, yuv420p12le, yuv420p16le), limited range, matrix bt709 / bt601 / bt2020nc; order says whether plane 0 of x is blue ('bgr', the
     video path's frames) or red.  Half the bytes of the interleaved image.  Returns a flat uint8 device tensor of pixfmt.frameBytes(fmt, outW, outH); out: one to write into."""
-    pixfmt.check(fmt, matrix, order)
-    return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order), reuse=reuse)
+    pixfmt.check(fmt, matrix, order)          # (dither: quant.yuvFromSamples16 -- 'ordered' dithers the integer conversion's rounding, 'round' is the plain frame)
+    return _runPlan('doCropYuv', opt, x, out=out, yuv=(fmt, matrix, order), reuse=reuse, dither=dither)
 
 
-def doCropPlanes(opt, x, depth, out=None, reuse=None):
+def doCropPlanes(opt, x, depth, out=None, reuse=None, dither=None):
     """doCrop(opt, x) quantised plane by plane at `depth` bits (8, 10, 12, 16), as ONE call (moe_run_plan_planes): the final fold rounds each pixel as the canvas of x's
     dtype would have and writes C = 1 .. 4 planes of outH x outW samples (uint8 for depth 8, else little-endian uint16) -- the Y plane or the two chroma planes of a
     planar 4:2:0 frame (pixfmt.fromPlanes).  Returns a flat uint8 device tensor of those bytes; out: one to write into, e.g. a view into a frame at a plane's offset."""
-    return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth), reuse=reuse)
+    return _runPlan('doCropPlanes', opt, x, out=out, planes=int(depth), reuse=reuse, dither=dither)          # (dither: each sample at its coordinates in its own plane)
 
 
 # ---- luma-only steps (no counterpart: the reference sends every plane through the net; the definition: moephoto_amd/luma.py) -------------------
@@ -495,7 +509,10 @@ def lumaMerge(matrix='bt709', order='rgb'):
     (3 | 4, H, W) of Y's dtype, or with bitDepth 8 | 16 the quantised (H, W, 3 | 4) image as doCropOut gives it; out: a tensor of that shape and dtype to write into."""
     mat, ordr = _lumaIds('lumaMerge', matrix, order)
 
-    def f(Y, Cc, bitDepth=None, out=None):
+    def f(Y, Cc, bitDepth=None, out=None, dither=None):          # (dither: the sample form only -- quant.py)
+        qf = ditherFlags('lumaMerge', dither, bitDepth, 'rgb')
+        if qf and bitDepth is None:
+            raise ValueError("lumaMerge: 'dither' applies to the sample form (bitDepth 8 | 16); the canvas form quantises nothing")
         if Y.device.type != 'cuda' or Cc.device != Y.device:
             raise _lib.EngineError('lumaMerge: both inputs must live on one HIP device (moephoto_amd has no CPU path)')
         if Y.dim() != 3 or Y.shape[0] not in (1, 2):
@@ -516,7 +533,7 @@ def lumaMerge(matrix='bt709', order='rgb'):
         elif tuple(out.shape) != shape or out.dtype != o_dt or not out.is_contiguous() or out.device != Y.device:
             raise ValueError('lumaMerge: out must be a contiguous {} tensor of shape {} on {}'.format(o_dt, shape, Y.device))
         cur = torch.cuda.current_stream(Y.device)
-        _lib.check(_lib.lib().moe_luma_merge(Y.data_ptr(), _DT[Y.dtype], Cc.data_ptr(), P + 2, H, W, mat, ordr, int(bitDepth or 0), out.data_ptr(), lib_dt,
+        _lib.check(_lib.lib().moe_luma_merge(Y.data_ptr(), _DT[Y.dtype], Cc.data_ptr(), P + 2, H, W, mat, ordr, int(bitDepth or 0) | qf, out.data_ptr(), lib_dt,
                                              Y.device.index or 0, cur.cuda_stream))
         Y.record_stream(cur)
         Cc.record_stream(cur)
@@ -532,7 +549,7 @@ def lumaChroma(Cc, height, width, method):
     return resizeByTorch(Cc, width, height, method)
 
 
-def doCropLuma(opt, x, method, matrix='bt709', order='rgb', bitDepth=None, out=None, reuse=None):
+def doCropLuma(opt, x, method, matrix='bt709', order='rgb', bitDepth=None, out=None, reuse=None, dither=None):
     """A luma-only step with the merge inside the last fold (moe_run_plan_luma; with reuse moe_run_plan_subset + moe_stitch_luma): lumaSplit(x), the chroma planes
     resized to the step's output size, doCrop on Y with the final fold writing the colour planes -- the Y' canvas never exists.  The bytes of
     lumaMerge(doCrop(opt, Y), lumaChroma(C, ..)).  With bitDepth the fold writes the encoder's samples into `out`, as doCropOut does.  An image of fewer than three
@@ -541,10 +558,10 @@ def doCropLuma(opt, x, method, matrix='bt709', order='rgb', bitDepth=None, out=N
         raise ValueError('doCropLuma: chroma "{}" is not supported ({})'.format(method, ', '.join(_lib.RESIZE_MODES)))
     _lumaIds('doCropLuma', matrix, order)
     if x.dim() == 3 and x.shape[0] < 3:
-        return _runPlan('doCropLuma', opt, x, bitDepth, out, reuse=reuse)
+        return _runPlan('doCropLuma', opt, x, bitDepth, out, reuse=reuse, dither=dither)
     Y, Cc = lumaSplit(matrix, order)(x)
     plan = _plan_for(opt, Y.shape)
-    return _runPlan('doCropLuma', opt, Y, bitDepth, out, reuse=reuse, luma=(lumaChroma(Cc, plan.outH, plan.outW, method), matrix, order))
+    return _runPlan('doCropLuma', opt, Y, bitDepth, out, reuse=reuse, luma=(lumaChroma(Cc, plan.outH, plan.outW, method), matrix, order), dither=dither)
 
 
 # ---- resize step (python/imageProcess.py:174-214, 555-556) --------------------------------------------------
@@ -755,7 +772,7 @@ def _RGBFilter(opt, img, reuse=None):
     return mergeAlpha(alpha)(strengthOp(doCrop(opt, rgb, reuse=reuse), rgb, opt.strength))
 
 
-def filterOut(opt, img, bitDepth, out=None, reuse=None):
+def filterOut(opt, img, bitDepth, out=None, reuse=None, dither=None):
     """toOutput(bitDepth)(toFloat(_RGBFilter(opt, img))) without the download, as ONE call (moe_run_plan_filter), as doCropOut is to doCrop: the final fold blends each
     pixel with the input, rounds as the canvas of img's dtype would have and writes the quantised (H, W, C) image, alpha included; neither the canvas nor its fp32
     copy exists.  strength must be finite.  out: as doCropOut's."""
@@ -763,7 +780,7 @@ def filterOut(opt, img, bitDepth, out=None, reuse=None):
         raise ValueError('filterOut: strength must be finite, got {!r}'.format(opt.strength))
     alpha = {}
     rgb = opt.prepare(extractAlpha(alpha)(img))
-    return _runPlan('filterOut', opt, rgb, bitDepth, out, mix=(opt.strength, alpha.get('im')), reuse=reuse)
+    return _runPlan('filterOut', opt, rgb, bitDepth, out, mix=(opt.strength, alpha.get('im')), reuse=reuse, dither=dither)          # (dither: the fold's quantiser, quant.py)
 
 
 RGBFilter = lambda opt: lambda img: _RGBFilter(opt, img)
@@ -803,8 +820,11 @@ def toFloat(image):
     return image.to(dtype=torch.float)
 
 
-def toOutput(bitDepth):
-    """python/imageProcess.py:245-257: x * 2^bits, clamp [0, 2^bits - 1], truncate, to host numpy (H,W,C)."""
+def toOutput(bitDepth, dither=None):
+    """python/imageProcess.py:245-257: x * 2^bits, clamp [0, 2^bits - 1], truncate, to host numpy (H,W,C).  dither: None | 'round' | 'ordered' -- the rounding or
+    ordered-dither quantiser instead (moephoto_amd/quant.py; 8 bits at unit scale, the inverse of toTorch's / 255)."""
+    qf = ditherFlags('toOutput', dither, 8 if bitDepth <= 8 else bitDepth, 'rgb')
+
     def f(image):
         if image.dim() == 2:
             image = image.unsqueeze(2)
@@ -818,7 +838,7 @@ def toOutput(bitDepth):
         out_dt, np_dt, lib_dt = (torch.uint8, np.uint8, _lib.U8) if bitDepth <= 8 else (torch.int16, np.uint16, _lib.U16)
         dst = torch.empty((H, W, C), dtype=out_dt, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib().moe_to_output(planar.data_ptr(), _DT[planar.dtype], H, W, C, int(bitDepth), dst.data_ptr(), lib_dt, dev.index or 0, stream))
+        _lib.check(_lib.lib().moe_to_output(planar.data_ptr(), _DT[planar.dtype], H, W, C, int(bitDepth) | qf, dst.data_ptr(), lib_dt, dev.index or 0, stream))
         planar.record_stream(torch.cuda.current_stream(dev))
         res = dst.cpu().numpy()
         return res.view(np_dt) if bitDepth > 8 else res
@@ -828,10 +848,11 @@ def toOutput(bitDepth):
 toOutput8 = toOutput(8)
 
 
-def toYuv(fmt, matrix='bt709', order='bgr'):
+def toYuv(fmt, matrix='bt709', order='bgr', dither=None):
     """The unfused form of doCropYuv (moe_to_yuv): a (3, H, W) fp16 / fp32 device image -> the flat uint8 device tensor of its Y'CbCr 4:2:0 frame, from the samples
     toOutput(16)(toFloat(y)) would give.  f(y, out=None); out as doCropYuv's."""
     depth, mat, ordr = pixfmt.check(fmt, matrix, order)
+    depth |= ditherFlags('toYuv', dither, depth, 'yuv')          # (quant.yuvFromSamples16)
 
     def f(y, out=None):
         if y.device.type != 'cuda':
@@ -879,11 +900,12 @@ def fromPlanes(fmt, w, h, dtype=None):
     return f
 
 
-def toPlanes(depth):
+def toPlanes(depth, dither=None):
     """The unfused form of doCropPlanes (moe_to_output on the dense planes: H = C * h, W = w, C = 1, bits = depth): f(y, out=None) quantises a (C, h, w) fp16 / fp32 device
     image plane by plane into a flat uint8 device tensor of C * h * w samples (uint8 for depth 8, else uint16); out as doCropPlanes'."""
     if depth not in pixfmt.FORMATS.values():
         raise ValueError('toPlanes: depth must be one of {}, got {!r}'.format(sorted(pixfmt.FORMATS.values()), depth))
+    qf = ditherFlags('toPlanes', dither, depth, 'planes')          # (with a mode: one call per plane, so that a sample's coordinates are its own plane's -- the fused edge's bytes)
 
     def f(y, out=None):
         if y.device.type != 'cuda':
@@ -896,8 +918,10 @@ def toPlanes(depth):
         C, H, W = y.shape
         out = _planesOut('toPlanes', depth, C, H, W, out, y.device)
         cur = torch.cuda.current_stream(y.device)
-        _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], C * H, W, 1, int(depth), out.data_ptr(), _lib.U8 if depth == 8 else _lib.U16,
-                                            y.device.index or 0, cur.cuda_stream))
+        o_dt, es = (_lib.U8, 1) if depth == 8 else (_lib.U16, 2)
+        for c in range(C) if qf else (0,):
+            _lib.check(_lib.lib().moe_to_output(y.data_ptr() + c * H * W * y.element_size(), _DT[y.dtype], H if qf else C * H, W, 1, int(depth) | qf,
+                                                out.data_ptr() + c * H * W * es, o_dt, y.device.index or 0, cur.cuda_stream))
         y.record_stream(cur)
         return out
     return f

@@ -29,12 +29,16 @@ asked for by a rational integer polyphase filter that antialiases where it shrin
 With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on an SR or DN step of a chain on an RGB source (a file, an array, a bgr24 / bgr48le buffer) that step is luma-only:
 the net runs on Y' alone and Cb / Cr go to its output size through the existing resize; a last step whose fold writes the samples merges the planes inside that fold
 (moephoto_amd/luma.py, imageProcess.doCropLuma, moe_run_plan_luma).
+
+With {'op': 'output', 'dither': 'round' | 'ordered'} the chain's last operation -- a float becomes an 8-, 10-, 12- or 16-bit sample -- rounds to nearest or adds an 8 x 8
+ordered dither instead of truncating, in whichever edge writes the samples: the last fold, the unfused quantiser, the Y'CbCr conversion (moephoto_amd/quant.py is the
+definition; the MOE_Q_* flags of include/moephoto_amd.h).  'none', the default, changes nothing.
 """
 import math
 import time
 from functools import reduce
 
-from . import _lib, pixfmt, reuse as _reuse, runDN, runSR
+from . import _lib, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
 from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPlanes, fromPlanes, identity, lumaChroma, lumaKeys,
                            lumaMerge, lumaSplit, mergeAlpha, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
@@ -58,6 +62,29 @@ def _outputFormat(steps):
             pixfmt.check(*req)
             return req
     return None
+
+
+def _outputDither(steps):
+    """The `dither` key of the output step -- {'op': 'output', 'dither': 'round' | 'ordered'}; 'none' is the default -- checked before any model is loaded: 'round' / 'ordered'
+    or None.  The chain's quantising edge then rounds to nearest or adds the 8 x 8 ordered dither (moephoto_amd/quant.py): RGB samples at 8 bits at unit scale (the
+    inverse of the reader's / 255), 16-bit and planar samples at 2^bits, a Y'CbCr output in the integer conversion's rounding constants.  It needs no pixFmt and is valid
+    behind file, array, buffer and planar sources.  On a luma-only planar chain the key governs Y' alone: Cb / Cr come from the integer resampling filter
+    (resize_kernel_codes), which already rounds to nearest.  ValueError naming the key for an unknown value and for 'dither' beside 'width' / 'height' / 'fit': the
+    integer fit filter writes those samples, not a quantiser."""
+    mode = None
+    for s in steps:
+        if s.get('op') != 'output' or 'dither' not in s:
+            continue
+        v = s['dither']
+        if not isinstance(v, str) or v not in quant.MODES:
+            raise ValueError("output: 'dither' {!r} is not supported ({})".format(v, ', '.join(quant.MODES)))
+        mode = None if v == 'none' else v
+        for k in FIT_KEYS:
+            if k in s and mode is not None:
+                raise ValueError("output: 'dither' does not apply beside '{}': the integer fit filter writes those samples (it rounds to nearest)".format(k))
+    if mode is not None and any(k in s for s in steps if s.get('op') == 'output' for k in FIT_KEYS):
+        raise ValueError("output: 'dither' does not apply to a chain with 'width' / 'height' / 'fit': the integer fit filter writes those samples (it rounds to nearest)")
+    return mode
 
 
 # ---- luma-only steps on an RGB source (DESIGN.md section 17) --------------------------------------------------------------------------------------
@@ -118,16 +145,16 @@ def _lumaStep(op, o):
     return f, ('luma', g)
 
 
-def _lumaLast(op, o, unfused, bitDepth):
+def _lumaLast(op, o, unfused, bitDepth, dither=None):
     """genProcess' last step when it is a luma-only SR without ensemble or DN of strength 1: doCropLuma with the merge and the quantiser inside the last fold, downloaded
     as toOutput returns its image.  A four-plane image through a DN step (alpha rides around the net) takes the unfused form: the same bytes."""
     import numpy as np
-    quantise = toOutput(bitDepth)
+    quantise = toOutput(bitDepth, dither)
 
     def f(x):
         if op == 'DN' and x.shape[0] == 4:
             return quantise(toFloat(unfused(x)))
-        a = doCropLuma(o, o.prepare(x) if op == 'DN' else x, o.chroma, o.chromaMatrix, o.order, bitDepth).cpu().numpy()
+        a = doCropLuma(o, o.prepare(x) if op == 'DN' else x, o.chroma, o.chromaMatrix, o.order, bitDepth, dither=dither).cpu().numpy()
         return a.view(np.uint16) if bitDepth > 8 else a
     return f
 
@@ -272,12 +299,12 @@ def _planeChain(steps, fuse, rsteps=None):
     return funcs, nodes, scale, last
 
 
-def _genProcessPlanes(steps, fmts):
+def _genProcessPlanes(steps, fmts, dither=None):
     import numpy as np
     import torch
     src, dst = fmts
     funcs, nodes, scale, _ = _planeChain(steps, False)
-    quantise = toPlanes(pixfmt.FORMATS[dst])
+    quantise = toPlanes(pixfmt.FORMATS[dst], dither)
     chroma, resamplers = _planeChroma(steps), {}
     fit, quantise16, fitters = _planeFit(steps), toPlanes(16), {}
 
@@ -334,8 +361,9 @@ def genProcess(steps, bitDepth=8, outFile=None):
     steps = [dict(s) for s in steps]
     planar = _planeFormats(steps)
     _lumaCheck(steps, bool(planar))
+    dither = _outputDither(steps)          # (before any model is loaded)
     if planar:          # the decoder's own Y'CbCr 4:2:0 planes in, planar frames out
-        return _genProcessPlanes(steps, planar)
+        return _genProcessPlanes(steps, planar, dither)
     _refuseFit(steps)
     ctx = Context()
     funcs, nodes = [], []
@@ -373,7 +401,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         if _isLuma(o):          # a luma-only step; the last one's fold writes the samples itself where it can (an SR without ensemble, a DN of strength 1)
             f = _lumaStep(op, o)[0]
             if opt is work[-1] and not yuv and bitDepth in (8, 16) and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
-                fused = _lumaLast(op, o, f, bitDepth)
+                fused = _lumaLast(op, o, f, bitDepth, dither)
             else:
                 funcs.append(f)
         elif op == 'SR':
@@ -382,10 +410,10 @@ def genProcess(steps, bitDepth=8, outFile=None):
             funcs.append(RGBFilter(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
     if yuv:          # the encoder's planes from the canvas, then bytes
-        funcs += [toYuv(*yuv), lambda t: t.cpu().numpy().tobytes()]
+        funcs += [toYuv(*yuv, dither=dither), lambda t: t.cpu().numpy().tobytes()]
         run = lambda im: reduce(apply, funcs, im)
         return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
-    funcs += [fused] if fused else [toFloat, toOutput(bitDepth)]
+    funcs += [fused] if fused else [toFloat, toOutput(bitDepth, dither)]
     if has_file and outFile is not None:
         funcs.append(lambda im: writeFile(im, outFile, ctx))
     if has_buffer:
@@ -789,7 +817,7 @@ class _PlanesBackend(_DeviceBackend):
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
 
-def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False):
+def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False, dither=None):
     src, dst = fmts
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
@@ -802,9 +830,9 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
     D, cb = pixfmt.FORMATS[dst], pixfmt.planeOffsets(dst, w, h)[1]
     if last:          # the last step's two folds write straight into the slot's frame, at the Y and at the Cb offset: no canvas exists
         o, prepare = last
-        into, edgeName = (lambda x, out, reuse=None: doCropPlanes(o, prepare(x), D, out, reuse=reuse)), 'crop'
+        into, edgeName = (lambda x, out, reuse=None: doCropPlanes(o, prepare(x), D, out, reuse=reuse, dither=dither)), 'crop'
     else:
-        quantise = toPlanes(D)
+        quantise = toPlanes(D, dither)
         into, edgeName = (lambda x, out, reuse=None: quantise(x, out)), 'quantise'
 
     def edge(y, c, out, reuseY=None, reuseC=None):
@@ -861,10 +889,11 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
     return stream
 
 
-def _quantiseInto(bitDepth):
+def _quantiseInto(bitDepth, dither=None):
     """The unfused output edge: moe_to_output straight on a step's (C, H, W) result.  toFloat's fp32 copy of an fp16 result is skipped: fp16 -> fp32 is exact and the
     kernel widens each value itself, so the samples are toOutput(toFloat(y))'s."""
     lib_dt = _outStorage(bitDepth)[2]
+    bits = int(bitDepth) | quant.flags(dither, bitDepth, 'rgb')
 
     def f(y, out):
         import torch
@@ -875,7 +904,7 @@ def _quantiseInto(bitDepth):
         if tuple(out.shape) != (H, W, C):
             raise ValueError('frame stream: the chain gave {} where {} was planned'.format((H, W, C), tuple(out.shape)))
         cur = torch.cuda.current_stream(y.device)
-        _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], H, W, C, int(bitDepth), out.data_ptr(), lib_dt, y.device.index or 0, cur.cuda_stream))
+        _lib.check(_lib.lib().moe_to_output(y.data_ptr(), _DT[y.dtype], H, W, C, bits, out.data_ptr(), lib_dt, y.device.index or 0, cur.cuda_stream))
         y.record_stream(cur)
     return f
 
@@ -912,21 +941,25 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     not last, an ensemble, a blended DN, a chain with an {'op': 'output', 'pixFmt': ..} step -- merges unfused (lumaMerge) and the edge is what it is without the key
     for that chain's tail ('quantise').  'chroma': 'net', the default, is today's path; 'chromaMatrix' / 'order' beside it, unknown values, and any of the three keys on
     a step of a planar chain raise ValueError naming the key before a model is loaded.  reuse=True works unchanged: the change map applies to Y' as it is
-    (DESIGN.md section 17)."""
+    (DESIGN.md section 17).
+    With {'op': 'output', 'dither': 'round' | 'ordered'} whichever edge the chain ends in rounds to nearest or adds the 8 x 8 ordered dither instead of truncating
+    (_outputDither; moephoto_amd/quant.py): at every ring depth, with reuse and with views, the same bytes as genProcess + runFrames.  On a luma-only planar chain the key
+    governs Y' alone (Cb / Cr come from the integer filter, which rounds to nearest); beside 'width' / 'height' / 'fit' it is refused."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
     planar = _planeFormats(steps, width, height)
     _lumaCheck(steps, bool(planar))
+    dither = _outputDither(steps)          # (before any model is loaded)
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
-        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views)
+        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views, dither)
     _refuseFit(steps)
     bitDepth = int(steps[0].get('bitDepth', 16))
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
     _checkReuse(reuse)                   # (likewise)
     _checkViews(views)                   # (likewise)
-    yuvOf = toYuv(*yuv) if yuv else None
+    yuvOf = toYuv(*yuv, dither=dither) if yuv else None
     work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
     for opt in work:
         if opt['op'] not in stepOpts:
@@ -954,7 +987,7 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
         if _isLuma(o):          # a luma-only step: the merge rides in the last fold where that fold writes the samples; every other position or form merges unfused
             if last and not yuv and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
                 edge, edgeName = (lambda x, out, reuse=None, o=o, prepare=o.prepare if op == 'DN' else identity:
-                                  doCropLuma(o, prepare(x), o.chroma, o.chromaMatrix, o.order, bitDepth, out, reuse=reuse)), 'crop'
+                                  doCropLuma(o, prepare(x), o.chroma, o.chromaMatrix, o.order, bitDepth, out, reuse=reuse, dither=dither)), 'crop'
             else:
                 f, r = _lumaStep(op, o)
                 funcs.append(f)
@@ -963,24 +996,24 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
                 h, w = h * opt['scale'], w * opt['scale']
         elif op == 'SR':
             if last and o.ensemble == 0:
-                edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:], reuse=reuse) if yuv
-                                  else doCropOut(o, x, bitDepth, out, reuse=reuse)), 'crop'
+                edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:], reuse=reuse, dither=dither) if yuv
+                                  else doCropOut(o, x, bitDepth, out, reuse=reuse, dither=dither)), 'crop'
             else:
                 funcs.append(runSR.sr(o))
                 rsteps.append(_reuseSR(o, funcs[-1]))
             h, w = h * opt['scale'], w * opt['scale']
         elif last and o.strength == 1:         # RGBFilter on three planes with nothing to blend: prepare, doCrop
-            edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, o.prepare(x), yuv[0], out, *yuv[1:], reuse=reuse) if yuv
-                              else doCropOut(o, o.prepare(x), bitDepth, out, reuse=reuse)), 'crop'
+            edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, o.prepare(x), yuv[0], out, *yuv[1:], reuse=reuse, dither=dither) if yuv
+                              else doCropOut(o, o.prepare(x), bitDepth, out, reuse=reuse, dither=dither)), 'crop'
         elif last and config.filterOnDevice and isinstance(o.strength, (int, float)) and math.isfinite(o.strength):      # the blend with the frame inside the fold
-            edge, edgeName = (lambda x, out, reuse=None, o=o: yuvOf(_RGBFilter(o, x, reuse), out) if yuv else filterOut(o, x, bitDepth, out, reuse=reuse)), 'filter'
+            edge, edgeName = (lambda x, out, reuse=None, o=o: yuvOf(_RGBFilter(o, x, reuse), out) if yuv else filterOut(o, x, bitDepth, out, reuse=reuse, dither=dither)), 'filter'
         else:
             funcs.append(RGBFilter(o))
             rsteps.append(_reuseDN(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
     tiledEdge = edge is not None
     if edge is None:
-        edge = yuvOf or _quantiseInto(bitDepth)
+        edge = yuvOf or _quantiseInto(bitDepth, dither)
     state = _ReuseState(rsteps, tiledEdge) if reuse else None
     backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state, views)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
