@@ -180,8 +180,11 @@ int moe_net_set_exact_blocks(moe_net* net, int blocks);
 int moe_net_set_option(moe_net* net, const char* key, const char* value);
 /* keep fp32 copies of named intermediates during forwards (slow; debugging / layer-by-layer parity only).
  * enable = 0: off.  1 (any other non-zero value): taps, and the forwards leave their fused forms so that every layer has a tensor to tap.
- * 2: taps and nothing else -- no kernel choice changes, the forward is the production one and its result is bit-identical to enable = 0.  Defined for
- *    SEDN (MOE_EINVAL for the other architectures); its fused block tail then leaves per block K: bK.rb0, bK.rb2 (fp16 activations), bK.mean (the 256 fp32
+ * 2: taps and nothing else -- no kernel choice changes, the forward is the production one and its result is bit-identical to enable = 0.  MOE_EINVAL for lite.
+ *    Net2x / Net3x / Net4x / NetDN: stem, input2, arsb1..6 and the upsampler stages the production form stores (the fused tail leaves none).  A pair of the fp8 low-part
+ *    chain is tapped as hi + word 2^-9 and leaves NAME.hi (its fp16 part) and NAME.w8 (its e4m3 words as fp32) beside it; an fp16 pair leaves NAME.hi; block 6 of an SR
+ *    net, whose low part is not written, neither.
+ *    SEDN: its fused block tail then leaves per block K: bK.rb0, bK.rb2 (fp16 activations), bK.mean (the 256 fp32
  *    channel means, shape (B, 256, 1, 1)), bK.weff (the per-plane 64 x 64 x 9 weights as the fp16 MFMA A fragments lie in memory, shape (B, 72 * 512, 1, 1):
  *    fragment tap * 8 + ks * 2 + nblk, lane l, element e = W_eff[cout 32 nblk + l % 32][cin 16 ks + 8 (l / 32) + e][tap]) and blockK.
  * Where SEDN's forward takes the unfused form (enable = 1; more planes than workgroups; FP16X3) it leaves bK.rb0, bK.rb2, bK.rb4, bK.wtrans (the gated

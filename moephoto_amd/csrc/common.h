@@ -543,3 +543,5 @@ void launch_maxabsdiff(const float* a, const float* b, long long n, unsigned* ou
 // map[i][j] = some byte of block (i, j) differs between cur and prev in any of their n matrices of rows x row_bytes; prev <- cur in the same pass (moe_changed_blocks)
 void launch_changed_blocks(const void* cur, void* prev, int n, int rows, long long row_bytes, int block_rows, int block_bytes, unsigned char* map, hipStream_t s);
 void launch_nhwc_to_nchw_f32(const half_t* in, const half_t* in_lo, float* out, int B, int H, int W, int cs, int C, hipStream_t s);
+// ... of a pair whose low part is fp8 words (Act::lo8): out = hi + word 2^-9, out_w8 = the words as fp32
+void launch_nhwc8_to_nchw_f32(const half_t* in, const unsigned char* in_w8, float* out, float* out_w8, int B, int H, int W, int cs, int C, hipStream_t s);

@@ -699,8 +699,8 @@ int64_t moe_net_max_tile_pixels(const moe_net* n)
 int moe_net_set_debug(moe_net* n, int enable)
 {
     if (!n) return fail(MOE_EINVAL, "moe_net_set_debug: NULL net");
-    if (enable == 2 && n->arch != MOE_ARCH_SEDN)
-        return fail(MOE_EINVAL, "moe_net_set_debug: value 2 (taps of the production forward) is defined for SEDN only; 1 taps this architecture's unfused forward");
+    if (enable == 2 && n->arch == MOE_ARCH_LITE)
+        return fail(MOE_EINVAL, "moe_net_set_debug: value 2 (taps of the production forward) is defined for SEDN, Net2x / Net3x / Net4x and NetDN; 1 taps lite's unfused forward");
     n->debug = enable != 0 && enable != 2;
     n->tap_only = enable == 2;
     return MOE_OK;

@@ -171,13 +171,14 @@ int ArsbRun::run_trunk()
         const ConvLayer& L2 = n.convs[n.conv_index.at(k2)];
         const bool trunk64 = L1.w_arsb != 0;      // a bias-free 64 -> 64 trunk conv (weights.cpp packs w_arsb for exactly those)
         const int cin = (L1.cin == 48 && L2.cin == 48 && n.opt.k48) ? 48 : 64;      // NetDN: channels 48..63 are zeros in activations and weights
+        const bool drop6 = mixed && i == 6 && n.arch != MOE_ARCH_NETDN && !n.debug;      // the upsamplers take the fp16 part: nobody reads block 6's low part (arsb32c's drop_lo)
         if (arsb_fuse && !ex && (!mixed || (cur.has_lo && oth.has_lo)) && trunk64 && arsb32c_applicable(B, h, w, L1.slope, mixed, mixed, cin)) {
             if (!f.dry()) {
                 ArsbArgs q{};
                 q.x_hi = cur.hi; q.x_lo = mixed ? cur.lo : nullptr; q.y_hi = oth.hi; q.y_lo = mixed ? oth.lo : nullptr;
                 q.w1 = f.blob<half_t>(L1.w_hi); q.w2 = f.blob<half_t>(L2.w_hi); q.zero = f.small<half_t>("zero");      // (pack_conv order; conv_2's carry the ScaleLayer factor as well)
                 q.slope = L1.slope; q.B = B; q.H = h; q.W = w; q.cin = cin;
-                q.drop_lo = (mixed && i == 6 && n.arch != MOE_ARCH_NETDN && !n.debug) ? 1 : 0;      // the upsamplers take the fp16 part: nobody reads block 6's low part
+                q.drop_lo = drop6 ? 1 : 0;
                 const bool trace = n.opt.arsb_trace;   // MOE_ARSB_TRACE with a -DARSB_TRACE build: stamps of ARSB 3 -> /tmp/arsb_trace.bin
                 const size_t tb = 8 * 16 * 4 * 40 * 8;
                 if (trace && i == 3 && hipMalloc((void**)&q.trace, tb) == hipSuccess) (void)hipMemsetAsync(q.trace, 0, tb, s);
@@ -194,7 +195,10 @@ int ArsbRun::run_trunk()
                 }
                 if (!done) return fail(MOE_EINVAL, "internal error: arsb32c rejected layer %s its predicate took", k1.c_str());
             }
-            std::swap(cur, oth); cur.lo8 = oth.lo8 = false; f.tap("arsb" + std::to_string(i), cur, h, w, 64, n.C);      // (fp16 low parts out; the scratch side's form is its next writer's)
+            std::swap(cur, oth); cur.lo8 = oth.lo8 = false;      // (fp16 low parts out; the scratch side's form is its next writer's)
+            Act seen = cur;
+            if (drop6) seen.drop_lo();      // (cur.lo still points at the bytes block 6 did not write: the tap is the fp16 part alone)
+            f.tap("arsb" + std::to_string(i), seen, h, w, 64, n.C);
             continue;
         }
         if (ex && chain8 && n.opt.exact_fuse && n.opt.q8_impl == 1 && cur.lo8 && cur.has_lo && oth.has_lo && L1.wq_hi8 && L2.wq_hi8 && !L1.has_bias && !L2.has_bias && L2.slope == 1.f &&
@@ -276,6 +280,7 @@ int ArsbRun::run()
     // add (see Fwd::conv).  DESIGN.md section 5 has the error budget behind this choice.
     mixed = f.mixed;
     nx = mixed ? exact_blocks_of(n) : 0;
+    f.drop_taps();      // (the tapped forms leave different taps -- value 1 stores every upsampler stage, value 2 the production form's: none of another forward's stays behind)
     A = f.act(P, 64, mixed); Bb = f.act(P, 64, mixed); Cc = f.act(P, 64, mixed);
     if (mixed && n.opt.conv_impl != 2)
         return fail(MOE_EINVAL, "precision 'mixed' runs on the fast 3x3 kernels only: conv_impl=v1 (MOE_CONV_IMPL=v1) is a debugging switch for 'fp16' / 'fp16x3'");
@@ -283,7 +288,7 @@ int ArsbRun::run()
     // (Act::lo8): three quarters of the bytes of layers that are held by bytes (profiles/r03/o_stream_bytes.txt), no conversion of a_lo inside the kernel.
     // The last conv_2 writes an fp16 low part again -- into the stem's low-part buffer, which conv_input2 was the only reader of (its own buffer still
     // holds the fp8 residual it reads) -- for the fused ARSB kernels behind it.  The stem writes its low part in that form too (conv_input2 is its only
-    // reader: the U branch takes the fp16 part).  Debug taps read fp16 low parts: no chain under set_debug.
+    // reader: the U branch takes the fp16 part).  No chain under set_debug's value 1 (its taps were written for fp16 low parts); value 2 taps the chain as it runs (Fwd::tap).
     // NetDN (round 6): its tail convs read the stem's hi + lo pair at the very end -- tail3 takes the stem's low part as the same fp8 words (TailArgs::in1_lo8), so the
     // stem writes ONE low-part form here too.  What NetDN cannot share is the buffer: the two-launch fallback of the last exact block writes its fp16 low part into a
     // buffer of its own (lo16x) instead of over the stem's words.

@@ -1230,6 +1230,24 @@ __global__ void nhwc_to_nchw_kernel(const half_t* in, const half_t* in_lo, float
     out[idx] = v;
 }
 
+// the same copy of a pair whose low part is the chain's fp8 words (Act::lo8; [B][H][W][cs] bytes beside the fp16 part): out = hi + word 2^-9, the value op_add of
+// conv64_sq.hip / arsb_sq.hip adds (one fused multiply-add, as there), and the words themselves as fp32 in out_w8 -- the pair cannot be taken out of the sum again
+__global__ void nhwc8_to_nchw_kernel(const half_t* in, const unsigned char* in_w8, float* out, float* out_w8, int B, int H, int W, int cs, int C)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n = (long long)B * C * H * W;
+    if (idx >= n) return;
+    const int x = (int)(idx % W);
+    long long t = idx / W;
+    const int y = (int)(t % H); t /= H;
+    const int c = (int)(t % C);
+    const int b = (int)(t / C);
+    const long long o = ((long long)(b * H + y) * W + x) * cs + c;
+    const float w8 = __builtin_amdgcn_cvt_f32_fp8((int)in_w8[o], 0);
+    out[idx] = __builtin_fmaf(w8, 0.001953125f, (float)in[o]);
+    out_w8[idx] = w8;
+}
+
 }  // namespace
 
 void launch_stem(const StemArgs& a, hipStream_t s)
@@ -1541,6 +1559,12 @@ void launch_nhwc_to_nchw_f32(const half_t* in, const half_t* in_lo, float* out, 
 {
     const long long n = (long long)B * C * H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, in_lo, out, B, H, W, cs, C);
+}
+
+void launch_nhwc8_to_nchw_f32(const half_t* in, const unsigned char* in_w8, float* out, float* out_w8, int B, int H, int W, int cs, int C, hipStream_t s)
+{
+    const long long n = (long long)B * C * H * W;
+    hipLaunchKernelGGL(nhwc8_to_nchw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, in_w8, out, out_w8, B, H, W, cs, C);
 }
 
 // max |a - b| over n floats into *out as the bit pattern of a non-negative float (order-preserving as unsigned; a NaN difference counts as +inf): the comparison of

@@ -217,7 +217,7 @@ struct moe_net {
     int max_groups = 256;        // persistent workgroups per launch (one per CU, or option max_groups): set at finalize
     std::vector<std::string> prof_keys;          // comma-separated substrings of moe_net_set_profile
     bool debug = false;          // debug taps wanted (moe_net_set_debug, value 1): the forwards also leave their fused forms, so that every layer has a tensor to tap
-    bool tap_only = false;       // moe_net_set_debug, value 2 (SEDN): taps wanted and NOTHING else changes -- no kernel choice reads this, the forward is the production one
+    bool tap_only = false;       // moe_net_set_debug, value 2 (every family but lite): taps wanted and NOTHING else changes -- no kernel choice reads this, the forward is the production one
     bool tapping() const { return debug || tap_only; }
     // what forwards write: the stream set of ordinary forwards, the two sets of forwards that run ahead of the caller's stream, the records
     moe::StreamSet set;
@@ -338,15 +338,34 @@ struct Fwd {
 
     // tap `name`: the activation as fp32, hi + lo 2^-11 where it has a low part.  That sum does not say which fp16 value a single-pass reader of the pair takes
     // (a low part of exactly half an ulp puts the sum midway between two fp16 values), so a pair also leaves tap `name`.hi: its fp16 part alone
+    // A pair of the fp8 low-part chain (Act::lo8: value 2 on the ARSB nets, the chain does not exist under value 1) is hi + word 2^-9, what its readers add; it leaves
+    // `name`.hi and `name`.w8, the words as fp32: (hi, word) is then the stored pair exactly.  An activation whose low part was dropped leaves neither.
     void tap(const std::string& name, const Act& a, int H, int W, int cs, int C)
     {
         if (!n.tapping() || dry()) return;
-        tap_part(name, a.hi, a.lo, H, W, cs, C);
-        if (a.lo) tap_part(name + ".hi", a.hi, nullptr, H, W, cs, C);
-        else {      // (no stale fp16 part of an earlier forward that kept a pair here)
-            auto it = rt->taps.find(name + ".hi");
+        auto forget = [&](const std::string& k) {      // (no stale part of an earlier forward that kept another form here)
+            auto it = rt->taps.find(k);
             if (it != rt->taps.end()) { if (it->second.dev) (void)hipFree(it->second.dev); rt->taps.erase(it); }
+        };
+        if (a.lo && a.lo8) {
+            float* v = tap_alloc(name, H, W, C);
+            float* w8 = tap_alloc(name + ".w8", H, W, C);
+            if (v && w8) launch_nhwc8_to_nchw_f32(a.hi, (const unsigned char*)a.lo, v, w8, B, H, W, cs, C, s);
+            else { forget(name); forget(name + ".w8"); }      // (out of memory: no tap, never an unwritten one)
+        } else {
+            tap_part(name, a.hi, a.lo, H, W, cs, C);
+            forget(name + ".w8");
         }
+        if (a.lo) tap_part(name + ".hi", a.hi, nullptr, H, W, cs, C);
+        else forget(name + ".hi");
+    }
+    float* tap_alloc(const std::string& name, int H, int W, int C)
+    {
+        auto& t = rt->taps[name];
+        if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
+        if (hipMalloc((void**)&t.dev, (size_t)B * C * H * W * 4) != hipSuccess) { t.dev = nullptr; return nullptr; }
+        t.shape[0] = B; t.shape[1] = C; t.shape[2] = H; t.shape[3] = W;
+        return t.dev;
     }
     void tap_part(const std::string& name, const half_t* hi, const half_t* lo, int H, int W, int cs, int C)
     {

@@ -289,8 +289,9 @@ class EngineModule(object):
 
     # ---- debugging -----------------------------------------------------------------------------------
     def set_debug(self, flag=True):
-        """False / 0: off.  True / 1: keep fp32 copies of named intermediates; the forwards leave their fused forms so that every layer has one.  2 (SEDN): keep the copies
-        and change nothing else -- the forward is the production one, its fused block tail included (moe_net_set_debug)."""
+        """False / 0: off.  True / 1: keep fp32 copies of named intermediates; the forwards leave their fused forms so that every layer has one.  2 (every family but lite):
+        keep the copies and change nothing else -- the forward is the production one: SEDN's fused block tail, the ARSB nets' fp8 low-part chain, drop_lo, fork and fused
+        tail included (moe_net_set_debug).  A pair of that chain is tapped as hi + word 2^-9 and leaves NAME.hi and NAME.w8 (the e4m3 words as fp32) beside it."""
         _lib.check(_lib.lib().moe_net_set_debug(self._h, 2 if flag == 2 else 1 if flag else 0))
         return self
 

@@ -10,7 +10,8 @@ that noise over 1e5 samples differ by well under 2x, and the other 2x is left fo
 unmeasured, and a complete run writes every observed ratio to profiles/layer_parity/summary.md.  tests/test_layer_models_cpu.py shows, on the reference
 alone, that these bounds catch a residual that drops the stream's low part, a lost border column of conv_1 and an R tail that reads fp16 activations.
 
-Not bounded here: lite (held at 2e-5 end to end; SEDN has tests/test_gpu_sedn_layers.py), the untapped interior of the fp8 low-part chain (lo8), fp16 I/O edges."""
+The fp8 low-part chain (lo8, arsb_sq, drop_lo, the fork) that the default forward runs is held the same way by tests/test_gpu_chain8_layers.py, under set_debug's value 2.
+Not bounded here: lite (held at 2e-5 end to end; SEDN has tests/test_gpu_sedn_layers.py), fp16 I/O edges."""
 import os
 
 import pytest
@@ -44,7 +45,7 @@ def dev():
 @pytest.fixture(scope='module', autouse=True)
 def summary():
     yield
-    want = len(CASES) * len(SHAPES) * len(KINDS) + len(KEYS) * len(SHAPES) * len(KINDS)
+    want = len(CASES) * len(SHAPES) * len(KINDS) + 2 * len(KEYS) * len(SHAPES) * len(KINDS)      # (the production form: lo8 off and on)
     if len({k[:5] for k in ROWS}) != want:      # a partial run (-k ...) leaves the record of the last complete one alone
         return
     lines = ['# Layer parity: observed distance to the float64 model, in units of the reference\'s own spread', '',
@@ -129,7 +130,7 @@ def test_every_tapped_layer_against_its_float64_model(key, blocks, shape, kind, 
 @pytest.mark.parametrize('shape', SHAPES, ids=shape_id)
 @pytest.mark.parametrize('key', KEYS)
 def test_production_form_against_the_float64_composite(key, shape, kind, dev):
-    """set_debug turns off the fused tail, the fp8 low-part chain, drop_lo and the branch fork, so the fused tail has no taps.  With debug off and lo8 off
+    """set_debug's value 1 turns off the fused tail, the fp8 low-part chain, drop_lo and the branch fork, so the fused tail has no taps.  With debug off and lo8 off
     the trunk's kernels are the tapped run's: y of THAT run is held to the float64 composite "R branch from tap arsb6 + U branch from tap stem"
     (emu_layers.tail_fused) under the same two bounds, computed for the composite.  Where this fails while the tapped layers pass, the message says whether
     the run with fuse_tail off holds ITS composite (then the fused tail is at fault) or not (then the untapped trunk: drop_lo, the fork)."""
@@ -154,3 +155,26 @@ def test_production_form_against_the_float64_composite(key, shape, kind, dev):
     finally:
         m.set_option('lo8', 'on').set_option('fuse_tail', 1)
     assert not bad, '{} {} {}: {}'.format(key, shape_id(shape), kind, bad)
+    # The same with lo8 ON, the form that ships: set_debug(2) taps the production forward and changes nothing else (tests/test_gpu_chain8_layers.py holds its layers), so y
+    # of THAT run is held to the composite fed that run's own `stem` and `arsb6` -- arsb6 without a low part (drop_lo), the stem as (fp16, word); NetDN: its tail on arsb6
+    # and the stem's pair as stored (emu_layers.tail_dn8).  The same two bounds.
+    from moephoto_amd import _lib
+    m.set_debug(2)
+    try:
+        y2 = m(xd)[-1].float().cpu()
+        torch.cuda.synchronize()
+        taps2 = {}
+        for name in ('stem', 'arsb6'):
+            for part in ('', '.hi', '.w8'):
+                try:
+                    taps2[name + part] = torch.from_numpy(m.debug_tap(name + part))
+                except _lib.EngineError:
+                    pass      # (a part this form does not store)
+    finally:
+        m.set_debug(False)
+    assert 'stem.w8' in taps2 and ('arsb6.hi' in taps2) == (net.arch == 'netdn'), sorted(taps2)
+    with torch.no_grad():
+        ok, text, fig = el.check(y2, el.run_layer(net, 'y', taps2, torch.float64, chain8=True, fused=fused), el.run_layer(net, 'y', taps2, torch.float32, chain8=True, fused=fused))
+    ROWS[('production, lo8 on', key, -1, shape, kind, 'y (fused tail)' if fused else 'y')] = fig
+    print('{} {} {} y with lo8 on ({}): {}'.format(key, shape_id(shape), kind, 'fused tail' if fused else 'stored branches', text))
+    assert ok, '{} {} {} with lo8 on: {}'.format(key, shape_id(shape), kind, text)

@@ -333,6 +333,7 @@ NOT_IN_THE_TABLE = {
     'conv_mfma_kernel<1, 3>': 'generic 1x1 conv with split operands: shapes beyond conv1x1.hip (32-bit offsets)',
     'conv_mfma_kernel<9, 1>': 'generic 3x3 conv: conv_impl = v1 and 64-bit shapes',
     'nhwc_to_nchw_kernel': 'debug taps (moe_net_debug_tap)',
+    'nhwc8_to_nchw_kernel': "debug taps of a pair whose low part is the chain's fp8 words (moe_net_set_debug value 2 on the ARSB nets)",
     'tail_kernel<1>': 'unfused 1x1 tail (lite with fuse_tail = 0)',
     'tail_kernel<9>': 'first-generation 3x3 tail: MOE_TAIL_V1',
     'tailadd_kernel<false>': 'branch sum into output planes that are not 16-byte aligned',

@@ -180,15 +180,15 @@ def test_planes_input_separates_the_gates(shape):
     print('{}: the closest two planes differ by {:.2e} in their most different gate'.format(shape_id(shape), least))
 
 
-def test_debug_value_2_is_defined_for_sedn_only():
-    """moe_net_set_debug: 2 = taps of the production forward, SEDN; the other architectures refuse it with a message and keep 0 / 1"""
+def test_debug_value_2_is_defined_for_every_family_but_lite():
+    """moe_net_set_debug: 2 = taps of the production forward -- SEDN, and the ARSB nets with their fp8 low-part chain; lite refuses it with a message and keeps 0 / 1"""
     from moephoto_amd import _lib, models
-    for ctor in (models.Net2x, models.NetDN, lambda: models.Net(2)):
-        m = ctor()
-        with pytest.raises(_lib.EngineError, match='SEDN only'):
-            m.set_debug(2)
-        m.set_debug(True).set_debug(False)
-    models.SEDN().set_debug(2).set_debug(1).set_debug(0)
+    m = models.Net(2)
+    with pytest.raises(_lib.EngineError, match="1 taps lite's unfused forward"):
+        m.set_debug(2)
+    m.set_debug(True).set_debug(False)
+    for ctor in (models.SEDN, models.Net2x, models.Net3x, models.Net4x, models.NetDN):
+        ctor().set_debug(2).set_debug(1).set_debug(0)
 
 
 @pytest.mark.parametrize('shape', (SMALLEST, LARGEST), ids=shape_id)
