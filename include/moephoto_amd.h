@@ -412,10 +412,16 @@ int moe_run_plan_luma(moe_net* net, const moe_plan* plan, const void* img_y, int
 typedef struct moe_fit moe_fit;
 int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
                    int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out);
+/* The same filter on ONE INTERLEAVED image (bgr24 / bgr48le frames, RGBA arrays): src = h x w pixels of `channels` (1 .. 4) codes each, dst = oh x ow pixels of as many;
+ * the definition is pixfmt.fitPixels = fitPlanes on each channel.  The tables are moe_fit_create's, per PIXEL (m = ow or oh rows); the handle is of the same type and
+ * moe_fit_run / _info / _destroy serve it (info[3] = channels).  The kernel's tile is info[0] ELEMENTS wide, so it may end inside a pixel.  Refused (MOE_EINVAL, before any
+ * device call): everything moe_fit_create refuses, channels outside 1 .. 4, and a row of w or ow pixels whose elements do not fit an int. */
+int moe_fit_create_px(int channels, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
+                      int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out);
 /* One resample with the handle's geometry, asynchronous on `stream`.  src / dst: any 2-byte aligned address (any address at depth 8) -- the Cb plane of a frame starts
  * wherever its Y plane ends.  Refused: a NULL pointer, a misaligned one. */
 int moe_fit_run(const moe_fit* fit, const void* src, void* dst, void* stream);
-/* info[0 .. 4) = the kernel's output tile (width, height), the LDS bytes of a workgroup, the planes. */
+/* info[0 .. 4) = the kernel's output tile (width, height), the LDS bytes of a workgroup, the planes (moe_fit_create_px: the channels). */
 int moe_fit_info(const moe_fit* fit, int64_t info[4]);
 void moe_fit_destroy(moe_fit* fit);
 

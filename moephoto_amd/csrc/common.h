@@ -536,6 +536,8 @@ constexpr int FIT_TW = 128, FIT_TAPS = 16;
 constexpr size_t FIT_LDS_BUDGET = 80 * 1024;          // per workgroup: two of them share a CU's 160 KiB
 struct FitAxis { const int* off; const short* coef; int taps; };
 void launch_fit(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int oh, int ow, int planes, int th, size_t lds, const FitAxis& ax, const FitAxis& ay, hipStream_t s);
+// fit_px.hip: the same filter on one interleaved image of `channels` (1 .. 4) codes per pixel; h, w, oh, ow in pixels, the tile FIT_TW ELEMENTS x th
+void launch_fit_px(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int oh, int ow, int channels, int th, size_t lds, const FitAxis& ax, const FitAxis& ay, hipStream_t s);
 // (C, H, W) -> (C, h, w); mode 0 nearest, 1 bilinear, 2 bicubic (torch F.interpolate semantics, align_corners = False)
 void launch_resize(const void* src, void* dst, int dtype, int C, int H, int W, int h, int w, int mode, hipStream_t s);
 // max |a - b| over n floats, atomically folded into *out as the bits of a non-negative float (zero it first)

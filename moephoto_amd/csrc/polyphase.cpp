@@ -1,5 +1,5 @@
 // polyphase.cpp -- the entry points of the two integer polyphase resamplers of planar codes: moe_chroma_resample (chroma.hip: the chroma planes of a luma-only
-// chain, integer scales) and moe_fit_create / _run / _info / _destroy (fit.hip: planes brought to a fitted size).  What they check of the caller's tables is the
+// chain, integer scales) and moe_fit_create / moe_fit_create_px / _run / _info / _destroy (fit.hip, fit_px.hip: planes / an interleaved image brought to a fitted size).  What they check of the caller's tables is the
 // contract the kernels rely on (polyphase.h): the kernels check nothing.
 #include "net.h"
 
@@ -55,48 +55,54 @@ int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst,
 // ---- fitted sizes (fit.hip) ------------------------------------------------------------------------------
 struct moe_fit {
     int planes, ds, dd, h, w, oh, ow, th, device;
+    int channels;       // 0: `planes` planes (moe_fit_create); 1 .. 4: one interleaved image of as many channels (moe_fit_create_px)
     size_t lds;
     void* tab;          // one device block: ox[ow], oy[oh], then the coefficient rows of x and of y
     FitAxis ax, ay;
 };
 
 // The largest source window (samples along the axis) of any tile of `tile` output indices: off[last] + taps - off[first]; off is non-decreasing.
-static long long fit_window(const int32_t* off, long long m, int taps, int tile)
+// C > 1: the axis holds m pixels of C interleaved elements and a tile is `tile` ELEMENTS; its window is that of the pixels its elements belong to, in elements.
+static long long fit_window(const int32_t* off, long long m, int taps, int tile, int C = 1)
 {
     long long worst = 0;
-    for (long long o0 = 0; o0 < m; o0 += tile) {
-        const long long o1 = std::min<long long>(o0 + tile, m) - 1;
-        worst = std::max(worst, (long long)off[o1] + taps - off[o0]);
+    for (long long e0 = 0; e0 < m * C; e0 += tile) {
+        const long long e1 = std::min<long long>(e0 + tile, m * C) - 1;
+        worst = std::max(worst, ((long long)off[e1 / C] + taps - off[e0 / C]) * C);
     }
     return worst;
 }
 
-int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
-                   int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
+// Both creators (`who`): channels = 0 -- `planes` planes, a tile FIT_TW samples wide -- or the channels of one interleaved image, whose tile is FIT_TW ELEMENTS wide.
+static int fit_create(const char* who, int planes, int channels, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx,
+                      const int32_t* ox, int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
 {
-    if (!cx || !ox || !cy || !oy || !out) return fail(MOE_EINVAL, "moe_fit_create: NULL argument");
+    if (!cx || !ox || !cy || !oy || !out) return fail(MOE_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
-    if (int rc = poly_depths_check("moe_fit_create", src_depth, dst_depth)) return rc;
-    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "moe_fit_create: %d planes (1 to 4)", planes);
-    if (h < 1 || w < 1 || oh < 1 || ow < 1) return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld must be positive", (long long)w, (long long)h, (long long)ow, (long long)oh);
+    if (int rc = poly_depths_check(who, src_depth, dst_depth)) return rc;
+    if (planes < 1 || planes > 4) return fail(MOE_EINVAL, "%s: %d planes (1 to 4)", who, planes);
+    if (h < 1 || w < 1 || oh < 1 || ow < 1) return fail(MOE_EINVAL, "%s: size %lld x %lld -> %lld x %lld must be positive", who, (long long)w, (long long)h, (long long)ow, (long long)oh);
     if (h > 0x7fffffffll || w > 0x7fffffffll || oh > 0x7fffffffll || ow > 0x7fffffffll)
-        return fail(MOE_EINVAL, "moe_fit_create: size %lld x %lld -> %lld x %lld does not fit an int", (long long)w, (long long)h, (long long)ow, (long long)oh);
-    if (taps_x < 1 || taps_x > FIT_TAPS || taps_y < 1 || taps_y > FIT_TAPS) return fail(MOE_EINVAL, "moe_fit_create: %d x %d taps (1 to %d)", taps_x, taps_y, FIT_TAPS);
+        return fail(MOE_EINVAL, "%s: size %lld x %lld -> %lld x %lld does not fit an int", who, (long long)w, (long long)h, (long long)ow, (long long)oh);
+    const int C = channels ? channels : 1;
+    if (w * C > 0x7fffffffll || ow * C > 0x7fffffffll)
+        return fail(MOE_EINVAL, "%s: a row of %lld -> %lld pixels of %d channels does not fit an int", who, (long long)w, (long long)ow, C);
+    if (taps_x < 1 || taps_x > FIT_TAPS || taps_y < 1 || taps_y > FIT_TAPS) return fail(MOE_EINVAL, "%s: %d x %d taps (1 to %d)", who, taps_x, taps_y, FIT_TAPS);
     const int16_t* const coef[2] = {cx, cy};
     const int32_t* const off[2] = {ox, oy};
     const long long n[2] = {w, h}, m[2] = {ow, oh};
     const int taps[2] = {taps_x, taps_y};
     for (int a = 0; a < 2; ++a)
         for (long long o = 0; o < m[a]; ++o) {
-            if (int rc = poly_row_check("moe_fit_create", axis_name(a), "output", o, coef[a] + o * taps[a], taps[a])) return rc;
+            if (int rc = poly_row_check(who, axis_name(a), "output", o, coef[a] + o * taps[a], taps[a])) return rc;
             const long long first = off[a][o];
             if (first + taps[a] - 1 < 0 || first > n[a] - 1)
-                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld: its %d taps do not reach the %lld samples", axis_name(a), first, o, taps[a], n[a]);
+                return fail(MOE_EINVAL, "%s: %s offset %lld of output %lld: its %d taps do not reach the %lld samples", who, axis_name(a), first, o, taps[a], n[a]);
             if (o && first < off[a][o - 1])
-                return fail(MOE_EINVAL, "moe_fit_create: %s offset %lld of output %lld is below its predecessor's %d (offsets must not decrease)", axis_name(a), first, o, (int)off[a][o - 1]);
+                return fail(MOE_EINVAL, "%s: %s offset %lld of output %lld is below its predecessor's %d (offsets must not decrease)", who, axis_name(a), first, o, (int)off[a][o - 1]);
         }
     // the tile: FIT_TW outputs wide and th high, the largest th whose window (the row pass's int32 sums and the source samples) fits the budget
-    const long long es = src_depth == 8 ? 1 : 2, sw = fit_window(ox, ow, taps_x, FIT_TW);
+    const long long es = src_depth == 8 ? 1 : 2, sw = fit_window(ox, ow, taps_x, FIT_TW, C);
     int th = 0;
     long long lds = 0;
     for (int t : {32, 16, 8}) {
@@ -104,9 +110,9 @@ int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_dept
         lds = sh * FIT_TW * 4 + ((sh * sw * es + 15) & ~15ll);
         if (lds <= (long long)FIT_LDS_BUDGET) { th = t; break; }
     }
-    if (!th) return fail(MOE_EINVAL, "moe_fit_create: the source window of a %d x 8 tile takes %lld bytes of LDS (%lld at most): the offsets step too far", FIT_TW, lds, (long long)FIT_LDS_BUDGET);
+    if (!th) return fail(MOE_EINVAL, "%s: the source window of a %d x 8 tile takes %lld bytes of LDS (%lld at most): the offsets step too far", who, FIT_TW, lds, (long long)FIT_LDS_BUDGET);
     std::unique_ptr<moe_fit> f(new moe_fit{});
-    f->planes = planes; f->ds = src_depth; f->dd = dst_depth; f->h = (int)h; f->w = (int)w; f->oh = (int)oh; f->ow = (int)ow; f->th = th; f->device = device;
+    f->planes = planes; f->channels = channels; f->ds = src_depth; f->dd = dst_depth; f->h = (int)h; f->w = (int)w; f->oh = (int)oh; f->ow = (int)ow; f->th = th; f->device = device;
     f->lds = (size_t)lds;
     // the upload: offsets, then (16-byte aligned) the coefficient rows padded to FIT_TAPS with zeros
     const size_t n_off = (((size_t)(ow + oh) * 4) + 15) & ~(size_t)15, n_cx = (size_t)ow * FIT_TAPS * 2, n_cy = (size_t)oh * FIT_TAPS * 2;
@@ -122,7 +128,7 @@ int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_dept
     const hipError_t e = hipMemcpy(f->tab, host.data(), host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(f->tab);
-        return fail(MOE_EHIP, "moe_fit_create: the tables' upload failed: %s", hipGetErrorString(e));
+        return fail(MOE_EHIP, "%s: the tables' upload failed: %s", who, hipGetErrorString(e));
     }
     const unsigned char* d = (const unsigned char*)f->tab;
     f->ax = FitAxis{(const int*)d, (const short*)(d + n_off), taps_x};
@@ -131,11 +137,29 @@ int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_dept
     return MOE_OK;
 }
 
+int moe_fit_create(int planes, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
+                   int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
+{
+    return fit_create("moe_fit_create", planes, 0, src_depth, h, w, dst_depth, oh, ow, taps_x, cx, ox, taps_y, cy, oy, device, out);
+}
+
+int moe_fit_create_px(int channels, int src_depth, int64_t h, int64_t w, int dst_depth, int64_t oh, int64_t ow, int taps_x, const int16_t* cx, const int32_t* ox,
+                      int taps_y, const int16_t* cy, const int32_t* oy, int device, moe_fit** out)
+{
+    if (out) *out = nullptr;
+    if (channels < 1 || channels > 4) return fail(MOE_EINVAL, "moe_fit_create_px: %d channels (1 to 4)", channels);
+    return fit_create("moe_fit_create_px", 1, channels, src_depth, h, w, dst_depth, oh, ow, taps_x, cx, ox, taps_y, cy, oy, device, out);
+}
+
 int moe_fit_run(const moe_fit* f, const void* src, void* dst, void* stream)
 {
     if (!f || !src || !dst) return fail(MOE_EINVAL, "moe_fit_run: NULL argument");
     if (int rc = poly_aligned_check("moe_fit_run", src, f->ds, dst, f->dd)) return rc;
     HIP_TRY(hipSetDevice(f->device));
+    if (f->channels) {
+        launch_fit_px(src, f->ds, f->h, f->w, dst, f->dd, f->oh, f->ow, f->channels, f->th, f->lds, f->ax, f->ay, (hipStream_t)stream);
+        return launched("resize_kernel_fit_px");
+    }
     launch_fit(src, f->ds, f->h, f->w, dst, f->dd, f->oh, f->ow, f->planes, f->th, f->lds, f->ax, f->ay, (hipStream_t)stream);
     return launched("resize_kernel_fit");
 }
@@ -143,7 +167,7 @@ int moe_fit_run(const moe_fit* f, const void* src, void* dst, void* stream)
 int moe_fit_info(const moe_fit* f, int64_t info[4])
 {
     if (!f || !info) return fail(MOE_EINVAL, "moe_fit_info: NULL argument");
-    info[0] = FIT_TW; info[1] = f->th; info[2] = (int64_t)f->lds; info[3] = f->planes;
+    info[0] = FIT_TW; info[1] = f->th; info[2] = (int64_t)f->lds; info[3] = f->channels ? f->channels : f->planes;
     return MOE_OK;
 }
 

@@ -1,5 +1,5 @@
-// polyphase.h -- the arithmetic of the two integer polyphase kernels, once: resize_kernel_codes (chroma.hip: integer scales, phase tables in the kernel's arguments)
-// and resize_kernel_fit (fit.hip: any n -> m, per-output tables in device memory).  The definition: moephoto_amd/pixfmt.py, _polyAxis / _polyPlanes.
+// polyphase.h -- the arithmetic of the integer polyphase kernels, once: resize_kernel_codes (chroma.hip: integer scales, phase tables in the kernel's arguments),
+// resize_kernel_fit (fit.hip: any n -> m, per-output tables in device memory) and resize_kernel_fit_px (fit_px.hip: the same on interleaved pixels).  The definition: moephoto_amd/pixfmt.py, _polyAxis / _polyPlanes.
 // Output index o reads the taps clamp(first(o) + j, 0, n - 1) with 14-bit coefficients c[j] that sum to 2^14.  Row pass t = sum_j cx[j] * code in int32, column pass
 // v = sum_i cy[i] * t_i in int64, sample = clamp((v + 2^27) >> 28, 0, 2^Ds - 1) << (Dd - Ds) or >> (Ds - Dd).  No floating point anywhere.
 // A kernel keeps what is its own: the tile, where its window starts, where output o's first tap and coefficients come from, which thread computes which sample.
@@ -30,6 +30,36 @@ __device__ __forceinline__ void poly_window(const Src* __restrict__ plane, int h
         const Src* row = plane + (long long)min(max(y0 + r, 0), h - 1) * w;
         for (int c = threadIdx.x & 63; c < sw; c += 64) win[r * sw + c] = row[min(max(x0 + c, 0), w - 1)];
     }
+}
+
+// The same window of an interleaved image of C channels (fit_px.hip), x0 and sw counted in PIXELS: win[sh][sw * C], element c of a window row belongs to window
+// pixel c / C and win[r][c] = image[clamp(y0 + r, 0, h - 1)][clamp(x0 + c / C, 0, w - 1)][c % C] -- the clamp is per pixel: past an edge the edge PIXEL repeats,
+// channel by channel, where a clamp per element would repeat the last channel.
+template <int C, typename Src>
+__device__ __forceinline__ void poly_window_px(const Src* __restrict__ image, int h, int w, int y0, int x0, Src* win, int sh, int sw)
+{
+    // A thread's loads are issued in batches of up to KR rows x KC chunks of a row before the first of them is stored: with the few waves a CU holds beside a window of
+    // this size, one load in flight per thread left the kernel waiting on memory latency (profiles/fit_px/summary.md).
+    constexpr int KR = 4, KC = 4;
+    const int n = sw * C;
+    for (int r0 = threadIdx.x >> 6; r0 < sh; r0 += 4 * KR)
+        for (int c0 = threadIdx.x & 63; c0 < n; c0 += 64 * KC) {
+            Src v[KR][KC];
+#pragma unroll
+            for (int i = 0; i < KR; ++i) {
+                const Src* row = image + (long long)min(max(y0 + min(r0 + 4 * i, sh - 1), 0), h - 1) * w * C;      // (a row past the window reads the last one and is not stored)
+#pragma unroll
+                for (int k = 0; k < KC; ++k) {
+                    const int c = min(c0 + 64 * k, n - 1), p = c / C;                                              // (likewise a chunk past the row's end)
+                    v[i][k] = row[min(max(x0 + p, 0), w - 1) * C + (c - p * C)];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < KR; ++i)
+#pragma unroll
+                for (int k = 0; k < KC; ++k)
+                    if (r0 + 4 * i < sh && c0 + 64 * k < n) win[(r0 + 4 * i) * n + c0 + 64 * k] = v[i][k];
+        }
 }
 
 // sum_{j < taps} c[j] * e[j] in int32: |c| < 2^15 and codes < 2^16 are signed 24-bit factors, and the entry points refuse a row with sum |c| > 32767, so

@@ -16,6 +16,7 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
                                        polyphase filter of pixfmt.resampleChroma
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
+  fitPixels                            (no counterpart) -> moe_fit_create_px / moe_fit_run: the same filter on an interleaved image (pixfmt.fitPixels)
   lumaSplit, lumaMerge, doCropLuma     (no counterpart: the reference sends every plane of an RGB image through the net, python/runSR.py:37-40) -> moe_luma_split /
                                        moe_luma_merge / moe_run_plan_luma: a luma-only step -- the net on Y' alone, Cb / Cr resized, merged inside the last fold
                                        (the definition: moephoto_amd/luma.py)
@@ -982,9 +983,9 @@ def fitTables(method, n, m, loc='center'):
 class _FitHandle(object):
     """A moe_fit handle: the geometry and the tables on the device, freed with the object."""
 
-    def __init__(self, planes, srcDepth, h, w, dstDepth, oh, ow, tx, ty, device):
-        self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib().moe_fit_create(planes, srcDepth, h, w, dstDepth, oh, ow, tx[0], tx[1], tx[2], ty[0], ty[1], ty[2], device, ctypes.byref(self._h)))
+    def __init__(self, planes, srcDepth, h, w, dstDepth, oh, ow, tx, ty, device, create='moe_fit_create'):
+        self._h = ctypes.c_void_p()          # (create = 'moe_fit_create_px': `planes` are the channels of one interleaved image)
+        _lib.check(getattr(_lib.lib(), create)(planes, srcDepth, h, w, dstDepth, oh, ow, tx[0], tx[1], tx[2], ty[0], ty[1], ty[2], device, ctypes.byref(self._h)))
 
     def info(self):
         """dict(tile=(width, height), lds=bytes per workgroup, planes=..) of the kernel's launch."""
@@ -1020,6 +1021,35 @@ def fitPlanes(srcDepth, dstDepth, planes, h, w, oh, ow, method, loc='center'):
 
     def f(src_dev, out):
         _flatPair('fitPlanes', 'buffers', src_dev, n_in, out, n_out)
+        cur = torch.cuda.current_stream(src_dev.device)
+        _lib.check(_lib.lib().moe_fit_run(handle(src_dev.device)._h, src_dev.data_ptr(), out.data_ptr(), cur.cuda_stream))
+        src_dev.record_stream(cur)
+        return out
+    f.info = lambda device=None: handle(device if device is not None else torch.device(config.device())).info()
+    return f
+
+
+def fitPixels(srcDepth, dstDepth, channels, h, w, oh, ow, method):
+    """An interleaved image of codes brought to a fitted size (moe_fit_create_px / moe_fit_run; the definition: pixfmt.fitPixels): f(src_dev, out) reads h x w pixels
+    of `channels` codes each at srcDepth from src_dev (a flat contiguous uint8 device tensor of exactly those bytes: a bgr24 / bgr48le frame, or a view of one) and
+    writes oh x ow pixels at dstDepth into out, likewise.  fitPlanes' tables ('center' on both axes), cache, per-device handle and f.info() (planes = the channels)."""
+    for d in (srcDepth, dstDepth):
+        if d not in pixfmt.FORMATS.values():
+            raise ValueError('fitPixels: depth must be one of {}, got {!r}'.format(sorted(pixfmt.FORMATS.values()), d))
+    if not isinstance(channels, int) or isinstance(channels, bool) or not 1 <= channels <= 4:
+        raise ValueError('fitPixels: channels must be 1..4, got {!r}'.format(channels))
+    h, w, oh, ow = int(h), int(w), int(oh), int(ow)
+    tx, ty = fitTables(method, w, ow), fitTables(method, h, oh)          # (ValueError for what fitTable refuses)
+    n_in, n_out = channels * h * w * (1 if srcDepth == 8 else 2), channels * oh * ow * (1 if dstDepth == 8 else 2)
+    handles = {}
+
+    def handle(device):
+        if device not in handles:
+            handles[device] = _FitHandle(channels, srcDepth, h, w, dstDepth, oh, ow, tx, ty, device.index or 0, 'moe_fit_create_px')
+        return handles[device]
+
+    def f(src_dev, out):
+        _flatPair('fitPixels', 'buffers', src_dev, n_in, out, n_out)
         cur = torch.cuda.current_stream(src_dev.device)
         _lib.check(_lib.lib().moe_fit_run(handle(src_dev.device)._h, src_dev.data_ptr(), out.data_ptr(), cur.cuda_stream))
         src_dev.record_stream(cur)

@@ -315,3 +315,12 @@ def fitPlanes(P, srcDepth, dstDepth, oh, ow, method, loc='center'):
     ox, cx = fitTable(method, int(x.shape[2]), ow, loc)
     oy, cy = fitTable(method, int(x.shape[1]), oh, 'center')
     return _polyPlanes(x, (ox, cx), (oy, cy), srcDepth, dstDepth)
+
+
+def fitPixels(hwc, srcDepth, dstDepth, oh, ow, method):
+    """hwc = the (h, w, C) integer codes of an interleaved image, C = 1 .. 4, at depth srcDepth -> (oh, ow, C) codes at dstDepth: fitPlanes on each channel, 'center'
+    on both axes -- what the device kernel of interleaved images (resize_kernel_fit_px, moe_fit_create_px / moe_fit_run) is held to, byte for byte."""
+    x = np.asarray(hwc)
+    if x.ndim != 3 or not 1 <= x.shape[2] <= 4 or x.dtype.kind not in 'ui':
+        raise ValueError('fitPixels: the (h, w, C) integer codes of an interleaved image of 1 to 4 channels expected, got {} {}'.format(x.dtype, x.shape))
+    return np.ascontiguousarray(fitPlanes(x.transpose(2, 0, 1), srcDepth, dstDepth, oh, ow, method, 'center').transpose(1, 2, 0))

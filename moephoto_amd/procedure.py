@@ -33,6 +33,10 @@ the net runs on Y' alone and Cb / Cr go to its output size through the existing 
 With {'op': 'output', 'dither': 'round' | 'ordered'} the chain's last operation -- a float becomes an 8-, 10-, 12- or 16-bit sample -- rounds to nearest or adds an 8 x 8
 ordered dither instead of truncating, in whichever edge writes the samples: the last fold, the unfused quantiser, the Y'CbCr conversion (moephoto_amd/quant.py is the
 definition; the MOE_Q_* flags of include/moephoto_amd.h).  'none', the default, changes nothing.
+
+With {'op': 'resize', 'width': W, 'height': H, 'fit': 'bicubic'} as the last compute step of a chain on an RGB source both builders deliver W x H frames through the
+integer filter instead of moe_resize on a float canvas: the chain in front of the step writes its 16-bit samples as it would without the step, and one
+moe_fit_run on the interleaved frame (pixfmt.fitPixels, moe_fit_create_px) brings them to the size and the depth asked for.
 """
 import math
 import time
@@ -40,7 +44,7 @@ from functools import reduce
 
 from . import _lib, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPlanes, fromPlanes, identity, lumaChroma, lumaKeys,
+from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, lumaChroma, lumaKeys,
                            lumaMerge, lumaSplit, mergeAlpha, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -159,6 +163,53 @@ def _lumaLast(op, o, unfused, bitDepth, dither=None):
     return f
 
 
+def _lumaLastOnDevice(op, o, unfused):
+    """_lumaLast at 16 bits without the download, for a 'fit' resize step behind it (_pixelFitLast): the (H, W, C) samples stay on the device."""
+    quantise = _samplesOnDevice(16)
+
+    def f(x):
+        if op == 'DN' and x.shape[0] == 4:
+            return quantise(unfused(x))
+        return doCropLuma(o, o.prepare(x) if op == 'DN' else x, o.chroma, o.chromaMatrix, o.order, 16)
+    return f
+
+
+def _samplesOnDevice(bitDepth):
+    """toOutput(bitDepth)(toFloat(y)) without the download: y (C, H, W) -> the (H, W, C) samples on y's device (_quantiseInto)."""
+    into = _quantiseInto(bitDepth)
+
+    def f(y):
+        import torch
+        C, H, W = y.shape
+        out = torch.empty((H, W, C), dtype=_outStorage(bitDepth)[0], device=y.device)
+        into(y, out)
+        return out
+    return f
+
+
+def _pixelFitLast(fit, fused, bitDepth):
+    """genProcess' tail behind a 'fit' resize step: the chain's 16-bit samples on the device (the fused luma fold's, or the unfused quantiser's), one fitPixels to the
+    step's size and the chain's bitDepth, downloaded as toOutput returns its image.  The handle is kept per image shape."""
+    import numpy as np
+    import torch
+    samples, fitters = fused or _samplesOnDevice(16), {}
+
+    def f(y):
+        mid = samples(y).contiguous()
+        H, W, C = mid.shape
+        if (H, W, C) not in fitters:
+            oh, ow = _pixelFitSize(fit, H, W)          # (the ratios, now that the chain's size is known)
+            if len(fitters) >= 8:
+                fitters.clear()
+            fitters[(H, W, C)] = (oh, ow, fitPixels(16, bitDepth, C, H, W, oh, ow, fit['fit']))
+        oh, ow, run = fitters[(H, W, C)]
+        out = torch.empty((oh, ow, C), dtype=_outStorage(bitDepth)[0], device=mid.device)
+        run(_flatBytes(mid), _flatBytes(out))
+        a = out.cpu().numpy()
+        return a.view(np.uint16) if bitDepth > 8 else a
+    return f
+
+
 # ---- chains on the decoder's own planes -----------------------------------------------------------------------------------------------------
 # {'op': 'buffer', 'pixFmt': 'yuv420p10le'} as the source step: a frame is the decoder's planar Y'CbCr 4:2:0 frame (pixfmt.frameBytes bytes), the chain runs on Y' as a
 # (1, h, w) image and then on Cb / Cr as a (2, h / 2, w / 2) image -- every step treats each as it treats any (C, H, W) image, plans cached per shape on the step's
@@ -238,6 +289,78 @@ def _refuseFit(steps):
             for k in FIT_KEYS:
                 if k in s:
                     raise ValueError("output: '{}' applies to a chain on planar Y'CbCr 4:2:0 frames only ({{'op': 'buffer', 'pixFmt': ..}}); an RGB chain takes a resize step".format(k))
+
+
+# ---- a fitted size on an RGB chain: {'op': 'resize', .., 'fit': ..} ----------------------------------------------------------------
+def _pixelFit(steps, bitDepth):
+    """The resize step that carries a 'fit' key -- {'op': 'resize', 'width': W, 'height': H (or 'scaleW' / 'scaleH'), 'fit': 'nearest' | 'bilinear' | 'bicubic'} -- of a
+    chain whose source is not planar, its size keys converted, or None: the frame's samples are pixfmt.fitPixels of the 16-bit samples the chain in front of the step
+    writes, at the chain's bitDepth.  ValueError naming the key, before any model is loaded: such a step that is not the last compute step, 'method' beside 'fit', an
+    unknown 'fit', an axis without a size, a size below 1, 'dither' or 'pixFmt' on the output step (the filter rounds to nearest and writes RGB samples)."""
+    work = [s for s in steps if s.get('op') not in ('file', 'buffer', 'output')]
+    fits = [s for s in work if s.get('op') == 'resize' and 'fit' in s]
+    if not fits:
+        return None
+    s = fits[0]
+    if s is not work[-1]:
+        raise ValueError("resize: a step with 'fit' must be the last compute step of the chain: the integer filter writes the frame's samples")
+    if 'method' in s:
+        raise ValueError("resize: 'method' does not apply beside 'fit' (one of them names the filter: 'method' moe_resize's on floats, 'fit' the integer one)")
+    if not isinstance(s['fit'], str) or s['fit'] not in pixfmt.CHROMA_METHODS:
+        raise ValueError("resize: 'fit' {!r} is not supported ({})".format(s['fit'], ', '.join(pixfmt.CHROMA_METHODS)))
+    for size, scale in (('width', 'scaleW'), ('height', 'scaleH')):
+        if size not in s and scale not in s:
+            raise ValueError("resize: 'fit' needs a size: '{}' or '{}' is missing".format(size, scale))
+    for o in steps:
+        if o.get('op') == 'output':
+            if o.get('dither', 'none') != 'none':
+                raise ValueError("output: 'dither' does not apply to a chain whose resize step has 'fit': the integer fit filter writes those samples (it rounds to nearest)")
+            if o.get('pixFmt') is not None:
+                raise ValueError("output: 'pixFmt' does not apply to a chain whose resize step has 'fit': the filter writes the interleaved RGB samples")
+    if bitDepth not in (8, 16):
+        raise ValueError("resize: 'fit' writes 8- or 16-bit samples, the chain's bitDepth is {!r}".format(bitDepth))
+    convertValues(int, s, stepOpts['resize']['toInt'])
+    convertValues(float, s, stepOpts['resize']['toFloat'])
+    for k in ('width', 'height', 'scaleW', 'scaleH'):
+        if k in s and not s[k] > 0:
+            raise ValueError("resize: '{}' must be positive, got {!r}".format(k, s[k]))
+    return s
+
+
+def _pixelFitSize(s, h, w):
+    """(oh, ow) of a 'fit' resize step behind a chain that gives h x w, rounded as imageProcess.resize rounds; ValueError naming the key for a ratio beyond
+    pixfmt.FIT_MAX_DOWN down or pixfmt.FIT_MAX_UP up."""
+    oh = round(h * s['scaleH']) if 'scaleH' in s else s['height']
+    ow = round(w * s['scaleW']) if 'scaleW' in s else s['width']
+    for have, want, size, scale in ((w, ow, 'width', 'scaleW'), (h, oh, 'height', 'scaleH')):
+        k = scale if scale in s else size
+        if want < 1 or have > pixfmt.FIT_MAX_DOWN * want:
+            raise ValueError("resize: '{}' ({} samples) shrinks the chain's {} by more than {}".format(k, want, have, pixfmt.FIT_MAX_DOWN))
+        if want > pixfmt.FIT_MAX_UP * have:
+            raise ValueError("resize: '{}' ({} samples) enlarges the chain's {} by more than {}".format(k, want, have, pixfmt.FIT_MAX_UP))
+    return oh, ow
+
+
+def _chainSize(work, h, w):
+    """(h, w) a chain of compute steps gives from h x w frames, from the step dicts alone -- an SR step's 'scale', a resize step's size keys as the builders convert
+    and round them -- so that a 'fit' step's ratio can be refused before the first model is loaded; None where a step's keys do not say (the builder's own walk then
+    raises what it always raised)."""
+    try:
+        for s in work:
+            if s['op'] == 'SR':
+                h, w = h * int(s['scale']), w * int(s['scale'])
+            elif s['op'] == 'resize':
+                h = round(h * float(s['scaleH'])) if 'scaleH' in s else int(s['height'])
+                w = round(w * float(s['scaleW'])) if 'scaleW' in s else int(s['width'])
+    except (KeyError, TypeError, ValueError):
+        return None
+    return h, w
+
+
+def _flatBytes(t):
+    """A contiguous device tensor of samples as fitPixels takes it: flat uint8."""
+    import torch
+    return t.view(torch.uint8).reshape(-1)
 
 
 def _planeChroma(steps):
@@ -376,12 +499,14 @@ def genProcess(steps, bitDepth=8, outFile=None):
         funcs.append(readFile(context=ctx))
     if has_buffer:     # video frames: raw bgr24 / bgr48le in, the same out (channel order is irrelevant: planes are independent)
         bitDepth = int(steps[0].get('bitDepth', 16))
+    fit = _pixelFit(steps, bitDepth)          # (before any model is loaded)
+    if has_buffer:
         funcs.append(toNumPy(bitDepth))
     funcs.append(toTorch(bitDepth, config.dtype(), config.device()))
-    work, fused = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')], None
+    work, fused = [s for s in steps if s['op'] not in ('file', 'buffer', 'output') and s is not fit], None
     for opt in steps:
         op = opt['op']
-        if op in ('file', 'buffer', 'output'):
+        if op in ('file', 'buffer', 'output') or opt is fit:
             continue
         if op not in stepOpts:
             raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(op))
@@ -401,7 +526,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         if _isLuma(o):          # a luma-only step; the last one's fold writes the samples itself where it can (an SR without ensemble, a DN of strength 1)
             f = _lumaStep(op, o)[0]
             if opt is work[-1] and not yuv and bitDepth in (8, 16) and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
-                fused = _lumaLast(op, o, f, bitDepth, dither)
+                fused = _lumaLastOnDevice(op, o, f) if fit else _lumaLast(op, o, f, bitDepth, dither)
             else:
                 funcs.append(f)
         elif op == 'SR':
@@ -413,7 +538,11 @@ def genProcess(steps, bitDepth=8, outFile=None):
         funcs += [toYuv(*yuv, dither=dither), lambda t: t.cpu().numpy().tobytes()]
         run = lambda im: reduce(apply, funcs, im)
         return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
-    funcs += [fused] if fused else [toFloat, toOutput(bitDepth, dither)]
+    if fit:
+        funcs.append(_pixelFitLast(fit, fused, bitDepth))
+        nodes.append(dict(op='resize', mode=fit['fit']))
+    else:
+        funcs += [fused] if fused else [toFloat, toOutput(bitDepth, dither)]
     if has_file and outFile is not None:
         funcs.append(lambda im: writeFile(im, outFile, ctx))
     if has_buffer:
@@ -620,9 +749,10 @@ class _DeviceBackend(object):
     edge on torch's current stream; download = async D2H into the slot's pinned buffer on a third stream.  timing: the events take timestamps and `stats` sums the
     milliseconds per stage over the collected frames (tools/frame_stream_bench.py)."""
 
-    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None, reuse=None, views=False):
+    def __init__(self, funcs, edge, bitDepth, width, height, outHW, depth, timing=False, outBytes=None, reuse=None, views=False, fit=None):
         import torch
         self.torch, self.funcs, self.edge, self.bitDepth, self.timing, self.reuse, self.views = torch, funcs, edge, bitDepth, timing, reuse, views
+        self.fit = fit          # ((h, w), imageProcess.fitPixels' f) behind a 'fit' resize step: the edge writes a slot's `mid` (16-bit samples of h x w), f the slot's `out`
         self.dev = torch.device(config.device())
         if self.dev.type != 'cuda':
             raise _lib.EngineError('frame stream: needs a HIP device (moephoto_amd has no CPU path)')
@@ -635,6 +765,8 @@ class _DeviceBackend(object):
         for _ in range(depth):
             s = self._slot(out_dt)
             s.update(out=torch.empty(oshape, dtype=o_dt, device=self.dev), pin_out=torch.empty(oshape, dtype=o_dt, pin_memory=True))
+            if fit is not None:
+                s['mid'] = torch.empty((fit[0][0], fit[0][1], 3), dtype=_outStorage(16)[0], device=self.dev)
             s['in_bytes'] = s['pin_in'].numpy().view('uint8').reshape(-1)
             s['out_np'] = s['pin_out'].numpy()
             if views:          # the slot's pinned output as the caller sees it: flat bytes, read-only (the ring writes it through the tensor)
@@ -718,14 +850,17 @@ class _DeviceBackend(object):
         def work(stream):
             _lib.check(_lib.lib().moe_to_float(s['raw'].data_ptr(), self.src_dt, self.bitDepth, self.H, self.W, 3, s['x'].data_ptr(), _DT[s['x'].dtype],
                                                self.dev.index or 0, stream.cuda_stream))
+            into = s['out'] if self.fit is None else s['mid']
             if R is None:
-                self.edge(reduce(apply, self.funcs, s['x']), s['out'])
-                return
-            x, region = R.walk('rgb', s['x'], changed)
-            if R.tiledEdge:
-                self.edge(x, s['out'], R.edgeCallback('rgb', region))
+                self.edge(reduce(apply, self.funcs, s['x']), into)
             else:
-                self.edge(x, s['out'])
+                x, region = R.walk('rgb', s['x'], changed)
+                if R.tiledEdge:
+                    self.edge(x, into, R.edgeCallback('rgb', region))
+                else:
+                    self.edge(x, into)
+            if self.fit is not None:
+                self.fit[1](_flatBytes(into), _flatBytes(s['out']))
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
     def download(self, slot, wait, record):
@@ -944,7 +1079,13 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     (DESIGN.md section 17).
     With {'op': 'output', 'dither': 'round' | 'ordered'} whichever edge the chain ends in rounds to nearest or adds the 8 x 8 ordered dither instead of truncating
     (_outputDither; moephoto_amd/quant.py): at every ring depth, with reuse and with views, the same bytes as genProcess + runFrames.  On a luma-only planar chain the key
-    governs Y' alone (Cb / Cr come from the integer filter, which rounds to nearest); beside 'width' / 'height' / 'fit' it is refused."""
+    governs Y' alone (Cb / Cr come from the integer filter, which rounds to nearest); beside 'width' / 'height' / 'fit' it is refused.
+    With {'op': 'resize', 'width': W, 'height': H, 'fit': 'nearest' | 'bilinear' | 'bicubic'} (or 'scaleW' / 'scaleH') as the last compute step of a chain whose source
+    is not planar the finished frames are W x H x 3 at the chain's bitDepth: the edge the chain ends in without that step ('crop', 'filter' or 'quantise') writes 16-bit
+    samples of the chain's own size into one more device buffer per slot, and one moe_fit_run on the interleaved frame writes the slot's frame -- pixfmt.fitPixels of
+    those samples, byte for byte; `edge` reads 'crop+fit', 'filter+fit' or 'quantise+fit'.  reuse and views work unchanged.  Refused by key before a model is loaded:
+    such a step anywhere else, 'method' beside 'fit', an unknown 'fit', an axis without a size, 'dither' or 'pixFmt' on the output step, a ratio beyond 4 down or 16 up
+    of the chain's own size -- known from the step dicts alone (_chainSize: the SR steps' scales, the resize steps' sizes) -- (DESIGN.md section 19)."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
@@ -959,13 +1100,17 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     yuv = _outputFormat(steps)           # (likewise)
     _checkReuse(reuse)                   # (likewise)
     _checkViews(views)                   # (likewise)
+    fit = _pixelFit(steps, bitDepth)     # (likewise)
+    edgeDepth = 16 if fit else bitDepth          # (a 'fit' resize step: the edge writes 16-bit samples of the chain's own size, the slot's frame is the filter's)
     yuvOf = toYuv(*yuv, dither=dither) if yuv else None
-    work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output')]
+    work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output') and s is not fit]
     for opt in work:
         if opt['op'] not in stepOpts:
             raise NotImplementedError('op "{}" is not part of the SR/DN hot path this engine implements'.format(opt['op']))
     funcs, nodes, edge, edgeName, rsteps = [], [], None, 'quantise', []
     h, w = int(height), int(width)
+    if fit and _chainSize(work, h, w):          # the fit's ratio against the chain's own size, known here from the step dicts: refused before any model is loaded
+        _pixelFitSize(fit, *_chainSize(work, h, w))
     for k, opt in enumerate(work):
         op, last = opt['op'], k == len(work) - 1
         so = stepOpts[op]
@@ -987,7 +1132,7 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
         if _isLuma(o):          # a luma-only step: the merge rides in the last fold where that fold writes the samples; every other position or form merges unfused
             if last and not yuv and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
                 edge, edgeName = (lambda x, out, reuse=None, o=o, prepare=o.prepare if op == 'DN' else identity:
-                                  doCropLuma(o, prepare(x), o.chroma, o.chromaMatrix, o.order, bitDepth, out, reuse=reuse, dither=dither)), 'crop'
+                                  doCropLuma(o, prepare(x), o.chroma, o.chromaMatrix, o.order, edgeDepth, out, reuse=reuse, dither=dither)), 'crop'
             else:
                 f, r = _lumaStep(op, o)
                 funcs.append(f)
@@ -997,25 +1142,31 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
         elif op == 'SR':
             if last and o.ensemble == 0:
                 edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, x, yuv[0], out, *yuv[1:], reuse=reuse, dither=dither) if yuv
-                                  else doCropOut(o, x, bitDepth, out, reuse=reuse, dither=dither)), 'crop'
+                                  else doCropOut(o, x, edgeDepth, out, reuse=reuse, dither=dither)), 'crop'
             else:
                 funcs.append(runSR.sr(o))
                 rsteps.append(_reuseSR(o, funcs[-1]))
             h, w = h * opt['scale'], w * opt['scale']
         elif last and o.strength == 1:         # RGBFilter on three planes with nothing to blend: prepare, doCrop
             edge, edgeName = (lambda x, out, reuse=None, o=o: doCropYuv(o, o.prepare(x), yuv[0], out, *yuv[1:], reuse=reuse, dither=dither) if yuv
-                              else doCropOut(o, o.prepare(x), bitDepth, out, reuse=reuse, dither=dither)), 'crop'
+                              else doCropOut(o, o.prepare(x), edgeDepth, out, reuse=reuse, dither=dither)), 'crop'
         elif last and config.filterOnDevice and isinstance(o.strength, (int, float)) and math.isfinite(o.strength):      # the blend with the frame inside the fold
-            edge, edgeName = (lambda x, out, reuse=None, o=o: yuvOf(_RGBFilter(o, x, reuse), out) if yuv else filterOut(o, x, bitDepth, out, reuse=reuse, dither=dither)), 'filter'
+            edge, edgeName = (lambda x, out, reuse=None, o=o: yuvOf(_RGBFilter(o, x, reuse), out) if yuv else filterOut(o, x, edgeDepth, out, reuse=reuse, dither=dither)), 'filter'
         else:
             funcs.append(RGBFilter(o))
             rsteps.append(_reuseDN(o))
         nodes.append(dict(op=op, model=opt.get('model'), scale=opt.get('scale', 1)))
     tiledEdge = edge is not None
     if edge is None:
-        edge = yuvOf or _quantiseInto(bitDepth, dither)
+        edge = yuvOf or _quantiseInto(edgeDepth, dither)
+    outHW, fitted = (h, w), None
+    if fit:          # the edge above fills the slot's 16-bit samples of h x w; one moe_fit_run from them writes the slot's frame, behind everything reuse touches
+        outHW = _pixelFitSize(fit, h, w)
+        fitted = ((h, w), fitPixels(16, bitDepth, 3, h, w, outHW[0], outHW[1], fit['fit']))
+        edgeName += '+fit'
+        nodes.append(dict(op='resize', mode=fit['fit']))
     state = _ReuseState(rsteps, tiledEdge) if reuse else None
-    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, (h, w), depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state, views)
+    backend = _DeviceBackend(funcs, edge, bitDepth, width, height, outHW, depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state, views, fitted)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
     stream.edge, stream.reuse = edgeName, (state.stats if reuse else None)
     return stream
