@@ -369,6 +369,20 @@ int moe_run_plan_planes(moe_net* net, const moe_plan* plan, const void* img, int
 int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps,
                         const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, int device, void* stream);
 
+/* The same planes steered by the finished luma: a joint bilateral filter, in integers -- the definition is moephoto_amd/pixfmt.py (guidedTable, guidedRange, lumaGuide,
+ * guidedChroma) and the device matches it byte for byte.  src_c = the two planes of h x w chroma codes of the SOURCE frame and src_y its 2 h x 2 w luma plane, at
+ * src_depth; dst_c = two planes of h * scale x w * scale at dst_depth, written; dst_y = the OUTPUT frame's luma plane, 2 h * scale x 2 w * scale at dst_depth, read
+ * as the chain wrote it.  Any 2-byte aligned address (any address at depth 8).  loc sites the horizontal axis of the guide (the tables carry the filter's own siting).
+ * cx / ox and cy / oy are HOST tables, per axis scale x 4 8-bit coefficients and scale offsets: output index o = q * scale + p reads the source samples
+ * clamp(q + off[p] + j, 0, n - 1), j < 4; range64 = 64 range weights.  Per sample w = cy cx range64[min(|GH - GL| >> 10, 63)] over the 16 taps,
+ * s = (sum w code + den / 2) / den with den = sum w, then << (dst_depth - src_depth) or >> (src_depth - dst_depth).  Refused (MOE_EINVAL, before any device call): a
+ * NULL pointer, a depth outside {8, 10, 12, 16}, h or w below 1 or sizes beyond int, scale outside 2 .. 16, an unknown loc, a misaligned pointer, a coefficient row
+ * that does not sum to 256, an offset outside [-2, 1], a range table with a zero entry, a dst_c that overlaps dst_y.  Asynchronous on `stream`. */
+#define MOE_CHROMA_CENTER 0
+#define MOE_CHROMA_LEFT 1
+int moe_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h, int w, void* dst_c, const void* dst_y, int dst_depth, int scale, int loc,
+                      const uint8_t* cx, const int8_t* ox, const uint8_t* cy, const int8_t* oy, const uint8_t* range64, int device, void* stream);
+
 /* ---- luma-only steps on RGB images ------------------------------------------------------------------------
  * The reference sends every plane of a colour image through the net (planes are the batch: python/runSR.py:37-40); none of these entry points has a counterpart in
  * it.  None of the SR / DN nets convolves planes jointly, so a step may run on Y' alone while Cb / Cr go to the output's size through moe_resize: a third of the net's

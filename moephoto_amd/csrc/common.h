@@ -530,6 +530,9 @@ void launch_to_float_planes(const void* src, int depth, int H, int W, void* dst_
 // (relative to q = o / scale) with the 14-bit coefficients coef[p][0 .. TAPS) (moephoto_amd/pixfmt.py: chromaTable)
 struct ChromaTab { short coef[16][4]; signed char off[16]; };
 void launch_chroma_resample(const void* src, int src_depth, int h, int w, void* dst, int dst_depth, int scale, int taps, const ChromaTab& tx, const ChromaTab& ty, hipStream_t s);
+// chroma_guided.hip: moe_chroma_guided's joint bilateral filter (moephoto_amd/pixfmt.py: guidedTable / guidedChroma); the HOST tables as the entry point took and checked them
+void launch_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h, int w, void* dst_c, const void* dst_y, int dst_depth, int scale, int left,
+                          const unsigned char* cx, const signed char* ox, const unsigned char* cy, const signed char* oy, const unsigned char* range64, hipStream_t s);
 // fit.hip: one axis of moe_fit_run's rational polyphase filter, in DEVICE memory: output index o reads `taps` source samples from off[o] on with the 14-bit coefficients
 // coef[o * FIT_TAPS + 0 .. taps) (rows of FIT_TAPS, 32 bytes, the base 16-byte aligned; moephoto_amd/pixfmt.py: fitTable).  A workgroup's output tile is FIT_TW x th.
 constexpr int FIT_TW = 128, FIT_TAPS = 16;

@@ -1,5 +1,5 @@
 // polyphase.cpp -- the entry points of the two integer polyphase resamplers of planar codes: moe_chroma_resample (chroma.hip: the chroma planes of a luma-only
-// chain, integer scales) and moe_fit_create / moe_fit_create_px / _run / _info / _destroy (fit.hip, fit_px.hip: planes / an interleaved image brought to a fitted size).  What they check of the caller's tables is the
+// chain, integer scales; moe_chroma_guided, chroma_guided.hip: the same planes steered by the finished luma) and moe_fit_create / moe_fit_create_px / _run / _info / _destroy (fit.hip, fit_px.hip: planes / an interleaved image brought to a fitted size).  What they check of the caller's tables is the
 // contract the kernels rely on (polyphase.h): the kernels check nothing.
 #include "net.h"
 
@@ -50,6 +50,39 @@ int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst,
     HIP_TRY(hipSetDevice(device));
     launch_chroma_resample(src, src_depth, h, w, dst, dst_depth, scale, taps, t[0], t[1], (hipStream_t)stream);
     return launched("resize_kernel_codes");
+}
+
+// The guided form of the same planes (chroma_guided.hip): what the kernel's 32-bit row sums and its exact division rest on is checked here.
+int moe_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h, int w, void* dst_c, const void* dst_y, int dst_depth, int scale, int loc,
+                      const uint8_t* cx, const int8_t* ox, const uint8_t* cy, const int8_t* oy, const uint8_t* range64, int device, void* stream)
+{
+    if (!src_c || !src_y || !dst_c || !dst_y || !cx || !ox || !cy || !oy || !range64) return fail(MOE_EINVAL, "moe_chroma_guided: NULL argument");
+    if (int rc = poly_depths_check("moe_chroma_guided", src_depth, dst_depth)) return rc;
+    if (h < 1 || w < 1) return fail(MOE_EINVAL, "moe_chroma_guided: size %d x %d must be positive", w, h);
+    if (scale < 2 || scale > 16) return fail(MOE_EINVAL, "moe_chroma_guided: scale %d (2 to 16)", scale);
+    if (2ll * h * scale > 0x7fffffffll || 2ll * w * scale > 0x7fffffffll)
+        return fail(MOE_EINVAL, "moe_chroma_guided: the luma plane of %d x %d chroma samples times %d does not fit an int", w, h, scale);
+    if (loc != MOE_CHROMA_CENTER && loc != MOE_CHROMA_LEFT) return fail(MOE_EINVAL, "moe_chroma_guided: loc %d (MOE_CHROMA_CENTER or MOE_CHROMA_LEFT)", loc);
+    if (int rc = poly_aligned_check("moe_chroma_guided", src_c, src_depth, dst_c, dst_depth)) return rc;
+    if (src_depth > 8 && ((uintptr_t)src_y & 1)) return fail(MOE_EINVAL, "moe_chroma_guided: src_y is not 2-byte aligned (depth %d: uint16 samples)", src_depth);
+    if (dst_depth > 8 && ((uintptr_t)dst_y & 1)) return fail(MOE_EINVAL, "moe_chroma_guided: dst_y is not 2-byte aligned (depth %d: uint16 samples)", dst_depth);
+    const uint8_t* const coef[2] = {cx, cy};
+    const int8_t* const off[2] = {ox, oy};
+    for (int a = 0; a < 2; ++a)
+        for (int p = 0; p < scale; ++p) {
+            const uint8_t* c = coef[a] + p * 4;
+            if (c[0] + c[1] + c[2] + c[3] != 256)
+                return fail(MOE_EINVAL, "moe_chroma_guided: %s coefficients of phase %d sum to %d (must be 256)", axis_name(a), p, c[0] + c[1] + c[2] + c[3]);
+            if (off[a][p] < -2 || off[a][p] > 1) return fail(MOE_EINVAL, "moe_chroma_guided: %s offset %d of phase %d (-2 to 1)", axis_name(a), (int)off[a][p], p);
+        }
+    for (int d = 0; d < 64; ++d)
+        if (!range64[d]) return fail(MOE_EINVAL, "moe_chroma_guided: range weight %d is zero (the denominator must not vanish)", d);
+    const long long es = dst_depth == 8 ? 1 : 2, samples = (long long)h * scale * w * scale;
+    const uintptr_t y0 = (uintptr_t)dst_y, y1 = y0 + (uintptr_t)(4 * samples * es), c0 = (uintptr_t)dst_c, c1 = c0 + (uintptr_t)(2 * samples * es);
+    if (c0 < y1 && y0 < c1) return fail(MOE_EINVAL, "moe_chroma_guided: dst_c overlaps dst_y (the kernel reads the luma plane while it writes the chroma planes)");
+    HIP_TRY(hipSetDevice(device));
+    launch_chroma_guided(src_c, src_y, src_depth, h, w, dst_c, dst_y, dst_depth, scale, loc == MOE_CHROMA_LEFT, cx, ox, cy, oy, range64, (hipStream_t)stream);
+    return launched("resize_kernel_guided");
 }
 
 // ---- fitted sizes (fit.hip) ------------------------------------------------------------------------------

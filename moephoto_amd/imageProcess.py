@@ -14,6 +14,7 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
                                        the decoder's own 4:2:0 planes, Y' as a (1, H, W) image and Cb / Cr as a (2, H / 2, W / 2) image (pixfmt.toPlanes / fromPlanes)
   resampleChroma                       (no counterpart: the reference's pipe is RGB) -> moe_chroma_resample: the chroma planes of a luma-only chain, by the integer
                                        polyphase filter of pixfmt.resampleChroma
+  guidedChroma                         (no counterpart) -> moe_chroma_guided: the same planes by a joint bilateral filter steered by the finished luma (pixfmt.guidedChroma)
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
   fitPixels                            (no counterpart) -> moe_fit_create_px / moe_fit_run: the same filter on an interleaved image (pixfmt.fitPixels)
@@ -957,6 +958,31 @@ def resampleChroma(srcFmt, dstFmt, w, h, scale, method, loc='center'):
         cur = torch.cuda.current_stream(raw_dev.device)
         _lib.check(_lib.lib().moe_chroma_resample(raw_dev.data_ptr() + at_in, Ds, ch, cw, out.data_ptr() + at_out, Dd, scale, taps, *tabs,
                                                   raw_dev.device.index or 0, cur.cuda_stream))
+        raw_dev.record_stream(cur)
+        return out
+    return f
+
+
+def guidedChroma(srcFmt, dstFmt, w, h, scale, loc='center'):
+    """The chroma planes of a luma-only chain steered by the finished luma (moe_chroma_guided; the definition: pixfmt.guidedChroma): f(raw_dev, out) reads the Cb, Cr
+    and Y' planes of the planar 4:2:0 frame of w x h in raw_dev (a flat uint8 device tensor of pixfmt.frameBytes(srcFmt, w, h)) and the Y' plane of the frame of
+    w * scale x h * scale in out (flat uint8, pixfmt.frameBytes(dstFmt, w * scale, h * scale)) as the chain wrote it, and writes out's chroma planes; out's Y plane is
+    not touched.  The tables are pixfmt.guidedTable's and guidedRange's: `loc` sites the horizontal axis, the vertical one is always 'center'."""
+    (_, _), (ch, cw) = pixfmt.planeShapes(srcFmt, w, h)
+    if dstFmt not in pixfmt.FORMATS:
+        raise ValueError('pixFmt "{}" is not supported ({})'.format(dstFmt, ', '.join(pixfmt.FORMATS)))
+    (ox, cx), (oy, cy) = pixfmt.guidedTable(scale, loc), pixfmt.guidedTable(scale, 'center')
+    tabs = ((ctypes.c_uint8 * (scale * 4))(*sum(cx, [])), (ctypes.c_int8 * scale)(*ox), (ctypes.c_uint8 * (scale * 4))(*sum(cy, [])), (ctypes.c_int8 * scale)(*oy),
+            (ctypes.c_uint8 * 64)(*pixfmt.guidedRange()))
+    n_in, n_out = pixfmt.frameBytes(srcFmt, w, h), pixfmt.frameBytes(dstFmt, w * scale, h * scale)
+    at_in, at_out = pixfmt.planeOffsets(srcFmt, w, h)[1], pixfmt.planeOffsets(dstFmt, w * scale, h * scale)[1]
+    Ds, Dd = pixfmt.FORMATS[srcFmt], pixfmt.FORMATS[dstFmt]
+
+    def f(raw_dev, out):
+        _flatPair('guidedChroma', 'frames', raw_dev, n_in, out, n_out)
+        cur = torch.cuda.current_stream(raw_dev.device)
+        _lib.check(_lib.lib().moe_chroma_guided(raw_dev.data_ptr() + at_in, raw_dev.data_ptr(), Ds, ch, cw, out.data_ptr() + at_out, out.data_ptr(), Dd, scale,
+                                                _lib.CHROMA_LOCS[loc], *tabs, raw_dev.device.index or 0, cur.cuda_stream))
         raw_dev.record_stream(cur)
         return out
     return f

@@ -23,6 +23,9 @@ With 'chroma': 'nearest' | 'bilinear' | 'bicubic' on such a source step the chai
 by a fixed integer resampling filter (pixfmt.resampleChroma, moe_chroma_resample); `genFrameStream(.., views=True)` hands the finished frames out as read-only views of
 the ring's pinned buffers instead of copies.
 
+With 'chroma': 'guided' there the chain is luma-only as well, and Cb / Cr are written by a joint bilateral filter steered by the Y' the chain has just written into the
+frame (pixfmt.guidedChroma, moe_chroma_guided).
+
 With {'op': 'output', 'width': W, 'height': H, 'fit': 'bicubic'} on such a chain both builders deliver W x H frames: the planes the chain gives are brought to the size
 asked for by a rational integer polyphase filter that antialiases where it shrinks (pixfmt.fitPlanes, moe_fit_create / moe_fit_run).
 
@@ -44,7 +47,7 @@ from functools import reduce
 
 from . import _lib, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, lumaChroma, lumaKeys,
+from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, guidedChroma, lumaChroma, lumaKeys,
                            lumaMerge, lumaSplit, mergeAlpha, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -363,13 +366,17 @@ def _flatBytes(t):
     return t.view(torch.uint8).reshape(-1)
 
 
+GUIDED = 'guided'          # the source step's 'chroma' value that names the luma-guided filter
+
+
 def _planeChroma(steps):
     """(method, loc) of a luma-only chain -- the source step's 'chroma' is 'nearest', 'bilinear' or 'bicubic': the net runs on Y' alone and Cb / Cr are resampled by
-    pixfmt.resampleChroma -- or None for 'chroma': 'net' (the default: Cb / Cr go through the net as a second image).  ValueError for an unknown value of either key,
-    'chromaLoc' beside 'net' (the net path has no siting to choose) and a chain whose total scale exceeds the filter's 16."""
+    pixfmt.resampleChroma; or 'guided': by pixfmt.guidedChroma, steered by the Y' the chain has written -- or None for 'chroma': 'net' (the default: Cb / Cr go
+    through the net as a second image).  ValueError for an unknown value of either key, 'chromaLoc' beside 'net' (the net path has no siting to choose), a chain
+    whose total scale exceeds the filter's 16 and, for 'guided', a chain of total scale 1 and a size on the output step."""
     method, loc = steps[0].get('chroma', 'net'), steps[0].get('chromaLoc')
-    if method != 'net' and method not in pixfmt.CHROMA_METHODS:
-        raise ValueError('buffer: chroma "{}" is not supported (net, {})'.format(method, ', '.join(pixfmt.CHROMA_METHODS)))
+    if method not in ('net', GUIDED) and method not in pixfmt.CHROMA_METHODS:
+        raise ValueError('buffer: chroma "{}" is not supported (net, {}, {})'.format(method, ', '.join(pixfmt.CHROMA_METHODS), GUIDED))
     if loc is not None and loc not in pixfmt.CHROMA_LOCS:
         raise ValueError('buffer: chromaLoc "{}" is not supported ({})'.format(loc, ', '.join(pixfmt.CHROMA_LOCS)))
     if method == 'net':
@@ -382,7 +389,21 @@ def _planeChroma(steps):
             scale *= int(s.get('scale', 1))
     if scale > 16:
         raise ValueError('buffer: chroma "{}" resamples by 16 at most, the chain scales by {}'.format(method, scale))
+    if method == GUIDED:
+        if scale == 1:
+            raise ValueError('buffer: chroma "guided" needs a chain that enlarges the frame (an SR step): at scale 1 the filter would blur planes that need no resampling')
+        for s in steps[1:]:
+            if s.get('op') == 'output' and any(k in s for k in FIT_KEYS):
+                raise ValueError("buffer: chroma \"guided\" does not go with '{}' on the output step: the fitted Y' does not exist when the chroma planes are "
+                                 'written'.format(next(k for k in FIT_KEYS if k in s)))
     return method, loc or 'center'
+
+
+def _chromaPass(chroma, src, dst, width, height, scale):
+    """f(raw, out) that writes the chroma planes of a luma-only chain's frame: moe_chroma_resample, or for 'guided' moe_chroma_guided, which also reads the Y' plane
+    the chain has written into `out` -- it runs behind the chain's last edge, on the same stream."""
+    method, loc = chroma
+    return guidedChroma(src, dst, width, height, scale, loc) if method == GUIDED else resampleChroma(src, dst, width, height, scale, method, loc)
 
 
 def _planeChain(steps, fuse, rsteps=None):
@@ -465,9 +486,9 @@ def _genProcessPlanes(steps, fmts, dither=None):
         cb = pixfmt.planeOffsets(dst, w, h)[1]
         out = torch.empty((pixfmt.frameBytes(dst, w, h),), dtype=torch.uint8, device=dev)
         quantise(reduce(apply, funcs, y), out[:cb])
-        if chroma:          # luma-only: Cb / Cr from the raw frame's codes, by the integer filter
+        if chroma:          # luma-only: Cb / Cr from the raw frame's codes, by the integer filter ('guided': and from the Y' plane just written)
             if (width, height) not in resamplers:
-                resamplers[(width, height)] = resampleChroma(src, dst, width, height, scale, *chroma)
+                resamplers[(width, height)] = _chromaPass(chroma, src, dst, width, height, scale)
             resamplers[(width, height)](rawDev, out)
         else:
             quantise(reduce(apply, funcs, c), out[cb:])
@@ -973,8 +994,8 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
     def edge(y, c, out, reuseY=None, reuseC=None):
         into(y, out[:cb], reuseY)
         into(c, out[cb:], reuseC)
-    if chroma:          # luma-only: the Y edge as above, then one moe_chroma_resample from the raw frame's chroma codes into the frame's Cb / Cr planes, on the compute stream
-        resample = resampleChroma(src, dst, int(width), int(height), scale, *chroma)
+    if chroma:          # luma-only: the Y edge as above, then one moe_chroma_resample (moe_chroma_guided) from the raw frame's chroma codes into the frame's Cb / Cr planes, on the compute stream
+        resample = _chromaPass(chroma, src, dst, int(width), int(height), scale)
 
         def edge(y, raw, out, reuseY=None):
             into(y, out[:cb], reuseY)
@@ -1085,7 +1106,11 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     samples of the chain's own size into one more device buffer per slot, and one moe_fit_run on the interleaved frame writes the slot's frame -- pixfmt.fitPixels of
     those samples, byte for byte; `edge` reads 'crop+fit', 'filter+fit' or 'quantise+fit'.  reuse and views work unchanged.  Refused by key before a model is loaded:
     such a step anywhere else, 'method' beside 'fit', an unknown 'fit', an axis without a size, 'dither' or 'pixFmt' on the output step, a ratio beyond 4 down or 16 up
-    of the chain's own size -- known from the step dicts alone (_chainSize: the SR steps' scales, the resize steps' sizes) -- (DESIGN.md section 19)."""
+    of the chain's own size -- known from the step dicts alone (_chainSize: the SR steps' scales, the resize steps' sizes) -- (DESIGN.md section 19).
+    With 'chroma': 'guided' on a planar source step (and 'chromaLoc') the chain is luma-only as with 'bicubic', and the frame's Cb / Cr planes are written by one
+    moe_chroma_guided behind the Y edge, on the compute stream: a joint bilateral filter over the source's chroma codes, steered by the source's Y' and by the Y' plane
+    the edge has just written into the slot's frame (pixfmt.guidedChroma: integers, byte for byte).  It runs every frame; reuse, views and every ring depth work
+    unchanged.  Refused before a model is loaded: a chain of total scale 1 and 'width' / 'height' / 'fit' on the output step."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
