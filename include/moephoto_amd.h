@@ -383,6 +383,21 @@ int moe_chroma_resample(const void* src, int src_depth, int h, int w, void* dst,
 int moe_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h, int w, void* dst_c, const void* dst_y, int dst_depth, int scale, int loc,
                       const uint8_t* cx, const int8_t* ox, const uint8_t* cy, const int8_t* oy, const uint8_t* range64, int device, void* stream);
 
+/* RGB frames from a chain on 4:2:0 planes: the integer Y'CbCr -> RGB edge -- the definition is moephoto_amd/pixfmt.py (toRGB, rgbCoefficients) and the device matches it
+ * byte for byte.  src = a planar frame of H x W at `depth` (uint8 at depth 8, little-endian uint16 at 10, 12, 16; the Y plane, then Cb, then Cr; high bits are not masked);
+ * dst = H x W x 3 interleaved samples, uint8 for bits = 8, uint16 for bits = 16, red first for MOE_ORDER_RGB, blue first for MOE_ORDER_BGR.  Per pixel the chroma
+ * planes are brought to luma size by moe_chroma_resample's filter at scale 2 (cx / ox and cy / oy: HOST tables of 2 x taps 14-bit coefficients and 2 offsets per axis,
+ * pixfmt.chromaTable; the sample clamped to [0, 2^depth - 1]) -- the upsampled planes never exist in memory -- then y = Y - (16 << (depth - 8)), u = Cb' - (128 << (depth - 8)),
+ * v = Cr' - (128 << (depth - 8)) and, with coef = (cY, cRV, cGU, cGV, cBU) = pixfmt.rgbCoefficients(matrix, depth, bits), 20 fractional bits, in int64:
+ *     R = (cY y + cRV v + r) >> 20      G = (cY y + cGU u + cGV v + r) >> 20      B = (cY y + cBU u + r) >> 20      each clamped to [0, 2^bits - 1]
+ * r = 1 << 19, or with MOE_Q_ORDERED in `bits` T << 13 (T of the pixel's coordinates, shared by its three samples: moephoto_amd/quant.py); MOE_Q_ROUND is accepted and
+ * changes nothing.  One launch.  Refused (MOE_EINVAL, before any device call): a NULL pointer, a depth outside {8, 10, 12, 16}, bits outside {8, 16}, MOE_Q_UNIT or any
+ * other high bit, an odd H or W, one below 2, H * W * 3 beyond int, an unknown matrix or order, taps outside {1, 2, 4}, a misaligned pointer, a coefficient row that
+ * does not sum to 2^14 or whose sum of magnitudes exceeds 32767, an offset outside [-2, 1], cY outside [1, 2^30] or another constant whose magnitude exceeds 2^30
+ * (the three products and r then stay below 2^49 for any uint16 code and the shifted sum fits an int), a dst that overlaps src.  Asynchronous on `stream`. */
+int moe_planes_to_rgb(const void* src, int depth, int H, int W, void* dst, int bits, int matrix, int order, int taps,
+                      const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, const int32_t* coef, int device, void* stream);
+
 /* ---- luma-only steps on RGB images ------------------------------------------------------------------------
  * The reference sends every plane of a colour image through the net (planes are the batch: python/runSR.py:37-40); none of these entry points has a counterpart in
  * it.  None of the SR / DN nets convolves planes jointly, so a step may run on Y' alone while Cb / Cr go to the output's size through moe_resize: a third of the net's

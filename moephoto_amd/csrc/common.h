@@ -533,6 +533,12 @@ void launch_chroma_resample(const void* src, int src_depth, int h, int w, void* 
 // chroma_guided.hip: moe_chroma_guided's joint bilateral filter (moephoto_amd/pixfmt.py: guidedTable / guidedChroma); the HOST tables as the entry point took and checked them
 void launch_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h, int w, void* dst_c, const void* dst_y, int dst_depth, int scale, int left,
                           const unsigned char* cx, const signed char* ox, const unsigned char* cy, const signed char* oy, const unsigned char* range64, hipStream_t s);
+// planes_rgb.hip: moe_planes_to_rgb's integer Y'CbCr -> RGB edge (moephoto_amd/pixfmt.py: rgbCoefficients / toRGB).  coef = (cY, cRV, cGU, cGV, cBU) with RGB_FRAC
+// fractional bits, yoff / coff the codes of black and of neutral chroma at the source's depth, cmax = 2^depth - 1 (the chroma filter's clamp), top = 2^bits - 1
+constexpr int RGB_FRAC = 20;
+struct PlanesRgb { int coef[5]; int yoff, coff, cmax, top, rgb, ordered; };
+// src: a planar 4:2:0 frame of H x W at `depth` (u8 for 8, else u16); dst: H x W x 3 interleaved samples (u8 for bits 8, else u16); tx / ty: the x2 phase tables
+void launch_planes_rgb(const void* src, int depth, int H, int W, void* dst, int bits, int taps, const ChromaTab& tx, const ChromaTab& ty, const PlanesRgb& k, hipStream_t s);
 // fit.hip: one axis of moe_fit_run's rational polyphase filter, in DEVICE memory: output index o reads `taps` source samples from off[o] on with the 14-bit coefficients
 // coef[o * FIT_TAPS + 0 .. taps) (rows of FIT_TAPS, 32 bytes, the base 16-byte aligned; moephoto_amd/pixfmt.py: fitTable).  A workgroup's output tile is FIT_TW x th.
 constexpr int FIT_TW = 128, FIT_TAPS = 16;

@@ -1,5 +1,5 @@
 // polyphase.cpp -- the entry points of the two integer polyphase resamplers of planar codes: moe_chroma_resample (chroma.hip: the chroma planes of a luma-only
-// chain, integer scales; moe_chroma_guided, chroma_guided.hip: the same planes steered by the finished luma) and moe_fit_create / moe_fit_create_px / _run / _info / _destroy (fit.hip, fit_px.hip: planes / an interleaved image brought to a fitted size).  What they check of the caller's tables is the
+// chain, integer scales; moe_chroma_guided, chroma_guided.hip: the same planes steered by the finished luma; moe_planes_to_rgb, planes_rgb.hip: a planar frame's RGB form) and moe_fit_create / moe_fit_create_px / _run / _info / _destroy (fit.hip, fit_px.hip: planes / an interleaved image brought to a fitted size).  What they check of the caller's tables is the
 // contract the kernels rely on (polyphase.h): the kernels check nothing.
 #include "net.h"
 
@@ -83,6 +83,51 @@ int moe_chroma_guided(const void* src_c, const void* src_y, int src_depth, int h
     HIP_TRY(hipSetDevice(device));
     launch_chroma_guided(src_c, src_y, src_depth, h, w, dst_c, dst_y, dst_depth, scale, loc == MOE_CHROMA_LEFT, cx, ox, cy, oy, range64, (hipStream_t)stream);
     return launched("resize_kernel_guided");
+}
+
+// RGB frames from a planar 4:2:0 frame (planes_rgb.hip): the x2 chroma tables as moe_chroma_resample takes them, and the matrix constants whose magnitudes the
+// kernel's int64 sums and its 32-bit clamp rest on.
+int moe_planes_to_rgb(const void* src, int depth, int H, int W, void* dst, int bits, int matrix, int order, int taps,
+                      const int16_t* cx, const int8_t* ox, const int16_t* cy, const int8_t* oy, const int32_t* coef, int device, void* stream)
+{
+    if (!src || !dst || !cx || !ox || !cy || !oy || !coef) return fail(MOE_EINVAL, "moe_planes_to_rgb: NULL argument");
+    if (!plane_depth(depth)) return fail(MOE_EINVAL, "moe_planes_to_rgb: depth %d (8, 10, 12 or 16)", depth);
+    const int flags = bits & ~0xff, low = bits & 0xff;
+    if (flags & ~(MOE_Q_ROUND | MOE_Q_ORDERED | MOE_Q_UNIT)) return fail(MOE_EINVAL, "moe_planes_to_rgb: bits 0x%x carries unknown flags (MOE_Q_ROUND, MOE_Q_ORDERED)", bits);
+    if (flags & MOE_Q_UNIT) return fail(MOE_EINVAL, "moe_planes_to_rgb: MOE_Q_UNIT does not apply (the samples are quantised in integers; 8 bits always take the unit scale)");
+    if ((flags & MOE_Q_ROUND) && (flags & MOE_Q_ORDERED)) return fail(MOE_EINVAL, "moe_planes_to_rgb: MOE_Q_ROUND and MOE_Q_ORDERED are both set (one mode at most)");
+    if (low != 8 && low != 16) return fail(MOE_EINVAL, "moe_planes_to_rgb: bits %d (8 or 16)", low);
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(MOE_EINVAL, "moe_planes_to_rgb: size %d x %d (an even width and height of 2 at least)", W, H);
+    if (3ll * H * W > 0x7fffffffll) return fail(MOE_EINVAL, "moe_planes_to_rgb: the %d x %d x 3 samples do not fit an int", W, H);
+    if (matrix != MOE_YUV_BT709 && matrix != MOE_YUV_BT601 && matrix != MOE_YUV_BT2020NC) return fail(MOE_EINVAL, "moe_planes_to_rgb: matrix %d (MOE_YUV_BT709, _BT601 or _BT2020NC)", matrix);
+    if (order != MOE_ORDER_BGR && order != MOE_ORDER_RGB) return fail(MOE_EINVAL, "moe_planes_to_rgb: order %d (MOE_ORDER_BGR or MOE_ORDER_RGB)", order);
+    if (taps != 1 && taps != 2 && taps != 4) return fail(MOE_EINVAL, "moe_planes_to_rgb: %d taps (1, 2 or 4)", taps);
+    if (int rc = poly_aligned_check("moe_planes_to_rgb", src, depth, dst, low)) return rc;
+    ChromaTab t[2] = {};
+    const int16_t* const rows[2] = {cx, cy};
+    const int8_t* const off[2] = {ox, oy};
+    for (int a = 0; a < 2; ++a)
+        for (int p = 0; p < 2; ++p) {
+            if (int rc = poly_row_check("moe_planes_to_rgb", axis_name(a), "phase", p, rows[a] + p * taps, taps)) return rc;
+            if (off[a][p] < -2 || off[a][p] > 1) return fail(MOE_EINVAL, "moe_planes_to_rgb: %s offset %d of phase %d (-2 to 1)", axis_name(a), (int)off[a][p], p);
+            std::copy(rows[a] + p * taps, rows[a] + (p + 1) * taps, t[a].coef[p]);
+            t[a].off[p] = off[a][p];
+        }
+    // |y|, |u|, |v| < 2^16 and constants of 2^30 at most: three products and the rounding term stay below 2^49, and the sum shifted by RGB_FRAC fits an int
+    static const char* const names[5] = {"cY", "cRV", "cGU", "cGV", "cBU"};
+    for (int i = 0; i < 5; ++i)
+        if (coef[i] > (1 << 30) || coef[i] < (i ? -(1 << 30) : 1))
+            return fail(MOE_EINVAL, "moe_planes_to_rgb: matrix constant %s = %d (%s, with %d fractional bits)", names[i], (int)coef[i], i ? "a magnitude of 2^30 at most" : "1 to 2^30", RGB_FRAC);
+    const long long px = (long long)H * W;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (uintptr_t)(px + px / 2) * (depth == 8 ? 1 : 2), d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(3 * px) * (low == 8 ? 1 : 2);
+    if (d0 < s1 && s0 < d1) return fail(MOE_EINVAL, "moe_planes_to_rgb: dst overlaps src (a workgroup reads chroma samples that belong to its neighbours' pixels)");
+    PlanesRgb k = {};
+    std::copy(coef, coef + 5, k.coef);
+    k.yoff = 16 << (depth - 8); k.coff = 128 << (depth - 8); k.cmax = (1 << depth) - 1; k.top = (1 << low) - 1;
+    k.rgb = order == MOE_ORDER_RGB; k.ordered = (flags & MOE_Q_ORDERED) != 0;
+    HIP_TRY(hipSetDevice(device));
+    launch_planes_rgb(src, depth, H, W, dst, low, taps, t[0], t[1], k, (hipStream_t)stream);
+    return launched("to_output_rgb420_kernel");
 }
 
 // ---- fitted sizes (fit.hip) ------------------------------------------------------------------------------

@@ -15,6 +15,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   resampleChroma                       (no counterpart: the reference's pipe is RGB) -> moe_chroma_resample: the chroma planes of a luma-only chain, by the integer
                                        polyphase filter of pixfmt.resampleChroma
   guidedChroma                         (no counterpart) -> moe_chroma_guided: the same planes by a joint bilateral filter steered by the finished luma (pixfmt.guidedChroma)
+  planesToRGB                          (python/video.py:230 asks for bgr48le on the encoder's pipe) -> moe_planes_to_rgb: the interleaved RGB frame of a chain on 4:2:0
+                                       planes -- chroma x2 by the same integer filter, then the standard's inverse matrix in fixed point (pixfmt.toRGB)
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
   fitPixels                            (no counterpart) -> moe_fit_create_px / moe_fit_run: the same filter on an interleaved image (pixfmt.fitPixels)
@@ -984,6 +986,34 @@ def guidedChroma(srcFmt, dstFmt, w, h, scale, loc='center'):
         _lib.check(_lib.lib().moe_chroma_guided(raw_dev.data_ptr() + at_in, raw_dev.data_ptr(), Ds, ch, cw, out.data_ptr() + at_out, out.data_ptr(), Dd, scale,
                                                 _lib.CHROMA_LOCS[loc], *tabs, raw_dev.device.index or 0, cur.cuda_stream))
         raw_dev.record_stream(cur)
+        return out
+    return f
+
+
+def planesToRGB(srcFmt, w, h, rgbFmt, matrix='bt709', method='bicubic', loc='center', dither=None):
+    """RGB frames from a chain on 4:2:0 planes (moe_planes_to_rgb; the definition: pixfmt.toRGB): f(planar_dev, out) reads the planar 4:2:0 frame of w x h in
+    planar_dev (a flat uint8 device tensor of pixfmt.frameBytes(srcFmt, w, h)) and writes the interleaved h x w x 3 frame at rgbFmt ('bgr24', 'rgb24', 'bgr48le',
+    'rgb48le') into out (flat uint8, 3 w h bytes or twice that), in one launch; the chroma planes at luma size never exist.  The tables are pixfmt.chromaTable's at
+    scale 2 (`loc` sites the horizontal axis, the vertical one is always 'center'), the constants pixfmt.rgbCoefficients'; dither: None / 'round' (the same bytes) or
+    'ordered'."""
+    pixfmt.planeShapes(srcFmt, w, h)
+    if rgbFmt not in pixfmt.RGB_FORMATS:
+        raise ValueError('pixFmt "{}" is not an RGB format ({})'.format(rgbFmt, ', '.join(pixfmt.RGB_FORMATS)))
+    D, (bits, order) = pixfmt.FORMATS[srcFmt], pixfmt.RGB_FORMATS[rgbFmt]
+    ids = pixfmt.check(srcFmt, matrix, order)
+    (ox, cx), (oy, cy) = pixfmt.chromaTable(method, 2, loc), pixfmt.chromaTable(method, 2, 'center')
+    taps = pixfmt.CHROMA_METHODS[method]
+    tabs = ((ctypes.c_int16 * (2 * taps))(*sum(cx, [])), (ctypes.c_int8 * 2)(*ox), (ctypes.c_int16 * (2 * taps))(*sum(cy, [])), (ctypes.c_int8 * 2)(*oy),
+            (ctypes.c_int32 * 5)(*pixfmt.rgbCoefficients(matrix, D, bits)))
+    qf = ditherFlags('planesToRGB', dither, bits, 'yuv')          # (an integer edge: no unit flag, as the Y'CbCr edge)
+    n_in, n_out = pixfmt.frameBytes(srcFmt, w, h), 3 * int(w) * int(h) * (bits // 8)
+
+    def f(planar_dev, out):
+        _flatPair('planesToRGB', 'frames', planar_dev, n_in, out, n_out)
+        cur = torch.cuda.current_stream(planar_dev.device)
+        _lib.check(_lib.lib().moe_planes_to_rgb(planar_dev.data_ptr(), D, int(h), int(w), out.data_ptr(), bits | qf, ids[1], ids[2], taps, *tabs,
+                                                planar_dev.device.index or 0, cur.cuda_stream))
+        planar_dev.record_stream(cur)
         return out
     return f
 

@@ -1,6 +1,7 @@
 """The encoder's planar Y'CbCr 4:2:0 frames: the definition the device kernels (stitch_yuv_kernel, to_output_yuv_kernel) are held to, in numpy.  (Below it, the
 definition of chains that run on such planes as they come from the decoder, with no conversion at all: planeShapes, toPlanes, fromPlanes; and below that the
-integer resampling filter that writes the chroma planes of a luma-only chain: chromaTable, resampleChroma; at the end its luma-guided form: guidedTable, guidedChroma.)
+integer resampling filter that writes the chroma planes of a luma-only chain: chromaTable, resampleChroma; then its luma-guided form: guidedTable, guidedChroma; at the
+end the integer Y'CbCr -> RGB edge of a planar chain that hands back bgr24 / rgb24 / bgr48le / rgb48le frames: RGB_FORMATS, rgbCoefficients, toRGB.)
 
 The reference fixes the pipe's pixel format to bgr24 / bgr48le (python/video.py:24,219,230) and leaves the conversion to the encoder's side; here the last pass over a
 frame can write the encoder's own planes.  This module is the written specification and the comparator of the tests; it is on no hot path.
@@ -430,3 +431,69 @@ def guidedChroma(C, Ys, Yo, srcFmt, dstFmt, scale, loc='center'):
     s = (num + den // 2) // den
     s = s << (Dd - Ds) if Dd >= Ds else s >> (Ds - Dd)
     return s.astype(np.uint8 if Dd == 8 else np.dtype('<u2'))
+
+
+# ---- RGB frames from a chain on 4:2:0 planes: the integer Y'CbCr -> RGB edge ---------------------------------------------------------------------
+# A chain on the decoder's planes whose output step names an RGB pixFmt ({'op': 'output', 'pixFmt': 'bgr48le'}) hands back interleaved RGB samples -- what the device
+# kernel (to_output_rgb420_kernel, moe_planes_to_rgb) is held to, byte for byte.  Integers only; the library builds no table and no constant of its own.
+#
+#     chroma     C' = resampleChroma(C, fmt, fmt, 2, method, loc): the filter, the table and the clamp to [0, 2^D - 1] defined above, at scale 2 (`loc` sites the
+#                horizontal axis only).
+#     offsets    y = Y - (16 << (D - 8)),  u = Cb' - (128 << (D - 8)),  v = Cr' - (128 << (D - 8)).  Y codes as they are: high bits are not masked.
+#     matrix     the standard's inverse, (Kr, Kb) = LUMA[matrix], Kg = 1 - Kr - Kb, in units of 2^(D - 8):
+#                    E_R = y / 219 + 2 (1 - Kr) v / 224      E_B = y / 219 + 2 (1 - Kb) u / 224      E_G = y / 219 - (Kr 2 (1 - Kr) v + Kb 2 (1 - Kb) u) / (Kg 224)
+#                times the sample scale S: 2^16 for 16-bit samples (the inverse of how fromSamples16 reads them), 255 for 8-bit ones (the inverse of the reader's / 255,
+#                quant.py's `unit`).  As constants with F = RGB_FRAC = 20 fractional bits, each round(x 2^F) of an exact fraction (rgbCoefficients):
+#                    cY = S / (219 2^(D-8))    cRV = S 2 (1 - Kr) / (224 2^(D-8))    cBU = S 2 (1 - Kb) / (224 2^(D-8))
+#                    cGU = -S Kb 2 (1 - Kb) / (Kg 224 2^(D-8))                       cGV = -S Kr 2 (1 - Kr) / (Kg 224 2^(D-8))
+#     sample     int64:  R = (cY y + cRV v + r) >> F,  G = (cY y + cGU u + cGV v + r) >> F,  B = (cY y + cBU u + r) >> F  (>> an arithmetic shift), clamped to
+#                [0, 2^bits - 1].  r = 1 << (F - 1): round to nearest; dither 'ordered': r = T << (F - 7) with quant.threshold's T at the pixel's coordinates, one
+#                threshold for the three channels of a pixel.  None / 'none' / 'round' give the same bytes (the stance of quant.yuvFromSamples16).
+# F = 20: the largest constant (cBU of bt2020nc at D = 8, S = 2^16: 550.4) stays below 2^30, so every constant is an int32 and, with |y|, |u|, |v| < 2^16, the three
+# products and r stay below 2^49.  A constant is off by 2^-(F+1) at most, so before the clamp a sample differs from the exact S E by at most
+# 1/2 + (|y| + |u| + |v|) 2^-(F+1) <= 1/2 + 3 * 65535 * 2^-21 < 0.594.
+RGB_FORMATS = {'bgr24': (8, 'bgr'), 'rgb24': (8, 'rgb'), 'bgr48le': (16, 'bgr'), 'rgb48le': (16, 'rgb')}      # pix_fmt -> (bits, order)
+RGB_FRAC = 20
+
+
+def rgbCoefficients(matrix, D, bits):
+    """(cY, cRV, cGU, cGV, cBU) of a matrix for sources at depth D and samples of `bits` bits, as Python ints with RGB_FRAC fractional bits."""
+    from fractions import Fraction as Fr
+    from math import floor
+    if matrix not in MATRICES:
+        raise ValueError('matrix "{}" is not supported ({})'.format(matrix, ', '.join(MATRICES)))
+    if D not in FORMATS.values():
+        raise ValueError('rgbCoefficients: depth must be one of {}, got {!r}'.format(sorted(FORMATS.values()), D))
+    if bits not in (8, 16):
+        raise ValueError('rgbCoefficients: bits must be 8 or 16, got {!r}'.format(bits))
+    kr, kb = (Fr(str(k)) for k in LUMA[matrix])          # (the decimal constants of the standards, exactly)
+    kg = 1 - kr - kb
+    S = Fr(255 if bits == 8 else 1 << 16, 1 << (D - 8))
+    q = lambda x: floor(x * (1 << RGB_FRAC) + Fr(1, 2))
+    er, eb = 2 * (1 - kr), 2 * (1 - kb)
+    return q(S / 219), q(S * er / 224), -q(S * kb * eb / (kg * 224)), -q(S * kr * er / (kg * 224)), q(S * eb / 224)
+
+
+def toRGB(frame_bytes, fmt, w, h, rgbFmt, matrix='bt709', method='bicubic', loc='center', dither=None):
+    """The bytes of a planar frame of w x h at fmt -> the bytes of the interleaved h x w x 3 frame at rgbFmt (the definition above)."""
+    from . import quant
+    if rgbFmt not in RGB_FORMATS:
+        raise ValueError('pixFmt "{}" is not an RGB format ({})'.format(rgbFmt, ', '.join(RGB_FORMATS)))
+    (yh, yw), (ch, cw) = planeShapes(fmt, w, h)
+    D = FORMATS[fmt]
+    bits, order = RGB_FORMATS[rgbFmt]
+    cY, cRV, cGU, cGV, cBU = rgbCoefficients(matrix, D, bits)
+    mode = quant._mode(dither)
+    end = frameBytes(fmt, w, h)
+    if len(frame_bytes) != end:
+        raise ValueError('toRGB: a {} frame of {} x {} is {} bytes, got {}'.format(fmt, w, h, end, len(frame_bytes)))
+    codes = np.frombuffer(frame_bytes, np.uint8 if D == 8 else np.dtype('<u2'))
+    C = resampleChroma(codes[yh * yw:].reshape(2, ch, cw), fmt, fmt, 2, method, loc).astype(np.int64)
+    y = codes[:yh * yw].reshape(yh, yw).astype(np.int64) - (16 << (D - 8))
+    u, v = C[0] - (128 << (D - 8)), C[1] - (128 << (D - 8))
+    r = quant.threshold('round' if mode == 'none' else mode, yh, yw) << (RGB_FRAC - 7)
+    base = cY * y + r
+    top = (1 << bits) - 1
+    R, G, B = (np.clip(a >> RGB_FRAC, 0, top) for a in (base + cRV * v, base + cGU * u + cGV * v, base + cBU * u))
+    out = np.stack((R, G, B) if order == 'rgb' else (B, G, R), axis=2)
+    return out.astype(np.uint8 if bits == 8 else np.dtype('<u2')).tobytes()

@@ -40,6 +40,11 @@ definition; the MOE_Q_* flags of include/moephoto_amd.h). 
 With {'op': 'resize', 'width': W, 'height': H, 'fit': 'bicubic'} as the last compute step of a chain on an RGB source both builders deliver W x H frames through the
 integer filter instead of moe_resize on a float canvas: the chain in front of the step writes its 16-bit samples as it would without the step, and one
 moe_fit_run on the interleaved frame (pixfmt.fitPixels, moe_fit_create_px) brings them to the size and the depth asked for.
+
+With {'op': 'output', 'pixFmt': 'bgr24' | 'rgb24' | 'bgr48le' | 'rgb48le'} behind a planar source both builders deliver interleaved RGB frames: the chain writes its
+frame as yuv420p16le through the edge it always used, into one intermediate on the compute queue, and one moe_planes_to_rgb -- the chroma planes x2 by the integer
+filter, the standard's inverse matrix in fixed point -- writes the frame handed out (pixfmt.toRGB is the definition).  Beside such a pixFmt the
+step takes 'matrix', 'chromaUp' (the filter of the final x2), 'chromaLoc' (how the frame's chroma is sited: H.264 / HEVC material is 'left') and 'dither'.
 """
 import math
 import time
@@ -48,7 +53,7 @@ from functools import reduce
 from . import _lib, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
 from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, guidedChroma, lumaChroma, lumaKeys,
-                           lumaMerge, lumaSplit, mergeAlpha, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
+                           lumaMerge, lumaSplit, mergeAlpha, planesToRGB, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -221,7 +226,9 @@ def _pixelFitLast(fit, fused, bitDepth):
 def _planeFormats(steps, width=None, height=None):
     """(source pixFmt, output pixFmt) of a step list whose source is planar, or None for every other list.  Everything such a chain refuses is refused here, as a
     ValueError before any model is loaded: an unknown format, a resize step, matrix / order on the output step (there is no conversion they could steer), an odd size,
-    what _planeChroma refuses of the source step's 'chroma' / 'chromaLoc' keys and what _planeFit refuses of the output step's 'width' / 'height' / 'fit'."""
+    what _planeChroma refuses of the source step's 'chroma' / 'chromaLoc' keys and what _planeFit refuses of the output step's 'width' / 'height' / 'fit'.
+    The output pixFmt may be one of pixfmt.RGB_FORMATS: 'matrix' then steers that conversion, 'order' stays refused (the format's name carries
+    it), and 'chromaUp' / 'chromaLoc' on the output step are refused without such a pixFmt, as is an unknown value of either (_planeRGB)."""
     if not steps or steps[0].get('op') != 'buffer' or steps[0].get('pixFmt') is None:
         return None
     src = dst = steps[0]['pixFmt']
@@ -231,17 +238,52 @@ def _planeFormats(steps, width=None, height=None):
         if s.get('op') == 'resize':
             raise ValueError('a chain on {} planes cannot hold a resize step (chroma would need its own size)'.format(src))
         if s.get('op') == 'output':
-            if 'matrix' in s or 'order' in s:
+            rgb = s.get('pixFmt') in pixfmt.RGB_FORMATS
+            if 'order' in s or ('matrix' in s and not rgb):          # (an RGB pixFmt carries its order in its name)
                 raise ValueError("output: 'matrix' / 'order' do not apply to a chain on {} planes: no colour conversion takes place".format(src))
+            for k in RGB_KEYS:
+                if k in s and not rgb:
+                    raise ValueError("output: '{}' applies beside an RGB 'pixFmt' only ({}): it steers the conversion of the chain's planes to RGB".format(k, ', '.join(pixfmt.RGB_FORMATS)))
+            if rgb:
+                _planeRGB(s)
             if s.get('pixFmt') is not None:
                 dst = s['pixFmt']
-                if dst not in pixfmt.FORMATS:
+                if dst not in pixfmt.FORMATS and not rgb:
                     raise ValueError('output: pixFmt "{}" is not supported ({})'.format(dst, ', '.join(pixfmt.FORMATS)))
     if width is not None:
         pixfmt.planeShapes(src, width, height)
     _planeChroma(steps)
     _planeFit(steps, width, height)
     return src, dst
+
+
+# ---- RGB frames from a planar chain: {'op': 'output', 'pixFmt': 'bgr48le'} ----------------------------------------------------------
+RGB_KEYS = ('chromaUp', 'chromaLoc')          # the output step's keys that exist beside an RGB pixFmt only ('matrix' is shared with the RGB -> Y'CbCr edge)
+PLANAR16 = 'yuv420p16le'                      # the chain's own frame in front of the conversion
+
+
+def _planeRGB(s):
+    """(rgbFmt, matrix, method, loc) of an output step whose 'pixFmt' is one of pixfmt.RGB_FORMATS ('bgr24', 'rgb24', 'bgr48le', 'rgb48le') behind a planar source:
+    the chain writes its frame as yuv420p16le exactly as it would for that pixFmt, without 'dither', and one moe_planes_to_rgb turns it into interleaved RGB samples
+    (pixfmt.toRGB is the definition).  'matrix': 'bt709' (the default) | 'bt601' | 'bt2020nc'; 'chromaUp': 'nearest' | 'bilinear' | 'bicubic' (the default), the
+    filter of the final x2 of the chroma planes; 'chromaLoc': 'center' (the default) | 'left', how the frame's chroma is sited horizontally -- H.264 / HEVC material
+    is 'left' (MPEG-2's and their default co-sited columns), JPEG / MPEG-1 'center'.  The step's 'dither' ('round' | 'ordered') then governs the conversion's one
+    rounding.  ValueError naming the key for an unknown value."""
+    matrix, method, loc = s.get('matrix', 'bt709'), s.get('chromaUp', 'bicubic'), s.get('chromaLoc', 'center')
+    if matrix not in pixfmt.MATRICES:
+        raise ValueError("output: 'matrix' \"{}\" is not supported ({})".format(matrix, ', '.join(pixfmt.MATRICES)))
+    if method not in pixfmt.CHROMA_METHODS:
+        raise ValueError("output: 'chromaUp' \"{}\" is not supported ({})".format(method, ', '.join(pixfmt.CHROMA_METHODS)))
+    if loc not in pixfmt.CHROMA_LOCS:
+        raise ValueError("output: 'chromaLoc' \"{}\" is not supported ({})".format(loc, ', '.join(pixfmt.CHROMA_LOCS)))
+    return s['pixFmt'], matrix, method, loc
+
+
+def _planeRGBStep(steps, dst):
+    """_planeRGB of the output step that names `dst`, the format _planeFormats returned, or None where that is a planar format."""
+    if dst not in pixfmt.RGB_FORMATS:
+        return None
+    return _planeRGB([s for s in steps[1:] if s.get('op') == 'output' and s.get('pixFmt') is not None][-1])
 
 
 FIT_KEYS = ('width', 'height', 'fit')
@@ -447,10 +489,21 @@ def _genProcessPlanes(steps, fmts, dither=None):
     import numpy as np
     import torch
     src, dst = fmts
+    rgb, converters = _planeRGBStep(steps, dst), {}
+    if rgb:          # the chain's frame as yuv420p16le without 'dither', then one moe_planes_to_rgb: the key governs that conversion's rounding
+        dst, dither, rgbDither = PLANAR16, None, dither
     funcs, nodes, scale, _ = _planeChain(steps, False)
     quantise = toPlanes(pixfmt.FORMATS[dst], dither)
     chroma, resamplers = _planeChroma(steps), {}
     fit, quantise16, fitters = _planeFit(steps), toPlanes(16), {}
+
+    def finish(out, W, H):
+        """The bytes of the frame of W x H in `out`: the planar frame itself, or its RGB form."""
+        if rgb:
+            if (W, H) not in converters:
+                converters[(W, H)] = planesToRGB(dst, W, H, *rgb, dither=rgbDither)
+            out = converters[(W, H)](out, torch.empty((3 * W * H * (pixfmt.RGB_FORMATS[rgb[0]][0] // 8),), dtype=torch.uint8, device=out.device))
+        return out.cpu().numpy().tobytes()
 
     def runFit(rawDev, y, c, width, height, dev):
         """The frame at the size the output step names: the chain's planes at 16 bits (the existing edge), then pixfmt.fitPlanes' kernel per image."""
@@ -470,7 +523,7 @@ def _genProcessPlanes(steps, fmts, dither=None):
             fitC(rawDev[pixfmt.planeOffsets(src, width, height)[1]:], out[cb:])
         else:
             fitC(quantise16(reduce(apply, funcs, c)), out[cb:])
-        return out.cpu().numpy().tobytes()
+        return finish(out, W, H)
 
     def run(frame):
         raw, height, width = frame
@@ -492,7 +545,7 @@ def _genProcessPlanes(steps, fmts, dither=None):
             resamplers[(width, height)](rawDev, out)
         else:
             quantise(reduce(apply, funcs, c), out[cb:])
-        return out.cpu().numpy().tobytes()
+        return finish(out, w, h)
     return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
 
 
@@ -975,6 +1028,9 @@ class _PlanesBackend(_DeviceBackend):
 
 def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False, dither=None):
     src, dst = fmts
+    rgb = _planeRGBStep(steps, dst)
+    if rgb:          # the chain's frame as yuv420p16le without 'dither', then one moe_planes_to_rgb: the key governs that conversion's rounding
+        dst, dither, rgbDither = PLANAR16, None, dither
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     _checkReuse(reuse)
@@ -1038,6 +1094,18 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
                 into(c, mid[cb16:], reuseC)
                 fitY(mid[:cb16], out[:cbOut])
                 fitC(mid[cb16:], out[cbOut:])
+    if rgb:          # an RGB pixFmt: the edge above writes one intermediate planar frame (compute queue only), then one moe_planes_to_rgb into the slot's frame, every frame
+        import torch
+        fw, fh = fit[:2] if fit else (w, h)
+        toRGB, planarBytes, planarEdge, planar = planesToRGB(dst, fw, fh, *rgb, dither=rgbDither), outBytes, edge, {}
+        edgeName += '+rgb'
+        outBytes = 3 * fw * fh * (pixfmt.RGB_FORMATS[rgb[0]][0] // 8)
+
+        def edge(y, c, out, *reuses):          # (c: the raw frame on a luma-only chain)
+            if 'buf' not in planar:          # allocated once, at the first frame
+                planar['buf'] = torch.empty((planarBytes,), dtype=torch.uint8, device=out.device)
+            planarEdge(y, c, planar['buf'], *reuses)
+            toRGB(planar['buf'], out)
     state = _ReuseState(rsteps, bool(last)) if reuse else None
     backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, outBytes, state, views, bool(chroma))
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
@@ -1110,7 +1178,13 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     With 'chroma': 'guided' on a planar source step (and 'chromaLoc') the chain is luma-only as with 'bicubic', and the frame's Cb / Cr planes are written by one
     moe_chroma_guided behind the Y edge, on the compute stream: a joint bilateral filter over the source's chroma codes, steered by the source's Y' and by the Y' plane
     the edge has just written into the slot's frame (pixfmt.guidedChroma: integers, byte for byte).  It runs every frame; reuse, views and every ring depth work
-    unchanged.  Refused before a model is loaded: a chain of total scale 1 and 'width' / 'height' / 'fit' on the output step."""
+    unchanged.  Refused before a model is loaded: a chain of total scale 1 and 'width' / 'height' / 'fit' on the output step.
+    With {'op': 'output', 'pixFmt': 'bgr24' | 'rgb24' | 'bgr48le' | 'rgb48le'} on a planar chain the finished frames are interleaved RGB, 3 W H samples of 8 or 16
+    bits: the chain's edge -- 'crop', 'quantise', the chroma pass, the fit -- runs at 16 bits into one intermediate planar frame (compute queue only) and one
+    moe_planes_to_rgb writes the slot's frame, every frame: pixfmt.toRGB of the frame the same list yields with 'yuv420p16le', byte for byte; `edge` gains '+rgb'.
+    Beside such a pixFmt the step takes 'matrix' ('bt709'), 'chromaUp' ('nearest' | 'bilinear' | 'bicubic': the final x2 of the chroma planes), 'chromaLoc' ('center' |
+    'left': H.264 / HEVC material is 'left') and 'dither', which then governs the conversion's rounding; 'order' stays refused (the format's name carries it), so do
+    'chromaUp' / 'chromaLoc' without an RGB pixFmt and unknown values, before a model is loaded.  reuse and views work unchanged."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
