@@ -454,6 +454,27 @@ int moe_fit_run(const moe_fit* fit, const void* src, void* dst, void* stream);
 int moe_fit_info(const moe_fit* fit, int64_t info[4]);
 void moe_fit_destroy(moe_fit* fit);
 
+/* ---- the 3D LUT colour step ---------------------------------------------------------------------------------
+ * The reference's "Retouch" transform (python/AiLUT.py -> site-packages/ailut/csrc/ailut_transform_cuda.cu, the CPU twin ailut_transform_cpu.cpp:20-113): per pixel a
+ * trilinear lookup in a 3D table whose lattice has non-uniform intervals.  The definition is moephoto_amd/lut3d.py (transform, apply) and the device matches it byte
+ * for byte: i_c = clamp(lower_bound(v_c, x_c) - 1, 0, d - 2), t_c = (x_c - v_c[i]) / ((v_c[i + 1] - v_c[i]) + 1e-10f), eight three-factor weights, eight products
+ * summed left to right in the order 000, 100, 010, 110, 001, 101, 011, 111 -- every operation rounded to fp32 on its own.  Values outside the vertices extrapolate.
+ * moe_lut3d_create: table_host = float (3, d, d, d) indexed [c][b][g][r], red fastest (the reference's luts[0]); vertices_host = float (3, d), non-decreasing per row
+ * (its vertices[0]); both on the HOST, copied: the device keeps one 16-byte entry {R, G, B, 0} per lattice point.  Refused (MOE_EINVAL, before any device call): a NULL
+ * pointer, d outside 2 .. 65, a table or vertex value that is not finite, a vertex below the one before it. */
+typedef struct moe_lut3d moe_lut3d;
+int moe_lut3d_create(int d, const float* table_host, const float* vertices_host, int device, moe_lut3d** out);
+/* One frame, one launch, asynchronous on `stream`.  src = H x W x 3 interleaved samples on the device, uint8 (src_bits 8: x = code / 255) or uint16 (16: x = code 2^-16);
+ * dst = as many samples, uint8 for bits = 8, uint16 for bits = 16; red first for MOE_ORDER_RGB, blue first for MOE_ORDER_BGR, on both sides.  y = the transform of x;
+ * with strength s != 1 y = fl32(fl32(s y) + fl32(fl32(1 - s) x)) (moe_stitch_mix's blend); then the chain's quantiser: bits may carry MOE_Q_ROUND / MOE_Q_ORDERED /
+ * MOE_Q_UNIT, thresholds at the pixel's coordinates, its three samples sharing one.  Refused (MOE_EINVAL, before any device call): a NULL pointer, src_bits or bits
+ * outside {8, 16}, unknown or contradictory MOE_Q_* flags, MOE_Q_UNIT without a mode, H or W below 1, 3 H W beyond int, an unknown order, a strength that is not
+ * finite, a misaligned pointer to 16-bit samples, a dst that overlaps src. */
+int moe_lut3d_run(const moe_lut3d* lut, const void* src, int src_bits, int H, int W, void* dst, int bits, int order, float strength, void* stream);
+/* info[0 .. 4) = d, the bytes of the device's table, the LDS bytes of a workgroup (the vertices), the pixels a thread owns. */
+int moe_lut3d_info(const moe_lut3d* lut, int64_t info[4]);
+void moe_lut3d_destroy(moe_lut3d* lut);
+
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.
  * alpha, strength, bits (with its MOE_Q_* flags), dst, dst_dtype as in moe_stitch_mix with C = the plan's planes and T = img_dtype.  Asynchronous on `stream`. */

@@ -10,15 +10,16 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'stitch.hip', 'chroma.hip', 'chroma_guided.hip', 'planes_rgb.hip', 'fit.hip', 'fit_px.hip', 'luma.hip', 'blend.hip', 'sym.hip',
-           'errors.cpp', 'options.cpp', 'weights.cpp', 'forward.cpp', 'forward_arsb.cpp', 'forward_sedn.cpp', 'forward_lite.cpp', 'calibrate.cpp', 'plan_run.cpp', 'polyphase.cpp', 'planner.cpp']
+SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'stitch.hip', 'chroma.hip', 'chroma_guided.hip', 'planes_rgb.hip', 'lut3d.hip', 'fit.hip', 'fit_px.hip', 'luma.hip', 'blend.hip', 'sym.hip',
+           'errors.cpp', 'options.cpp', 'weights.cpp', 'forward.cpp', 'forward_arsb.cpp', 'forward_sedn.cpp', 'forward_lite.cpp', 'calibrate.cpp', 'plan_run.cpp', 'polyphase.cpp', 'lut3d_api.cpp', 'planner.cpp']
 HEADERS = ['common.h', 'engine.h', 'net.h', 'rowtile.h', 'mfma_stream.h', 'run_store.h', 'luma.h', 'quant.h', 'stitch_yuv_body.inc', 'to_output_yuv_body.inc', 'polyphase.h', os.path.join('..', '..', 'include', 'moephoto_amd.h')]      # (paths from csrc/; the ABI header last)
 LIB = os.path.join(HERE, 'libmoephoto_amd.so')
 ARCH = 'gfx950'
 # packed fp32 VALU (v_pk_add_f32 / v_pk_fma_f32, formed by the SLP vectoriser) costs ~+11 cycles per instruction beside MFMAs
 # (MI355X_MICROARCH.md, per-instruction constants): scalar fp32 in the epilogues that ride in an MFMA stream
 # -amdgpu-mfma-vgpr-form: MFMA results in arch VGPRs (the weights occupy the AGPRs), so the epilogues read them without v_accvgpr_read
-EXTRA_FLAGS = {'blend.hip': ['-ffp-contract=off'],      # three separately rounded operations per blend, as torch evaluates the reference's expression
+EXTRA_FLAGS = {'lut3d.hip': ['-ffp-contract=off'],      # every product, sum and quotient of the transform rounded on its own, as the definition writes them
+               'blend.hip': ['-ffp-contract=off'],      # three separately rounded operations per blend, as torch evaluates the reference's expression
                'sym.hip': ['-ffp-contract=off'],        # the ensemble's sum and its closing division: two roundings, as torch's `v + view` and `/ (n + 1)`
                'arsb32c.hip': ['-fno-slp-vectorize', '-fno-honor-nans', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv64_x3.hip': ['-fno-slp-vectorize'], 'conv64_q8.hip': ['-fno-slp-vectorize', '-fno-honor-nans', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv64_sq.hip': ['-fno-slp-vectorize', '-fno-honor-nans', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'arsb_sq.hip': ['-fno-slp-vectorize', '-fno-honor-nans', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv64_s.hip': ['-fno-slp-vectorize', '-fno-honor-nans', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv1x1.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv1x1_f2.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'], 'conv3x3_sp.hip': ['-fno-honor-nans'], 'conv3x3_rw.hip': ['-fno-honor-nans', '-fno-slp-vectorize'],
                'conv3x3_ps4.hip': ['-fno-honor-nans', '-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'],

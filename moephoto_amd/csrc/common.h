@@ -539,6 +539,12 @@ constexpr int RGB_FRAC = 20;
 struct PlanesRgb { int coef[5]; int yoff, coff, cmax, top, rgb, ordered; };
 // src: a planar 4:2:0 frame of H x W at `depth` (u8 for 8, else u16); dst: H x W x 3 interleaved samples (u8 for bits 8, else u16); tx / ty: the x2 phase tables
 void launch_planes_rgb(const void* src, int depth, int H, int W, void* dst, int bits, int taps, const ChromaTab& tx, const ChromaTab& ty, const PlanesRgb& k, hipStream_t s);
+// lut3d.hip: moe_lut3d_run's 3D LUT colour edge (moephoto_amd/lut3d.py: transform / apply).  table: d^3 entries {R, G, B, 0}, red fastest, and vert: the 3 x d
+// vertices, both in DEVICE memory (the handle's); strength / rest = s and fl32(1 - s), read where blend is set; rgb: red is the first sample of a pixel
+constexpr int LUT3D_MIN = 2, LUT3D_MAX = 65;
+struct Lut3dArgs { const float4* table; const float* vert; int d; float strength, rest; int blend, rgb; };
+// src / dst: H x W x 3 interleaved samples (u8 for 8 bits, u16 for 16); quant = 2^bits, or dq for the rounding / dithering quantiser
+void launch_lut3d(const void* src, int src_bits, int H, int W, void* dst, int bits, const Lut3dArgs& k, float quant, const QuantDither* dq, hipStream_t s);
 // fit.hip: one axis of moe_fit_run's rational polyphase filter, in DEVICE memory: output index o reads `taps` source samples from off[o] on with the 14-bit coefficients
 // coef[o * FIT_TAPS + 0 .. taps) (rows of FIT_TAPS, 32 bytes, the base 16-byte aligned; moephoto_amd/pixfmt.py: fitTable).  A workgroup's output tile is FIT_TW x th.
 constexpr int FIT_TW = 128, FIT_TAPS = 16;

@@ -17,6 +17,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
   guidedChroma                         (no counterpart) -> moe_chroma_guided: the same planes by a joint bilateral filter steered by the finished luma (pixfmt.guidedChroma)
   planesToRGB                          (python/video.py:230 asks for bgr48le on the encoder's pipe) -> moe_planes_to_rgb: the interleaved RGB frame of a chain on 4:2:0
                                        planes -- chroma x2 by the same integer filter, then the standard's inverse matrix in fixed point (pixfmt.toRGB)
+  lut3d                                (python/AiLUT.py's transform: site-packages/ailut/csrc/ailut_transform_cuda.cu) -> moe_lut3d_create / moe_lut3d_run: a 3D LUT with
+                                       non-uniform vertices on interleaved samples, with the strength blend and the quantiser in the same launch (lut3d.apply)
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
   fitPixels                            (no counterpart) -> moe_fit_create_px / moe_fit_run: the same filter on an interleaved image (pixfmt.fitPixels)
@@ -1108,6 +1110,62 @@ def fitPixels(srcDepth, dstDepth, channels, h, w, oh, ow, method):
         _flatPair('fitPixels', 'buffers', src_dev, n_in, out, n_out)
         cur = torch.cuda.current_stream(src_dev.device)
         _lib.check(_lib.lib().moe_fit_run(handle(src_dev.device)._h, src_dev.data_ptr(), out.data_ptr(), cur.cuda_stream))
+        src_dev.record_stream(cur)
+        return out
+    f.info = lambda device=None: handle(device if device is not None else torch.device(config.device())).info()
+    return f
+
+
+class _LutHandle(object):
+    """A moe_lut3d handle: the re-laid table and the vertices on the device, freed with the object."""
+
+    def __init__(self, table, vertices, device):
+        self._h = ctypes.c_void_p()
+        _lib.check(_lib.lib().moe_lut3d_create(int(table.shape[1]), table.ctypes.data, vertices.ctypes.data, device, ctypes.byref(self._h)))
+
+    def info(self):
+        """dict(d=.., tableBytes=the device's table, lds=bytes per workgroup, pixels=per thread) of the kernel's launch."""
+        v = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.lib().moe_lut3d_info(self._h, v))
+        return dict(d=int(v[0]), tableBytes=int(v[1]), lds=int(v[2]), pixels=int(v[3]))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h and _lib._lib is not None:
+            _lib._lib.moe_lut3d_destroy(h)
+
+
+def lut3d(table, vertices=None, srcBits=16, bits=16, order='bgr', strength=1.0, dither=None):
+    """The 3D LUT colour step (moe_lut3d_create / moe_lut3d_run; the definition: lut3d.apply): f(src_dev, out, h, w) reads the h x w x 3 interleaved samples at srcBits
+    (8 | 16) in src_dev (a flat contiguous uint8 device tensor of exactly those bytes) and writes as many at `bits` (8 | 16) into out, likewise, in one launch: the
+    reader, the trilinear lookup in `table` (float32 (3, d, d, d), [c, b, g, r]) over `vertices` (float32 (3, d); lut3d.uniform(d) by default), the blend with
+    `strength`, the quantiser with `dither` (None | 'round' | 'ordered').  order: 'bgr' | 'rgb', of both sides.  Everything lut3d.check refuses is refused here, before
+    a device is needed.  The handle (the table on the device) is made at the first call, for that call's device, and lives as long as f; f.info() describes it."""
+    from . import lut3d as _def
+    table = np.asarray(table)
+    table, vertices = _def.check(table, _def.uniform(table.shape[1]) if vertices is None and table.ndim == 4 else vertices)
+    for name, b in (('srcBits', srcBits), ('bits', bits)):
+        if b not in (8, 16):
+            raise ValueError('lut3d: {} must be 8 or 16, got {!r}'.format(name, b))
+    if order not in _def.ORDERS:
+        raise ValueError("lut3d: 'order' {!r} is not supported ({})".format(order, ', '.join(_def.ORDERS)))
+    strength = float(strength)
+    if not math.isfinite(strength):
+        raise ValueError("lut3d: 'strength' {!r} is not finite".format(strength))
+    qf = ditherFlags('lut3d', dither, bits, 'rgb')
+    oid = 1 if order == 'rgb' else 0          # MOE_ORDER_RGB / MOE_ORDER_BGR
+    handles = {}
+
+    def handle(device):
+        if device not in handles:
+            handles[device] = _LutHandle(table, vertices, device.index or 0)
+        return handles[device]
+
+    def f(src_dev, out, h, w):
+        n = 3 * int(h) * int(w)
+        _flatPair('lut3d', 'buffers', src_dev, n * (srcBits // 8), out, n * (bits // 8))
+        cur = torch.cuda.current_stream(src_dev.device)
+        _lib.check(_lib.lib().moe_lut3d_run(handle(src_dev.device)._h, src_dev.data_ptr(), srcBits, int(h), int(w), out.data_ptr(), bits | qf, oid, strength, cur.cuda_stream))
         src_dev.record_stream(cur)
         return out
     f.info = lambda device=None: handle(device if device is not None else torch.device(config.device())).info()

@@ -45,15 +45,20 @@ With {'op': 'output', 'pixFmt': 'bgr24' | 'rgb24' | 'bgr48le' | 'rgb48le'} behin
 frame as yuv420p16le through the edge it always used, into one intermediate on the compute queue, and one moe_planes_to_rgb -- the chroma planes x2 by the integer
 filter, the standard's inverse matrix in fixed point -- writes the frame handed out (pixfmt.toRGB is the definition).  Beside such a pixFmt the
 step takes 'matrix', 'chromaUp' (the filter of the final x2), 'chromaLoc' (how the frame's chroma is sited: H.264 / HEVC material is 'left') and 'dither'.
+
+With {'op': 'lut', 'file': path} or {'op': 'lut', 'table': array, 'vertices': array} ('strength': s is optional) as the last compute step of a chain whose frames are
+interleaved RGB samples both builders end the chain in a 3D LUT: whatever edge wrote the frame writes it at 16 bits into one intermediate, and one moe_lut3d_run --
+the reference's AiLUT transform, a trilinear lookup over non-uniform vertices, with the strength blend and the quantiser -- writes the frame at the depth asked for
+(lut3d.apply is the definition).
 """
 import math
 import time
 from functools import reduce
 
-from . import _lib, pixfmt, quant, reuse as _reuse, runDN, runSR
+from . import _lib, lut3d as _lut3d, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
 from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, guidedChroma, lumaChroma, lumaKeys,
-                           lumaMerge, lumaSplit, mergeAlpha, planesToRGB, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
+                           lumaMerge, lumaSplit, lut3d as lutSamples, mergeAlpha, planesToRGB, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
                 resize={'toInt': ['width', 'height'], 'toFloat': ['scaleW', 'scaleH']})
@@ -195,9 +200,10 @@ def _samplesOnDevice(bitDepth):
     return f
 
 
-def _pixelFitLast(fit, fused, bitDepth):
+def _pixelFitLast(fit, fused, bitDepth, download=True):
     """genProcess' tail behind a 'fit' resize step: the chain's 16-bit samples on the device (the fused luma fold's, or the unfused quantiser's), one fitPixels to the
-    step's size and the chain's bitDepth, downloaded as toOutput returns its image.  The handle is kept per image shape."""
+    step's size and the chain's bitDepth, downloaded as toOutput returns its image (download=False: left on the device, for a 'lut' step behind it).  The handle is
+    kept per image shape."""
     import numpy as np
     import torch
     samples, fitters = fused or _samplesOnDevice(16), {}
@@ -213,6 +219,8 @@ def _pixelFitLast(fit, fused, bitDepth):
         oh, ow, run = fitters[(H, W, C)]
         out = torch.empty((oh, ow, C), dtype=_outStorage(bitDepth)[0], device=mid.device)
         run(_flatBytes(mid), _flatBytes(out))
+        if not download:
+            return out
         a = out.cpu().numpy()
         return a.view(np.uint16) if bitDepth > 8 else a
     return f
@@ -408,6 +416,93 @@ def _flatBytes(t):
     return t.view(torch.uint8).reshape(-1)
 
 
+# ---- the 3D LUT colour step: {'op': 'lut', 'file': path} | {'op': 'lut', 'table': array, 'vertices': array} --------------------------------
+LUT_FMT16 = {'bgr24': 'bgr48le', 'rgb24': 'rgb48le', 'bgr48le': 'bgr48le', 'rgb48le': 'rgb48le'}          # the frame in front of the step, for the pixFmt asked for
+
+
+def _lutStep(steps, planar, bitDepth=None):
+    """dict(table, vertices, strength, order) of the step list's 'lut' step, or None where it has none.  The step is the last compute step of a chain whose frames
+    are interleaved RGB samples: an RGB source (files, arrays, bgr24 / bgr48le frames) or a planar source whose output step names an RGB 'pixFmt'.  'file': a .cube
+    file (lut3d.parseCube); or 'table': float32 (3, d, d, d) with 'vertices': float32 (3, d), lut3d.uniform(d) by default; 'strength': the blend with the frame in
+    front of the step, 1 by default.  The samples' order is the pixFmt's on a planar chain, 'bgr' behind another buffer source and 'rgb' behind a file or an array;
+    'order' on the step overrides the latter two.  ValueError naming the key, before any model is loaded: a 'lut' step that is not the last compute step, two of them,
+    both or neither of 'file' / 'table', 'vertices' without 'table', a planar Y'CbCr sink, a strength that is not finite, and what lut3d.parseCube / lut3d.check
+    refuse of the table."""
+    import numpy as np
+    luts = [s for s in steps if s.get('op') == 'lut']
+    if not luts:
+        return None
+    if len(luts) > 1:
+        raise ValueError("lut: a chain holds one 'lut' step at most, this one has {}".format(len(luts)))
+    s = luts[0]
+    work = [t for t in steps if t.get('op') not in ('file', 'buffer', 'output')]
+    if s is not work[-1]:
+        raise ValueError("lut: the 'lut' step must be the last compute step of the chain: it writes the frame's samples")
+    if 'vertices' in s and 'table' not in s:
+        raise ValueError("lut: 'vertices' needs 'table' beside it (a 'file' brings its own uniform vertices)")
+    if ('file' in s) == ('table' in s):
+        raise ValueError("lut: exactly one of 'file' and 'table' names the table, the step has {}".format('both' if 'file' in s else 'neither'))
+    try:
+        strength = float(s.get('strength', 1.0))
+    except (TypeError, ValueError):
+        raise ValueError("lut: 'strength' {!r} is not a number".format(s.get('strength')))
+    if not math.isfinite(strength):
+        raise ValueError("lut: 'strength' {!r} is not finite".format(s['strength']))
+    if planar:
+        if planar[1] not in pixfmt.RGB_FORMATS:
+            raise ValueError("lut: a planar Y'CbCr sink ('pixFmt': '{}') behind a 'lut' step is not in this change: the step writes interleaved RGB samples "
+                             "(output 'pixFmt': {})".format(planar[1], ', '.join(pixfmt.RGB_FORMATS)))
+        if 'order' in s:
+            raise ValueError("lut: 'order' does not apply to a chain on planar frames: the output step's 'pixFmt' carries it")
+        order = pixfmt.RGB_FORMATS[planar[1]][1]
+    else:
+        for o in steps:
+            if o.get('op') == 'output' and o.get('pixFmt') is not None:
+                raise ValueError("lut: a planar Y'CbCr sink ('pixFmt': '{}') behind a 'lut' step is not in this change: the step writes interleaved RGB samples".format(o['pixFmt']))
+        order = s.get('order', 'bgr' if steps[0].get('op') == 'buffer' else 'rgb')
+        if order not in _lut3d.ORDERS:
+            raise ValueError("lut: 'order' {!r} is not supported ({})".format(order, ', '.join(_lut3d.ORDERS)))
+        if bitDepth not in (8, 16):
+            raise ValueError("lut: the step writes 8- or 16-bit samples, the chain's bitDepth is {!r}".format(bitDepth))
+    if 'file' in s:
+        with open(s['file'], 'r') as f:
+            table, vertices = _lut3d.parseCube(f.read())
+    else:
+        table = np.asarray(s['table'], np.float32)
+        vertices = np.asarray(s['vertices'], np.float32) if s.get('vertices') is not None else (_lut3d.uniform(table.shape[1]) if table.ndim == 4 else None)
+        table, vertices = _lut3d.check(table, vertices)
+    return dict(table=table, vertices=vertices, strength=strength, order=order)
+
+
+def _withoutLut(steps):
+    return [s for s in steps if s.get('op') != 'lut']
+
+
+def _lutLast(lut, bitDepth, dither):
+    """genProcess' tail behind a 'lut' step: the chain's 16-bit samples on the device (H, W, C), one moe_lut3d_run on the three colour samples at the chain's bitDepth,
+    downloaded as toOutput returns its image.  With four planes alpha passes around the step, as RGBFilter passes it around its net: its 16-bit code, or at 8 bits that
+    code's high byte (the truncating quantiser's sample)."""
+    import numpy as np
+    import torch
+    run = lutSamples(lut['table'], lut['vertices'], 16, bitDepth, lut['order'], lut['strength'], dither)
+
+    def f(mid):
+        H, W, C = mid.shape
+        if C not in (3, 4):
+            raise ValueError("lut: the step takes an image of 3 or 4 planes (colour, or colour and alpha), this one has {}".format(C))
+        rgb = (mid if C == 3 else mid[:, :, :3]).contiguous()
+        out = torch.empty((H, W, 3), dtype=_outStorage(bitDepth)[0], device=mid.device)
+        run(_flatBytes(rgb), _flatBytes(out), H, W)
+        if C == 4:
+            alpha = mid[:, :, 3:]
+            if bitDepth == 8:
+                alpha = ((alpha.to(torch.int32) & 0xffff) >> 8).to(torch.uint8)
+            out = torch.cat([out, alpha], 2)
+        a = out.cpu().numpy()
+        return a.view(np.uint16) if bitDepth > 8 else a
+    return f
+
+
 GUIDED = 'guided'          # the source step's 'chroma' value that names the luma-guided filter (DESIGN.md section 20)
 
 
@@ -485,14 +580,20 @@ def _planeChain(steps, fuse, rsteps=None):
     return funcs, nodes, scale, last
 
 
-def _genProcessPlanes(steps, fmts, dither=None):
+def _genProcessPlanes(steps, fmts, dither=None, lut=None):
     import numpy as np
     import torch
     src, dst = fmts
     rgb, converters = _planeRGBStep(steps, dst), {}
     if rgb:          # the chain's frame as yuv420p16le without 'dither', then one moe_planes_to_rgb: the key governs that conversion's rounding
         dst, dither, rgbDither = PLANAR16, None, dither
+    if lut:          # a 'lut' step: the RGB frame at 16 bits without 'dither', then one moe_lut3d_run at the pixFmt's depth: the key governs the step's quantiser
+        lutBits = pixfmt.RGB_FORMATS[rgb[0]][0]
+        lutRun = lutSamples(lut['table'], lut['vertices'], 16, lutBits, lut['order'], lut['strength'], rgbDither)
+        rgb, rgbDither = (LUT_FMT16[rgb[0]],) + tuple(rgb[1:]), None
     funcs, nodes, scale, _ = _planeChain(steps, False)
+    if lut:
+        nodes.append(dict(op='lut'))
     quantise = toPlanes(pixfmt.FORMATS[dst], dither)
     chroma, resamplers = _planeChroma(steps), {}
     fit, quantise16, fitters = _planeFit(steps), toPlanes(16), {}
@@ -503,6 +604,8 @@ def _genProcessPlanes(steps, fmts, dither=None):
             if (W, H) not in converters:
                 converters[(W, H)] = planesToRGB(dst, W, H, *rgb, dither=rgbDither)
             out = converters[(W, H)](out, torch.empty((3 * W * H * (pixfmt.RGB_FORMATS[rgb[0]][0] // 8),), dtype=torch.uint8, device=out.device))
+        if lut:
+            out = lutRun(out, torch.empty((3 * W * H * (lutBits // 8),), dtype=torch.uint8, device=out.device), H, W)
         return out.cpu().numpy().tobytes()
 
     def runFit(rawDev, y, c, width, height, dev):
@@ -560,8 +663,10 @@ def genProcess(steps, bitDepth=8, outFile=None):
     _lumaCheck(steps, bool(planar))
     dither = _outputDither(steps)          # (before any model is loaded)
     if planar:          # the decoder's own Y'CbCr 4:2:0 planes in, planar frames out
-        return _genProcessPlanes(steps, planar, dither)
+        return _genProcessPlanes(_withoutLut(steps), planar, dither, _lutStep(steps, planar))
     _refuseFit(steps)
+    lut = _lutStep(steps, None, int(steps[0].get('bitDepth', 16)) if steps and steps[0].get('op') == 'buffer' else bitDepth)          # (likewise)
+    steps = _withoutLut(steps)
     ctx = Context()
     funcs, nodes = [], []
     has_file = bool(steps) and steps[0]['op'] == 'file'
@@ -600,7 +705,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         if _isLuma(o):          # a luma-only step; the last one's fold writes the samples itself where it can (an SR without ensemble, a DN of strength 1)
             f = _lumaStep(op, o)[0]
             if opt is work[-1] and not yuv and bitDepth in (8, 16) and (o.ensemble == 0 if op == 'SR' else o.strength == 1):
-                fused = _lumaLastOnDevice(op, o, f) if fit else _lumaLast(op, o, f, bitDepth, dither)
+                fused = _lumaLastOnDevice(op, o, f) if fit or lut else _lumaLast(op, o, f, bitDepth, dither)
             else:
                 funcs.append(f)
         elif op == 'SR':
@@ -613,10 +718,15 @@ def genProcess(steps, bitDepth=8, outFile=None):
         run = lambda im: reduce(apply, funcs, im)
         return (lambda frame: [] if not frame[0] else [run(frame)]), nodes
     if fit:
-        funcs.append(_pixelFitLast(fit, fused, bitDepth))
+        funcs.append(_pixelFitLast(fit, fused, 16, False) if lut else _pixelFitLast(fit, fused, bitDepth))
         nodes.append(dict(op='resize', mode=fit['fit']))
+    elif lut:
+        funcs.append(fused or _samplesOnDevice(16))
     else:
         funcs += [fused] if fused else [toFloat, toOutput(bitDepth, dither)]
+    if lut:          # the frame above at 16 bits, on the device; one moe_lut3d_run writes the samples handed out
+        funcs.append(_lutLast(lut, bitDepth, dither))
+        nodes.append(dict(op='lut'))
     if has_file and outFile is not None:
         funcs.append(lambda im: writeFile(im, outFile, ctx))
     if has_buffer:
@@ -1026,11 +1136,15 @@ class _PlanesBackend(_DeviceBackend):
         self._stage(self.torch.cuda.current_stream(self.dev), s, 'comp', wait, record, work)
 
 
-def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False, dither=None):
+def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False, views=False, dither=None, lut=None):
     src, dst = fmts
     rgb = _planeRGBStep(steps, dst)
     if rgb:          # the chain's frame as yuv420p16le without 'dither', then one moe_planes_to_rgb: the key governs that conversion's rounding
         dst, dither, rgbDither = PLANAR16, None, dither
+    if lut:          # a 'lut' step: the RGB frame at 16 bits without 'dither', then one moe_lut3d_run at the pixFmt's depth: the key governs the step's quantiser
+        lutBits = pixfmt.RGB_FORMATS[rgb[0]][0]
+        lutRun = lutSamples(lut['table'], lut['vertices'], 16, lutBits, lut['order'], lut['strength'], rgbDither)
+        rgb, rgbDither = (LUT_FMT16[rgb[0]],) + tuple(rgb[1:]), None
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     _checkReuse(reuse)
@@ -1106,6 +1220,17 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
                 planar['buf'] = torch.empty((planarBytes,), dtype=torch.uint8, device=out.device)
             planarEdge(y, c, planar['buf'], *reuses)
             toRGB(planar['buf'], out)
+    if lut:          # the RGB edge above writes one intermediate frame at 16 bits (compute queue only), then one moe_lut3d_run into the slot's frame, every frame
+        rgbBytes, rgbEdge, mid16 = outBytes, edge, {}
+        edgeName += '+lut'
+        outBytes = 3 * fw * fh * (lutBits // 8)
+        nodes.append(dict(op='lut'))
+
+        def edge(y, c, out, *reuses):
+            if 'buf' not in mid16:          # allocated once, at the first frame
+                mid16['buf'] = torch.empty((rgbBytes,), dtype=torch.uint8, device=out.device)
+            rgbEdge(y, c, mid16['buf'], *reuses)
+            lutRun(mid16['buf'], out, fh, fw)
     state = _ReuseState(rsteps, bool(last)) if reuse else None
     backend = _PlanesBackend(funcs, edge, src, width, height, depth, timing, outBytes, state, views, bool(chroma))
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes, frameBytes=pixfmt.frameBytes(src, width, height))
@@ -1184,7 +1309,14 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     moe_planes_to_rgb writes the slot's frame, every frame: pixfmt.toRGB of the frame the same list yields with 'yuv420p16le', byte for byte; `edge` gains '+rgb'.
     Beside such a pixFmt the step takes 'matrix' ('bt709'), 'chromaUp' ('nearest' | 'bilinear' | 'bicubic': the final x2 of the chroma planes), 'chromaLoc' ('center' |
     'left': H.264 / HEVC material is 'left') and 'dither', which then governs the conversion's rounding; 'order' stays refused (the format's name carries it), so do
-    'chromaUp' / 'chromaLoc' without an RGB pixFmt and unknown values, before a model is loaded.  reuse and views work unchanged."""
+    'chromaUp' / 'chromaLoc' without an RGB pixFmt and unknown values, before a model is loaded.  reuse and views work unchanged.
+    With {'op': 'lut', 'file': path} or {'op': 'lut', 'table': array, 'vertices': array} (and 'strength') as the last compute step of a chain whose frames are
+    interleaved RGB samples -- an RGB source, or a planar one with an RGB pixFmt on the output step -- the chain ends in a 3D LUT: the edge the chain ends in without
+    the step (the fold, the quantiser, the 'fit' kernel, moe_planes_to_rgb) writes 16-bit samples into one intermediate (allocated at the first frame, compute queue
+    only) and one moe_lut3d_run writes the slot's frame at the depth asked for, every frame: lut3d.apply of the 16-bit frame the same list yields without the step,
+    byte for byte; `edge` gains '+lut'.  'dither' on the output step governs the step's one quantisation.  reuse and views work unchanged.  Refused by key before a
+    model is loaded: a 'lut' step that is not the last compute step, two of them, both or neither of 'file' / 'table', 'vertices' without 'table', a planar Y'CbCr
+    sink, a strength that is not finite, a table lut3d.check refuses."""
     steps = [dict(s) for s in steps]
     if not steps or steps[0].get('op') != 'buffer':
         raise ValueError("frame stream: the first step must be {'op': 'buffer', 'bitDepth': 8 | 16}")
@@ -1192,15 +1324,19 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     _lumaCheck(steps, bool(planar))
     dither = _outputDither(steps)          # (before any model is loaded)
     if planar:          # {'op': 'buffer', 'pixFmt': ..}: the decoder's own Y'CbCr 4:2:0 planes in, planar frames out ('crop' or 'quantise'; a blended DN is a 'quantise' chain)
-        return _genFrameStreamPlanes(steps, planar, width, height, depth, timing, reuse, views, dither)
+        return _genFrameStreamPlanes(_withoutLut(steps), planar, width, height, depth, timing, reuse, views, dither, _lutStep(steps, planar))
     _refuseFit(steps)
     bitDepth = int(steps[0].get('bitDepth', 16))
+    lut = _lutStep(steps, None, bitDepth)          # (before any model is loaded)
+    steps = _withoutLut(steps)
+    if lut:          # the chain's edge writes 16-bit samples without 'dither': the key governs the step's quantiser
+        lutDither, dither = dither, None
     _checkRing(depth, bitDepth)          # (before any model is loaded)
     yuv = _outputFormat(steps)           # (likewise)
     _checkReuse(reuse)                   # (likewise)
     _checkViews(views)                   # (likewise)
     fit = _pixelFit(steps, bitDepth)     # (likewise)
-    edgeDepth = 16 if fit else bitDepth          # (a 'fit' resize step: the edge writes 16-bit samples of the chain's own size, the slot's frame is the filter's)
+    edgeDepth = 16 if fit or lut else bitDepth          # (a 'fit' resize step: the edge writes 16-bit samples of the chain's own size, the slot's frame is the filter's; a 'lut' step likewise)
     yuvOf = toYuv(*yuv, dither=dither) if yuv else None
     work = [s for s in steps if s['op'] not in ('file', 'buffer', 'output') and s is not fit]
     for opt in work:
@@ -1261,9 +1397,34 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
     outHW, fitted = (h, w), None
     if fit:          # the edge above fills the slot's 16-bit samples of h x w; one moe_fit_run from them writes the slot's frame, behind everything reuse touches
         outHW = _pixelFitSize(fit, h, w)
-        fitted = ((h, w), fitPixels(16, bitDepth, 3, h, w, outHW[0], outHW[1], fit['fit']))
+        fitted = ((h, w), fitPixels(16, 16 if lut else bitDepth, 3, h, w, outHW[0], outHW[1], fit['fit']))
         edgeName += '+fit'
         nodes.append(dict(op='resize', mode=fit['fit']))
+    if lut:          # the edge (and the fit) above write one intermediate frame at 16 bits (compute queue only); one moe_lut3d_run from it writes the slot's frame, every frame
+        import torch
+        lutRun, mid16, (lh, lw) = lutSamples(lut['table'], lut['vertices'], 16, bitDepth, lut['order'], lut['strength'], lutDither), {}, outHW
+        edgeName += '+lut'
+        nodes.append(dict(op='lut'))
+
+        def lutMid(dev):
+            if 'buf' not in mid16:          # allocated once, at the first frame
+                mid16['buf'] = torch.empty((lh, lw, 3), dtype=_outStorage(16)[0], device=dev)
+            return mid16['buf']
+        if fit:
+            fitRun = fitted[1]
+
+            def fitThenLut(mid, out):
+                buf = lutMid(out.device)
+                fitRun(mid, _flatBytes(buf))
+                lutRun(_flatBytes(buf), out, lh, lw)
+            fitted = (fitted[0], fitThenLut)
+        else:
+            plainEdge = edge
+
+            def edge(x, out, *reuses):
+                buf = lutMid(out.device)
+                plainEdge(x, buf, *reuses)
+                lutRun(_flatBytes(buf), _flatBytes(out), lh, lw)
     state = _ReuseState(rsteps, tiledEdge) if reuse else None
     backend = _DeviceBackend(funcs, edge, bitDepth, width, height, outHW, depth, timing, pixfmt.frameBytes(yuv[0], w, h) if yuv else None, state, views, fitted)
     stream = FrameStream(backend, width, height, bitDepth, depth, nodes)
