@@ -474,6 +474,44 @@ int moe_lut3d_run(const moe_lut3d* lut, const void* src, int src_bits, int H, in
 /* info[0 .. 4) = d, the bytes of the device's table, the LDS bytes of a workgroup (the vertices), the pixels a thread owns. */
 int moe_lut3d_info(const moe_lut3d* lut, int64_t info[4]);
 void moe_lut3d_destroy(moe_lut3d* lut);
+/* The handle's table back on the HOST in moe_lut3d_create's layout: table_host = float (3, d, d, d), vertices_host = float (3, d).  Synchronises `stream`.  For a
+ * caller that wants the table a generator wrote for a frame (as a .cube file: moephoto_amd/lut3d.py, formatCube), and for tests.  Refused: a NULL pointer. */
+int moe_lut3d_read(const moe_lut3d* lut, float* table_host, float* vertices_host, void* stream);
+
+/* ---- the AiLUT generator net --------------------------------------------------------------------------------
+ * The other half of the reference's "Retouch": the net that looks at a 256 x 256 thumbnail of the frame and writes the frame's own table and vertices
+ * (python/AiLUT.py:167-181 AiLUT.forward up to ailut_transform: F.interpolate, :26-46 TPAMIBackbone(extra_pooling=True), :57-80 LUTGenerator, :82-121 AdaInt; the
+ * AiLUT_sRGB_3 / AiLUT_XYZ_3 rows of python/dehaze.py:27-28).  The definition is moephoto_amd/ailut.py (thumbnail, generate); the device computes it in fp32 with
+ * fp64 statistics (the reference: fp16 autocast), eight launches a frame, no atomics: two runs on the same input give the same bits.
+ * moe_ailut_create .. moe_ailut_finalize are shaped as moe_net's loader (AiLUT(n_ranks, n_vertices) and load_state_dict, python/imageProcess.py:319-328):
+ * d = n_vertices (2 .. 65), ranks = n_ranks (1 .. 8); the names are the reference's state-dict keys (backbone.{0..4}.0.weight|bias, backbone.{0..3}.2.weight|bias,
+ * lut_generator.weights_generator.weight|bias, lut_generator.basis_luts_bank.weight, adaint.intervals_generator.weight|bias); data is fp32, C-contiguous, on the
+ * HOST, copied.  Refused (MOE_EINVAL, before any device call): a NULL pointer, d or ranks outside their range, an index outside the list, an unknown name, another
+ * shape than the generator's, a value that is not finite; MOE_ESTATE: a finalize with a parameter unset. */
+typedef struct moe_ailut moe_ailut;
+int moe_ailut_create(int d, int ranks, moe_ailut** out);
+int moe_ailut_num_params(const moe_ailut* g);
+int moe_ailut_param_info(const moe_ailut* g, int index, const char** name, int64_t shape[4], int* ndim);
+int moe_ailut_set_param(moe_ailut* g, const char* name, const float* data, const int64_t* shape, int ndim);
+/* uploads the parameters and allocates the workspace (about 2.7 MB beside the parameters) on `device`; may be called again after a parameter changed: the earlier
+ * device block is freed behind a synchronise of its device, so runs still in flight finish on it (moe_ailut_destroy likewise) */
+int moe_ailut_finalize(moe_ailut* g, int device);
+/* One frame: thumbnail, five conv blocks, the heads, the table -- eight launches, asynchronous on `stream`, no host round trip.  src = H x W x 3 interleaved samples
+ * on the device as moe_lut3d_run reads them (uint8 for src_bits 8, uint16 for 16; red first for MOE_ORDER_RGB, blue first for MOE_ORDER_BGR), left untouched.
+ * lut = a moe_lut3d of the same d on the same device: its table and vertices are OVERWRITTEN (the const is the host object's), so a moe_lut3d_run queued behind
+ * this call on the same stream applies this frame's table.  The handle owns one workspace: its runs belong on one stream at a time.  Refused (before any device
+ * call): a NULL pointer, a generator that is not finalized (MOE_ESTATE), a table handle of another d or on another device, src_bits outside {8, 16}, H or W below 1,
+ * 3 H W beyond int, an unknown order, a misaligned pointer to 16-bit samples. */
+int moe_ailut_run(const moe_ailut* g, const void* src, int src_bits, int H, int W, int order, const moe_lut3d* lut, void* stream);
+/* MEASUREMENT ONLY, not for callers (tools/ailut_bench.py): launch `stage` of moe_ailut_run alone (0 the thumbnail, 1 .. 5 the conv blocks, 6 the heads, 7 the table) */
+int moe_ailut_stage(const moe_ailut* g, int stage, const void* src, int src_bits, int H, int W, int order, const moe_lut3d* lut, void* stream);
+/* moe_ailut_run's first launch alone: dst = float (3, 256, 256) RGB planes on the device (ailut.thumbnail).  It has no handle, so it takes
+ * the device as moe_to_float does.  Refusals as moe_ailut_run's, and a dst off 4 bytes or a negative device. */
+int moe_ailut_thumbnail(const void* src, int src_bits, int H, int W, int order, float* dst, int device, void* stream);
+/* TESTS ONLY, not for callers: *bad = how many bytes of the guard bands between the handle's device buffers no longer hold their pattern, plus how many parameters differ from the host's
+ * copies (0 for an intact handle).  Synchronises `stream`.  For tests. */
+int moe_ailut_guards(const moe_ailut* g, int64_t* bad, void* stream);
+void moe_ailut_destroy(moe_ailut* g);
 
 /* The whole DN step (procDN: python/procedure.py:52-55 -> RGBFilter, python/imageProcess.py:350-377,562): moe_run_plan on the plan's internal pool with its final fold
  * replaced by moe_stitch_mix.  img: the colour planes doCrop would be handed, already padded where the plan pads; the blend reads its top-left out_h x out_w region.

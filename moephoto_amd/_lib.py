@@ -116,6 +116,17 @@ def lib():
         'moe_lut3d_run': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, ctypes.c_float, c_vp]),
         'moe_lut3d_info': (c_int, [c_vp, P(c_i64)]),
         'moe_lut3d_destroy': (None, [c_vp]),
+        'moe_lut3d_read': (c_int, [c_vp, c_vp, c_vp, c_vp]),
+        'moe_ailut_create': (c_int, [c_int, c_int, P(c_vp)]),
+        'moe_ailut_num_params': (c_int, [c_vp]),
+        'moe_ailut_param_info': (c_int, [c_vp, c_int, P(ctypes.c_char_p), P(c_i64), P(c_int)]),
+        'moe_ailut_set_param': (c_int, [c_vp, ctypes.c_char_p, c_vp, P(c_i64), c_int]),
+        'moe_ailut_finalize': (c_int, [c_vp, c_int]),
+        'moe_ailut_run': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+        'moe_ailut_stage': (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+        'moe_ailut_thumbnail': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+        'moe_ailut_guards': (c_int, [c_vp, P(c_i64), c_vp]),
+        'moe_ailut_destroy': (None, [c_vp]),
         'moe_luma_split': (c_int, [c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
         'moe_luma_merge': (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp]),
         'moe_stitch_luma': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp]),
@@ -142,7 +153,9 @@ EXPORTS = ['moe_last_error', 'moe_abi_version', 'moe_device_count', 'moe_net_cre
            'moe_run_plan_ex', 'moe_run_plan_frames', 'moe_run_plan_tiles', 'moe_sym_pad', 'moe_sym_fold', 'moe_run_plan_ens', 'moe_stitch_out', 'moe_run_plan_out', 'moe_stitch_mix', 'moe_run_plan_filter', 'moe_to_float', 'moe_to_output', 'moe_resize',
            'moe_stitch_yuv', 'moe_run_plan_yuv', 'moe_to_yuv', 'moe_planes_to_float', 'moe_stitch_planes', 'moe_run_plan_planes', 'moe_changed_blocks', 'moe_run_plan_subset', 'moe_chroma_resample',
            'moe_fit_create', 'moe_fit_run', 'moe_fit_info', 'moe_fit_destroy', 'moe_luma_split', 'moe_luma_merge', 'moe_stitch_luma', 'moe_run_plan_luma', 'moe_fit_create_px', 'moe_chroma_guided', 'moe_planes_to_rgb',
-           'moe_lut3d_create', 'moe_lut3d_run', 'moe_lut3d_info', 'moe_lut3d_destroy']
+           'moe_lut3d_create', 'moe_lut3d_run', 'moe_lut3d_info', 'moe_lut3d_destroy', 'moe_lut3d_read',
+           'moe_ailut_create', 'moe_ailut_num_params', 'moe_ailut_param_info', 'moe_ailut_set_param', 'moe_ailut_finalize', 'moe_ailut_run', 'moe_ailut_stage', 'moe_ailut_thumbnail', 'moe_ailut_guards',
+           'moe_ailut_destroy']
 
 
 def check(rc):

@@ -10,8 +10,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'stitch.hip', 'chroma.hip', 'chroma_guided.hip', 'planes_rgb.hip', 'lut3d.hip', 'fit.hip', 'fit_px.hip', 'luma.hip', 'blend.hip', 'sym.hip',
-           'errors.cpp', 'options.cpp', 'weights.cpp', 'forward.cpp', 'forward_arsb.cpp', 'forward_sedn.cpp', 'forward_lite.cpp', 'calibrate.cpp', 'plan_run.cpp', 'polyphase.cpp', 'lut3d_api.cpp', 'planner.cpp']
+SOURCES = ['conv_mfma.hip', 'conv3x3_sp.hip', 'conv3x3_rw.hip', 'conv3x3_ps4.hip', 'conv3x3_ps9.hip', 'arsb32c.hip', 'conv64_x3.hip', 'conv64_q8.hip', 'conv64_sq.hip', 'arsb_sq.hip', 'conv64_s.hip', 'conv1x1.hip', 'conv1x1_f2.hip', 'misc_kernels.hip', 'stitch.hip', 'chroma.hip', 'chroma_guided.hip', 'planes_rgb.hip', 'lut3d.hip', 'ailut.hip', 'fit.hip', 'fit_px.hip', 'luma.hip', 'blend.hip', 'sym.hip',
+           'errors.cpp', 'options.cpp', 'weights.cpp', 'forward.cpp', 'forward_arsb.cpp', 'forward_sedn.cpp', 'forward_lite.cpp', 'calibrate.cpp', 'plan_run.cpp', 'polyphase.cpp', 'lut3d_api.cpp', 'ailut_api.cpp', 'planner.cpp']
 HEADERS = ['common.h', 'engine.h', 'net.h', 'rowtile.h', 'mfma_stream.h', 'run_store.h', 'luma.h', 'quant.h', 'stitch_yuv_body.inc', 'to_output_yuv_body.inc', 'polyphase.h', os.path.join('..', '..', 'include', 'moephoto_amd.h')]      # (paths from csrc/; the ABI header last)
 LIB = os.path.join(HERE, 'libmoephoto_amd.so')
 ARCH = 'gfx950'

@@ -545,6 +545,24 @@ constexpr int LUT3D_MIN = 2, LUT3D_MAX = 65;
 struct Lut3dArgs { const float4* table; const float* vert; int d; float strength, rest; int blend, rgb; };
 // src / dst: H x W x 3 interleaved samples (u8 for 8 bits, u16 for 16); quant = 2^bits, or dq for the rounding / dithering quantiser
 void launch_lut3d(const void* src, int src_bits, int H, int W, void* dst, int bits, const Lut3dArgs& k, float quant, const QuantDither* dq, hipStream_t s);
+// ailut.hip: moe_ailut_run's generator net (moephoto_amd/ailut.py: thumbnail / generate), fp32 throughout, statistics in fp64.  Every pointer is DEVICE memory of the
+// generator's handle: w / b the five convs' weights (cout, cin, 3, 3) and biases, gamma / beta the four norms' affine pairs, act[i] block i's output after the
+// activation (not yet normalised: the consumer normalises as it loads), stat[i] block i's partial (sum, sum of squares) per channel and pixel group as doubles
+// (AILUT_STAT_GROUPS[i] groups, each written whole by one workgroup on every run), lin the ranks + 3 (d - 1) outputs of the two linear heads.
+constexpr int AILUT_SIZE = 256, AILUT_FEATS = 512, AILUT_MIN_RANKS = 1, AILUT_MAX_RANKS = 8, AILUT_STAGES = 8;
+constexpr int AILUT_CH[6] = {3, 16, 32, 64, 128, 128};
+constexpr int AILUT_STAT_GROUPS[4] = {64, 32, 16, 4};
+struct AilutNet {
+    const float* w[5]; const float* b[5]; const float* gamma[4]; const float* beta[4];
+    const float* h0_w; const float* h0_b; const float* bank; const float* g_w; const float* g_b;
+    float* thumb; float* act[5]; double* stat[4]; float* lin;
+    int d, ranks;
+};
+// src: H x W x 3 interleaved samples (u8 for 8 bits, u16 for 16); dst: the 3 x 256 x 256 RGB planes
+void launch_ailut_thumb(const void* src, int src_bits, int H, int W, int rgb, float* dst, hipStream_t s);
+// stage 1 .. 5: conv block `stage`; 6: pool and the two linear heads; 7: the bank products into table (d^3 entries {R, G, B, 0}) and softmax + cumulative sum into
+// vert (3 x d), both the moe_lut3d handle's.  Returns the kernel's name for moe::launched.
+const char* launch_ailut_stage(const AilutNet& n, int stage, float4* table, float* vert, hipStream_t s);
 // fit.hip: one axis of moe_fit_run's rational polyphase filter, in DEVICE memory: output index o reads `taps` source samples from off[o] on with the 14-bit coefficients
 // coef[o * FIT_TAPS + 0 .. taps) (rows of FIT_TAPS, 32 bytes, the base 16-byte aligned; moephoto_amd/pixfmt.py: fitTable).  A workgroup's output tile is FIT_TW x th.
 constexpr int FIT_TW = 128, FIT_TAPS = 16;

@@ -6,12 +6,6 @@
 
 using namespace moe;
 
-struct moe_lut3d {
-    int d, device;
-    void* dev;              // one allocation: d^3 entries {R, G, B, 0}, then the 3 d vertices
-    size_t table_bytes;
-};
-
 extern "C" {
 
 int moe_lut3d_create(int d, const float* table_host, const float* vertices_host, int device, moe_lut3d** out)

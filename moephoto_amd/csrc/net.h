@@ -48,6 +48,17 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }      // (the caller knows that nothing in flight reads it)
 };
 
+}  // namespace moe
+
+// the 3D LUT colour step's handle (lut3d_api.cpp; ailut_api.cpp's generator writes its table)
+struct moe_lut3d {
+    int d, device;
+    void* dev;              // one allocation: d^3 entries {R, G, B, 0}, then the 3 d vertices
+    size_t table_bytes;
+};
+
+namespace moe {
+
 // =====================================================================================================
 // model
 // =====================================================================================================

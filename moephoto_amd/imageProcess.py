@@ -19,6 +19,8 @@ builder) read unchanged; the work itself is done on the device by libmoephoto_am
                                        planes -- chroma x2 by the same integer filter, then the standard's inverse matrix in fixed point (pixfmt.toRGB)
   lut3d                                (python/AiLUT.py's transform: site-packages/ailut/csrc/ailut_transform_cuda.cu) -> moe_lut3d_create / moe_lut3d_run: a 3D LUT with
                                        non-uniform vertices on interleaved samples, with the strength blend and the quantiser in the same launch (lut3d.apply)
+  ailut                                (python/AiLUT.py's generator: AiLUT.forward up to ailut_transform) -> moe_ailut_run + moe_lut3d_run: the net that writes a frame's own
+                                       table and vertices from its 256 x 256 thumbnail, in front of lut3d's launch (ailut.generate, lut3d.apply)
   fitPlanes                            (no counterpart: the reference resizes floats, python/imageProcess.py:174-214) -> moe_fit_create / moe_fit_run: planes of codes
                                        brought to a fitted size by the rational integer polyphase filter of pixfmt.fitPlanes, antialiased where it shrinks
   fitPixels                            (no counterpart) -> moe_fit_create_px / moe_fit_run: the same filter on an interleaved image (pixfmt.fitPixels)
@@ -1169,6 +1171,91 @@ def lut3d(table, vertices=None, srcBits=16, bits=16, order='bgr', strength=1.0, 
         src_dev.record_stream(cur)
         return out
     f.info = lambda device=None: handle(device if device is not None else torch.device(config.device())).info()
+    return f
+
+
+class _AilutHandle(object):
+    """A moe_ailut handle: the generator's parameters and workspace on the device, freed with the object."""
+
+    def __init__(self, params, device):
+        L = _lib.lib()
+        self._h = ctypes.c_void_p()
+        _lib.check(L.moe_ailut_create(int(params['d']), int(params['ranks']), ctypes.byref(self._h)))
+        name, shape, ndim = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
+        for i in range(_lib.check(L.moe_ailut_num_params(self._h))):
+            _lib.check(L.moe_ailut_param_info(self._h, i, ctypes.byref(name), shape, ctypes.byref(ndim)))
+            a = np.ascontiguousarray(params[name.value.decode()], np.float32)
+            _lib.check(L.moe_ailut_set_param(self._h, name.value, a.ctypes.data, (ctypes.c_int64 * 4)(*a.shape), a.ndim))
+        _lib.check(L.moe_ailut_finalize(self._h, device))
+
+    def guards(self, stream=None):
+        """How many guard bytes between the handle's device buffers, and parameters, no longer hold what finalize wrote (moe_ailut_guards)."""
+        bad = ctypes.c_int64()
+        _lib.check(_lib.lib().moe_ailut_guards(self._h, ctypes.byref(bad), stream))
+        return int(bad.value)
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h and _lib._lib is not None:
+            _lib._lib.moe_ailut_destroy(h)
+
+
+def readLut3d(handle, stream=None):
+    """(table float32 (3, d, d, d), vertices float32 (3, d)) of a _LutHandle as they stand on the device behind `stream`'s work (moe_lut3d_read; synchronises it)."""
+    d = handle.info()['d']
+    table, vertices = np.empty((3, d, d, d), np.float32), np.empty((3, d), np.float32)
+    _lib.check(_lib.lib().moe_lut3d_read(handle._h, table.ctypes.data, vertices.ctypes.data, stream))
+    return table, vertices
+
+
+def ailut(params, srcBits=16, bits=16, order='bgr', strength=1.0, dither=None, tableOut=None):
+    """The image-adaptive 3D LUT (moe_ailut_run + moe_lut3d_run; the definition: lut3d.apply with ailut.generate(ailut.thumbnail(frame))'s table): f(src_dev, out, h,
+    w) as lut3d's f, but the table is the one the generator net writes for THIS frame -- eight launches from the frame's thumbnail to the table in the handle's own
+    device layout, then the LUT's launch, all on the current stream, no host round trip.  params: ailut.loadParams' dict.  tableOut: a callable handed every frame's
+    (table, vertices) behind its launches -- it synchronises the stream, so it is for a caller who wants the tables (lut3d.formatCube), not for speed.  f.read(device)
+    returns the (table, vertices) of the last frame queued on that device (it synchronises too); f.generator(device) / f.table(device) are the two handles."""
+    from . import ailut as _net, lut3d as _def
+    if not isinstance(params, dict) or 'd' not in params or 'ranks' not in params:
+        raise ValueError("ailut: 'params' is ailut.loadParams' dict")
+    for name, b in (('srcBits', srcBits), ('bits', bits)):
+        if b not in (8, 16):
+            raise ValueError('ailut: {} must be 8 or 16, got {!r}'.format(name, b))
+    if order not in _def.ORDERS:
+        raise ValueError("ailut: 'order' {!r} is not supported ({})".format(order, ', '.join(_def.ORDERS)))
+    strength = float(strength)
+    if not math.isfinite(strength):
+        raise ValueError("ailut: 'strength' {!r} is not finite".format(strength))
+    for key in _net.paramShapes(params['d'], params['ranks']):
+        if key not in params:
+            raise ValueError("ailut: 'params' has no '{}'".format(key))
+    if tableOut is not None and not callable(tableOut):
+        raise ValueError("ailut: 'tableOut' is a callable taking (table, vertices)")
+    qf = ditherFlags('ailut', dither, bits, 'rgb')
+    oid = 1 if order == 'rgb' else 0          # MOE_ORDER_RGB / MOE_ORDER_BGR
+    d, handles = int(params['d']), {}
+
+    def handle(device):
+        if device not in handles:          # the table handle starts as the identity; every run overwrites it
+            handles[device] = (_AilutHandle(params, device.index or 0), _LutHandle(_def.identity(d), _def.uniform(d), device.index or 0))
+        return handles[device]
+
+    def f(src_dev, out, h, w):
+        n = 3 * int(h) * int(w)
+        _flatPair('ailut', 'buffers', src_dev, n * (srcBits // 8), out, n * (bits // 8))
+        cur = torch.cuda.current_stream(src_dev.device)
+        gen, lut = handle(src_dev.device)
+        _lib.check(_lib.lib().moe_ailut_run(gen._h, src_dev.data_ptr(), srcBits, int(h), int(w), oid, lut._h, cur.cuda_stream))
+        _lib.check(_lib.lib().moe_lut3d_run(lut._h, src_dev.data_ptr(), srcBits, int(h), int(w), out.data_ptr(), bits | qf, oid, strength, cur.cuda_stream))
+        src_dev.record_stream(cur)
+        if tableOut is not None:
+            tableOut(*readLut3d(lut, cur.cuda_stream))
+        return out
+
+    def dev(device):
+        return torch.device(device) if device is not None else torch.device(config.device())
+    f.generator = lambda device=None: handle(dev(device))[0]
+    f.table = lambda device=None: handle(dev(device))[1]
+    f.read = lambda device=None: readLut3d(handle(dev(device))[1], torch.cuda.current_stream(dev(device)).cuda_stream)
     return f
 
 

@@ -50,14 +50,18 @@ With {'op': 'lut', 'file': path} or {'op': 'lut', 'table': array, 'vertices': ar
 interleaved RGB samples both builders end the chain in a 3D LUT: whatever edge wrote the frame writes it at 16 bits into one intermediate, and one moe_lut3d_run --
 the reference's AiLUT transform, a trilinear lookup over non-uniform vertices, with the strength blend and the quantiser -- writes the frame at the depth asked for
 (lut3d.apply is the definition).
+
+With {'op': 'dehaze', 'model': 'AiLUT_sRGB_3' | 'AiLUT_XYZ_3', 'strength': s} -- the reference's own step (python/dehaze.py:27-28) -- in that place the table is made
+per frame: moe_ailut_run, the AiLUT generator net, reads the 16-bit intermediate and writes the table the moe_lut3d_run behind it applies (ailut.generate is the
+definition).  Every other 'dehaze' model stays NotImplementedError.
 """
 import math
 import time
 from functools import reduce
 
-from . import _lib, lut3d as _lut3d, pixfmt, quant, reuse as _reuse, runDN, runSR
+from . import _lib, ailut as _ailut, lut3d as _lut3d, pixfmt, quant, reuse as _reuse, runDN, runSR
 from .config import config
-from .imageProcess import (LUMA_KEYS, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, guidedChroma, lumaChroma, lumaKeys,
+from .imageProcess import (LUMA_KEYS, ailut as ailutSamples, RGBFilter, _RGBFilter, apply, doCrop, doCropLuma, doCropOut, doCropPlanes, doCropYuv, extractAlpha, filterOut, fitPixels, fitPlanes, fromPlanes, identity, guidedChroma, lumaChroma, lumaKeys,
                            lumaMerge, lumaSplit, lut3d as lutSamples, mergeAlpha, planesToRGB, readFile, resampleChroma, resize, toBuffer, toFloat, toNumPy, toOutput, toPlanes, toTorch, toYuv, writeFile, _DT, _outStorage)
 
 stepOpts = dict(SR={'toInt': ['scale', 'ensemble'], 'getOpt': runSR}, DN={'toFloat': ['strength'], 'getOpt': runDN},
@@ -429,12 +433,20 @@ def _lutStep(steps, planar, bitDepth=None):
     both or neither of 'file' / 'table', 'vertices' without 'table', a planar Y'CbCr sink, a strength that is not finite, and what lut3d.parseCube / lut3d.check
     refuse of the table."""
     import numpy as np
-    luts = [s for s in steps if s.get('op') == 'lut']
+    for t in steps:          # (before anything else: the key that is not in this change is named as such wherever it stands)
+        if t.get('op') == 'dehaze' and t.get('model') in _ailut.NOT_HERE:
+            raise NotImplementedError("dehaze: 'model': '{}': {}".format(t['model'], _ailut.NOT_HERE[t['model']]))
+    luts = [s for s in steps if s.get('op') == 'lut' or _isAilut(s)]
     if not luts:
         return None
     if len(luts) > 1:
+        if any(_isAilut(t) for t in luts):
+            raise ValueError("dehaze: 'model': '{}' writes the chain's one colour table: no 'lut' step and no second 'AiLUT_*' step beside it (the chain has {})".format(
+                [t for t in luts if _isAilut(t)][0]['model'], len(luts)))
         raise ValueError("lut: a chain holds one 'lut' step at most, this one has {}".format(len(luts)))
     s = luts[0]
+    if _isAilut(s):
+        return _ailutStep(steps, s, planar, bitDepth)
     work = [t for t in steps if t.get('op') not in ('file', 'buffer', 'output')]
     if s is not work[-1]:
         raise ValueError("lut: the 'lut' step must be the last compute step of the chain: it writes the frame's samples")
@@ -471,11 +483,62 @@ def _lutStep(steps, planar, bitDepth=None):
         table = np.asarray(s['table'], np.float32)
         vertices = np.asarray(s['vertices'], np.float32) if s.get('vertices') is not None else (_lut3d.uniform(table.shape[1]) if table.ndim == 4 else None)
         table, vertices = _lut3d.check(table, vertices)
-    return dict(table=table, vertices=vertices, strength=strength, order=order)
+    return dict(table=table, vertices=vertices, strength=strength, order=order, op='lut', edge='+lut')
+
+
+def _isAilut(s):
+    return s.get('op') == 'dehaze' and s.get('model') in _ailut.MODELS
+
+
+def _ailutStep(steps, s, planar, bitDepth):
+    """_lutStep's dict for {'op': 'dehaze', 'model': 'AiLUT_sRGB_3' | 'AiLUT_XYZ_3', 'strength': s} (the reference's own spelling: python/dehaze.py:27-28,33-41): the
+    step goes where a 'lut' step goes and the chain is built as one, but the table is written per frame by the generator net (ailut.generate is the definition;
+    DESIGN.md section 23).  The checkpoint is read from config.modelRoot at the reference's path (ailut.MODELS) -- a file that is not there is the error every family
+    raises -- and checked by ailut.loadParams.  'tableOut': a callable handed every frame's (table, vertices).  ValueError naming the key, before any model is
+    loaded: the step anywhere but last, a planar Y'CbCr sink behind it, a strength that is not finite."""
+    import os
+    from .weights import load_state_dict_file
+    key = "dehaze: 'model': '{}'".format(s['model'])
+    work = [t for t in steps if t.get('op') not in ('file', 'buffer', 'output')]
+    if s is not work[-1]:
+        raise ValueError("{} must be the last compute step of the chain: it writes the frame's samples".format(key))
+    try:
+        strength = float(s.get('strength', 1.0))
+    except (TypeError, ValueError):
+        raise ValueError("{}: 'strength' {!r} is not a number".format(key, s.get('strength')))
+    if not math.isfinite(strength):
+        raise ValueError("{}: 'strength' {!r} is not finite".format(key, s['strength']))
+    if planar:
+        if planar[1] not in pixfmt.RGB_FORMATS:
+            raise ValueError("{}: a planar Y'CbCr sink ('pixFmt': '{}') behind the step is not in this change: the step writes interleaved RGB samples "
+                             "(output 'pixFmt': {})".format(key, planar[1], ', '.join(pixfmt.RGB_FORMATS)))
+        if 'order' in s:
+            raise ValueError("{}: 'order' does not apply to a chain on planar frames: the output step's 'pixFmt' carries it".format(key))
+        order = pixfmt.RGB_FORMATS[planar[1]][1]
+    else:
+        for o in steps:
+            if o.get('op') == 'output' and o.get('pixFmt') is not None:
+                raise ValueError("{}: a planar Y'CbCr sink ('pixFmt': '{}') behind the step is not in this change: the step writes interleaved RGB samples".format(key, o['pixFmt']))
+        order = s.get('order', 'bgr' if steps[0].get('op') == 'buffer' else 'rgb')
+        if order not in _lut3d.ORDERS:
+            raise ValueError("{}: 'order' {!r} is not supported ({})".format(key, order, ', '.join(_lut3d.ORDERS)))
+        if bitDepth not in (8, 16):
+            raise ValueError("{}: the step writes 8- or 16-bit samples, the chain's bitDepth is {!r}".format(key, bitDepth))
+    if s.get('tableOut') is not None and not callable(s['tableOut']):
+        raise ValueError("{}: 'tableOut' is a callable taking (table, vertices)".format(key))
+    params = _ailut.loadParams(load_state_dict_file(os.path.join(config.modelRoot, _ailut.MODELS[s['model']])))
+    return dict(params=params, strength=strength, order=order, tableOut=s.get('tableOut'), op='dehaze', edge='+ailut')
 
 
 def _withoutLut(steps):
-    return [s for s in steps if s.get('op') != 'lut']
+    return [s for s in steps if s.get('op') != 'lut' and not _isAilut(s)]
+
+
+def _lutRunner(lut, srcBits, bits, dither):
+    """f(src_dev, out, h, w) of _lutStep's dict: a fixed table (imageProcess.lut3d), or the generator net in front of it (imageProcess.ailut)."""
+    if 'params' in lut:
+        return ailutSamples(lut['params'], srcBits, bits, lut['order'], lut['strength'], dither, lut['tableOut'])
+    return lutSamples(lut['table'], lut['vertices'], srcBits, bits, lut['order'], lut['strength'], dither)
 
 
 def _lutLast(lut, bitDepth, dither):
@@ -484,7 +547,7 @@ def _lutLast(lut, bitDepth, dither):
     code's high byte (the truncating quantiser's sample)."""
     import numpy as np
     import torch
-    run = lutSamples(lut['table'], lut['vertices'], 16, bitDepth, lut['order'], lut['strength'], dither)
+    run = _lutRunner(lut, 16, bitDepth, dither)
 
     def f(mid):
         H, W, C = mid.shape
@@ -589,11 +652,11 @@ def _genProcessPlanes(steps, fmts, dither=None, lut=None):
         dst, dither, rgbDither = PLANAR16, None, dither
     if lut:          # a 'lut' step: the RGB frame at 16 bits without 'dither', then one moe_lut3d_run at the pixFmt's depth: the key governs the step's quantiser
         lutBits = pixfmt.RGB_FORMATS[rgb[0]][0]
-        lutRun = lutSamples(lut['table'], lut['vertices'], 16, lutBits, lut['order'], lut['strength'], rgbDither)
+        lutRun = _lutRunner(lut, 16, lutBits, rgbDither)
         rgb, rgbDither = (LUT_FMT16[rgb[0]],) + tuple(rgb[1:]), None
     funcs, nodes, scale, _ = _planeChain(steps, False)
     if lut:
-        nodes.append(dict(op='lut'))
+        nodes.append(dict(op=lut['op']))
     quantise = toPlanes(pixfmt.FORMATS[dst], dither)
     chroma, resamplers = _planeChroma(steps), {}
     fit, quantise16, fitters = _planeFit(steps), toPlanes(16), {}
@@ -726,7 +789,7 @@ def genProcess(steps, bitDepth=8, outFile=None):
         funcs += [fused] if fused else [toFloat, toOutput(bitDepth, dither)]
     if lut:          # the frame above at 16 bits, on the device; one moe_lut3d_run writes the samples handed out
         funcs.append(_lutLast(lut, bitDepth, dither))
-        nodes.append(dict(op='lut'))
+        nodes.append(dict(op=lut['op']))
     if has_file and outFile is not None:
         funcs.append(lambda im: writeFile(im, outFile, ctx))
     if has_buffer:
@@ -1143,7 +1206,7 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
         dst, dither, rgbDither = PLANAR16, None, dither
     if lut:          # a 'lut' step: the RGB frame at 16 bits without 'dither', then one moe_lut3d_run at the pixFmt's depth: the key governs the step's quantiser
         lutBits = pixfmt.RGB_FORMATS[rgb[0]][0]
-        lutRun = lutSamples(lut['table'], lut['vertices'], 16, lutBits, lut['order'], lut['strength'], rgbDither)
+        lutRun = _lutRunner(lut, 16, lutBits, rgbDither)
         rgb, rgbDither = (LUT_FMT16[rgb[0]],) + tuple(rgb[1:]), None
     bitDepth = 8 if pixfmt.FORMATS[src] == 8 else 16
     _checkRing(depth, bitDepth)          # (before any model is loaded)
@@ -1222,9 +1285,9 @@ def _genFrameStreamPlanes(steps, fmts, width, height, depth, timing, reuse=False
             toRGB(planar['buf'], out)
     if lut:          # the RGB edge above writes one intermediate frame at 16 bits (compute queue only), then one moe_lut3d_run into the slot's frame, every frame
         rgbBytes, rgbEdge, mid16 = outBytes, edge, {}
-        edgeName += '+lut'
+        edgeName += lut['edge']
         outBytes = 3 * fw * fh * (lutBits // 8)
-        nodes.append(dict(op='lut'))
+        nodes.append(dict(op=lut['op']))
 
         def edge(y, c, out, *reuses):
             if 'buf' not in mid16:          # allocated once, at the first frame
@@ -1402,9 +1465,9 @@ def genFrameStream(steps, width, height, depth=2, timing=False, reuse=False, vie
         nodes.append(dict(op='resize', mode=fit['fit']))
     if lut:          # the edge (and the fit) above write one intermediate frame at 16 bits (compute queue only); one moe_lut3d_run from it writes the slot's frame, every frame
         import torch
-        lutRun, mid16, (lh, lw) = lutSamples(lut['table'], lut['vertices'], 16, bitDepth, lut['order'], lut['strength'], lutDither), {}, outHW
-        edgeName += '+lut'
-        nodes.append(dict(op='lut'))
+        lutRun, mid16, (lh, lw) = _lutRunner(lut, 16, bitDepth, lutDither), {}, outHW
+        edgeName += lut['edge']
+        nodes.append(dict(op=lut['op']))
 
         def lutMid(dev):
             if 'buf' not in mid16:          # allocated once, at the first frame
